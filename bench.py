@@ -12,10 +12,22 @@ to uniform random +-1e-3 (rng seed 0), fp32, curl-stencil only.  A "step" = one 
 timed region.
 
 On one GPU the library advances this workload TWO time steps per sweep (fused2_step_kernel, bit-identical
-to single sweeps): K steps are K / 2 launches.  `single_steps` on the line is the same
-engine advancing one step per sweep.
+to single sweeps): K steps are K / 2 launches.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up (W steps), times ONE region of exactly K steps (`--repeats R`: R regions, the
+median is reported), writes the fields if `--dump-outputs DIR` is given, and prints the line: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step), the tile shape and the
+placement the library chose.  Everything else takes runs of its own and comes with `--full` (there `--repeats`
+defaults to 5): the roofline run, `single_steps` (the same engine advancing one step per sweep), the secondary
+workloads V1 / V2 / va / V3 / V4, the RCCL proof of a multi-rank run and the CPU baseline.
+
+--dump-outputs DIR: after the timed region (before any --full measurement touches the engine), what the timed
+path leaves in the six field arrays, float32: DIR/<E|H><x|y|z>_zmid.npy, the whole centre z plane (up to
+--size 1024), and DIR/<E|H><x|y|z>_sample.npy, the cells at a fixed seeded sample of flat (z, y, x) indices
+(dump_sample_index), in increasing index order.  30 MB at 512^3, at most 48 MB; the same arguments give the
+same inputs, so two builds can be compared output for output.
+
+Extra objects on the --full JSON line:
   roofline     — dominant kernel: algorithmic bytes per launch (the kernel's OWN minimum: 48 B per cell per launch,
                  whether the launch advances one time step or two — see roofline_entry; the cell rate against the
                  throughput roofline of SURVEY.md 8(d)'s 72 B two-pass kernel is reported beside it under an explicit
@@ -236,7 +248,49 @@ def init_plane(c, k, n):
     return _INIT[key]
 
 
-MIN_TIMED_STEPS = 100        # a timed region shorter than this is raised to it (20 steps are 14 ms)
+MIN_TIMED_STEPS = 100        # steps of each timed region of the --full single-steps leg
+
+FIELD_NAMES = ("Ex", "Ey", "Ez", "Hx", "Hy", "Hz")      # component ids 0..5 (include/fdtd_hip.h)
+DUMP_SAMPLES = 1 << 20       # cells drawn per component for --dump-outputs
+DUMP_PLANE_MAX_N = 1024      # the centre planes go with them up to this size (6 x (4 + 4) MB at 1024^3: under 64 MB in all)
+DUMP_SEED = 20261016
+
+
+def dump_sample_index(n: int) -> np.ndarray:
+    """The fixed sample of --dump-outputs: sorted distinct flat indices (z * n + y) * n + x of the n^3 grid."""
+    cells = n ** 3
+    if cells <= DUMP_SAMPLES:
+        return np.arange(cells, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, cells, DUMP_SAMPLES, dtype=np.int64))
+
+
+def dump_outputs(eng, out_dir, n, z0, z1, rank, world, dist):
+    """Write the six field arrays of `eng` as --dump-outputs describes (module docstring).  Every rank reads its own
+    slab; rank 0 gathers the sample in index order (the slabs are contiguous ranges of z) and writes the files."""
+    idx = dump_sample_index(n)
+    lo, hi = np.searchsorted(idx // (n * n), [z0, z1])
+    local = idx[lo:hi] - z0 * n * n
+    kmid = n // 2
+    parts = {}
+    for c, name in enumerate(FIELD_NAMES):
+        f = eng.get_field(c)
+        parts[name + "_sample"] = np.ascontiguousarray(f.reshape(-1)[local], dtype=np.float32)
+        if n <= DUMP_PLANE_MAX_N and z0 <= kmid < z1:
+            parts[name + "_zmid"] = np.array(f[kmid - z0], dtype=np.float32)
+        del f
+    if world > 1:
+        every = [None] * world
+        dist.all_gather_object(every, parts)
+        if rank != 0:
+            return
+        parts = {}
+        for name in FIELD_NAMES:
+            parts[name + "_sample"] = np.concatenate([p[name + "_sample"] for p in every])
+            if n <= DUMP_PLANE_MAX_N:
+                parts[name + "_zmid"] = next(p[name + "_zmid"] for p in every if name + "_zmid" in p)
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in parts.items():
+        np.save(os.path.join(out_dir, key + ".npy"), a)
 
 
 def secondary_workload(HipEngine, L, n, workload, device, args, steps=100, repeats=3):
@@ -337,13 +391,19 @@ def main():
     ap.add_argument("--placement-tries", type=int, default=-1, help="FDTD_OPT_PLACEMENT_TRIES (0 = keep the first allocations: profiling "
                     "runs, so that the kernel statistics hold the timed sweeps only)")
     ap.add_argument("--opt", action="append", default=[], help="extra engine option NAME=VALUE (tidy3d_amd.lib.OPT_*), e.g. OPT_PML_POOL=0; repeatable")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the secondary V2 (materials + CPML) measurement")
-    ap.add_argument("--no-single-steps", action="store_true", help="skip the single-steps leg of a run that goes out in step pairs "
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: roofline run, single steps, secondary "
+                    "workloads, RCCL proof (N > 1), CPU baseline; --repeats defaults to 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the fields after the last timed step to DIR/*.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each; the median is reported "
+                    "(default 1, 5 with --full)")
+    ap.add_argument("--no-workloads", action="store_true", help="--full: skip the secondary workload measurements")
+    ap.add_argument("--no-single-steps", action="store_true", help="--full: skip the single-steps leg of a run that goes out in step pairs "
                     "(profiling runs: the counters then hold the launches of the pairs only)")
     ap.add_argument("--sweep", action="store_true", help="A/B kernel launch parameters (N=1)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     import torch
     import torch.distributed as dist
@@ -379,9 +439,9 @@ def main():
     if world != args.gpus and rank == 0:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE {world}", file=sys.stderr)
 
-    n, K_asked, W = args.n, args.steps, args.warmup
-    # timed regions of at least MIN_TIMED_STEPS steps: a caller that asks for fewer gets that many, and the line says so
-    K = max(K_asked, MIN_TIMED_STEPS) if not os.environ.get("BENCH_EMULATE") else K_asked
+    n, K, W = args.n, args.steps, args.warmup
+    if K < 1 or W < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     spec = build_spec(n, K + W + 64, args.workload)
     slabs = split_slabs(n, world)
     eng = HipEngine(spec, lib=lib, device=local_rank, variant=args.variant, z_chunk=args.zchunk,
@@ -450,16 +510,12 @@ def main():
     cells = n ** 3
     value = cells * K / elapsed / 1e6
 
-    # roofline of the dominant kernel: separate short run with per-launch hipEvents on the launch stream
-    eng.set_option(L.OPT_FLAGS, L.FLAG_TIME_KERNELS)
-    kr = min(K, 100)            # (round 6: 100 steps, not 20 — ten launches straight after the timed region read 2 - 5 % long)
-    eng.run(kr)
-    st = eng.stats()
-    eng.set_option(L.OPT_FLAGS, 0)
-    local_cells = (z1 - z0) * n * n
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, n, z0, z1, rank, world, dist)
+    st = eng.stats()              # what the timed region ran with: tile shape, placement
     out = {
         "metric": "Mcells/s on 512^3 Yee grid", "value": value, "unit": "Mcells/s",
-        "n_gpus": world, "steps": K, "steps_requested": K_asked, "warmup": W, "ms_per_step": elapsed / K * 1e3,
+        "n_gpus": world, "steps": K, "steps_requested": K, "warmup": W, "ms_per_step": elapsed / K * 1e3,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
         "data": "synthetic",
         "config": {"workload": f"{args.workload}: {WORKLOADS[args.workload]}; {n}^3 Yee cells, Ez point dipole "
@@ -479,53 +535,61 @@ def main():
                       "note": "box-to-box spread of the headline (181-198 Gcells/s over round 5's visits) is this effect, not the kernel"},
         "repeats": {"n": R, "statistic": "median", "ms_per_step": [e / K * 1e3 for e in samples],
                     "min_ms_per_step": min(samples) / K * 1e3, "max_ms_per_step": max(samples) / K * 1e3},
-        "roofline": roofline_entry(st, kr, local_cells, cells, K, elapsed, world, args.workload, spec),
-        "schedule": {"two_steps_per_sweep_pairs_in_roofline_run": int(st.fused2_pairs),
-                     "two_step_pairs_in_roofline_run": int(st.two_step_pairs), "tblock_planes": int(st.tblock_planes),
-                     "stream_overlap": int(st.stream_overlap), "stream_retries": int(st.stream_retries)},
     }
-    if world > 1:
-        # proof that the halo communicator (RCCL; the emulator's shim under BENCH_EMULATE) spans `world` ranks: every rank
-        # reports what ncclCommCount / ncclCommUserRank return for ITS communicator
-        mine = torch.tensor([int(st.comm_ranks), int(st.comm_rank), z1 - z0, int(st.fused2_pairs), int(st.fused2_shape), int(st.fused2_off_reason)],
-                            dtype=torch.int64, device="cpu" if emulate else "cuda")
-        allc = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allc, mine)
-        rows = [[int(v) for v in x.tolist()] for x in allc]
-        med = np.median(np.asarray(rank_samples), axis=0) / K * 1e3
-        out["rccl"] = {"rccl_ranks": sorted({r[0] for r in rows}), "comm_user_ranks": [r[1] for r in rows],
-                       "planes_per_rank": [r[2] for r in rows],
-                       # z-slab ranks advance two time steps per sweep too (the planes next to a cut by single steps on the comm
-                       # stream, shipping after each): step pairs of every rank in the roofline run, their tile shape, and — where
-                       # a rank took none — why (FDTD_F2_OFF_*)
-                       "two_steps_per_sweep": {"steps_in_this_run": kr, "pairs_per_rank": [r[3] for r in rows],
-                                               "waves_per_workgroup": [r[4] & 63 for r in rows], "planes_per_chunk": [r[4] >> 6 for r in rows],
-                                               "off_reason_per_rank": [r[5] for r in rows]},
-                       "ms_per_step_per_rank": [float(v) for v in med],
-                       "ms_per_step_rank_min": float(med.min()), "ms_per_step_rank_max": float(med.max())}
-    if world == 1 and int(st.fused2_pairs) > 0 and not args.no_single_steps:
-        # the same engine (same placement of the arrays) advancing ONE step per sweep: what the headline was before
-        # the two-step kernel, and what every run outside its scope still gets
-        eng.set_option(L.OPT_TWOSTEP, 0)
-        eng.run(10)
-        ss = [timed(MIN_TIMED_STEPS) for _ in range(3)]
-        eng.set_option(L.OPT_TWOSTEP, -1)
-        el1 = float(np.median(ss))
-        out["single_steps"] = {"value": cells * MIN_TIMED_STEPS / el1 / 1e6, "unit": "Mcells/s", "ms_per_step": el1 / MIN_TIMED_STEPS * 1e3,
-                               "steps": MIN_TIMED_STEPS, "repeats": 3, "kernel": "fused_step_kernel"}
-    if world == 1 and not emulate and args.workload == "v0" and not args.no_workloads:
-        # the workload every real simulation resembles (materials + CPML on all faces), same grid, same box
-        eng.close()
-        eng = None
-        out["workloads"] = {"v2": secondary_workload(HipEngine, L, n, "v2", local_rank, args),
-                            # materials inside PEC walls: the two-step sweep's materials instantiation
-                            "v1": secondary_workload(HipEngine, L, n, "v1", local_rank, args),
-                            # an open problem without CPML: Absorber boundaries, damped inside the two-step sweep
-                            "va": secondary_workload(HipEngine, L, n, "va", local_rank, args),
-                            # + a Lorentz pole in the sphere — K4 (ADE) inside the step pairs since round 6
-                            "v3": secondary_workload(HipEngine, L, n, "v3", local_rank, args),
-                            # + a closed flux box with a running DFT at three frequencies — K6 inside the pairs
-                            "v4": secondary_workload(HipEngine, L, n, "v4", local_rank, args)}
+    if args.full:
+        # roofline of the dominant kernel: separate short run with per-launch hipEvents on the launch stream
+        eng.set_option(L.OPT_FLAGS, L.FLAG_TIME_KERNELS)
+        kr = min(K, 100)            # (round 6: 100 steps, not 20 — ten launches straight after the timed region read 2 - 5 % long)
+        eng.run(kr)
+        st = eng.stats()
+        eng.set_option(L.OPT_FLAGS, 0)
+        local_cells = (z1 - z0) * n * n
+        out["roofline"] = roofline_entry(st, kr, local_cells, cells, K, elapsed, world, args.workload, spec)
+        out["schedule"] = {"two_steps_per_sweep_pairs_in_roofline_run": int(st.fused2_pairs),
+                           "two_step_pairs_in_roofline_run": int(st.two_step_pairs), "tblock_planes": int(st.tblock_planes),
+                           "stream_overlap": int(st.stream_overlap), "stream_retries": int(st.stream_retries)}
+        if world > 1:
+            # proof that the halo communicator (RCCL; the emulator's shim under BENCH_EMULATE) spans `world` ranks: every rank
+            # reports what ncclCommCount / ncclCommUserRank return for ITS communicator
+            mine = torch.tensor([int(st.comm_ranks), int(st.comm_rank), z1 - z0, int(st.fused2_pairs), int(st.fused2_shape), int(st.fused2_off_reason)],
+                                dtype=torch.int64, device="cpu" if emulate else "cuda")
+            allc = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allc, mine)
+            rows = [[int(v) for v in x.tolist()] for x in allc]
+            med = np.median(np.asarray(rank_samples), axis=0) / K * 1e3
+            out["rccl"] = {"rccl_ranks": sorted({r[0] for r in rows}), "comm_user_ranks": [r[1] for r in rows],
+                           "planes_per_rank": [r[2] for r in rows],
+                           # z-slab ranks advance two time steps per sweep too (the planes next to a cut by single steps on the comm
+                           # stream, shipping after each): step pairs of every rank in the roofline run, their tile shape, and — where
+                           # a rank took none — why (FDTD_F2_OFF_*)
+                           "two_steps_per_sweep": {"steps_in_this_run": kr, "pairs_per_rank": [r[3] for r in rows],
+                                                   "waves_per_workgroup": [r[4] & 63 for r in rows], "planes_per_chunk": [r[4] >> 6 for r in rows],
+                                                   "off_reason_per_rank": [r[5] for r in rows]},
+                           "ms_per_step_per_rank": [float(v) for v in med],
+                           "ms_per_step_rank_min": float(med.min()), "ms_per_step_rank_max": float(med.max())}
+        if world == 1 and int(st.fused2_pairs) > 0 and not args.no_single_steps:
+            # the same engine (same placement of the arrays) advancing ONE step per sweep: what the headline was before
+            # the two-step kernel, and what every run outside its scope still gets
+            eng.set_option(L.OPT_TWOSTEP, 0)
+            eng.run(10)
+            ss = [timed(MIN_TIMED_STEPS) for _ in range(3)]
+            eng.set_option(L.OPT_TWOSTEP, -1)
+            el1 = float(np.median(ss))
+            out["single_steps"] = {"value": cells * MIN_TIMED_STEPS / el1 / 1e6, "unit": "Mcells/s", "ms_per_step": el1 / MIN_TIMED_STEPS * 1e3,
+                                   "steps": MIN_TIMED_STEPS, "repeats": 3, "kernel": "fused_step_kernel"}
+        if world == 1 and not emulate and args.workload == "v0" and not args.no_workloads:
+            # the workload every real simulation resembles (materials + CPML on all faces), same grid, same box
+            eng.close()
+            eng = None
+            out["workloads"] = {"v2": secondary_workload(HipEngine, L, n, "v2", local_rank, args),
+                                # materials inside PEC walls: the two-step sweep's materials instantiation
+                                "v1": secondary_workload(HipEngine, L, n, "v1", local_rank, args),
+                                # an open problem without CPML: Absorber boundaries, damped inside the two-step sweep
+                                "va": secondary_workload(HipEngine, L, n, "va", local_rank, args),
+                                # + a Lorentz pole in the sphere — K4 (ADE) inside the step pairs since round 6
+                                "v3": secondary_workload(HipEngine, L, n, "v3", local_rank, args),
+                                # + a closed flux box with a running DFT at three frequencies — K6 inside the pairs
+                                "v4": secondary_workload(HipEngine, L, n, "v4", local_rank, args)}
 
     if args.sweep and world == 1 and eng is not None:
         res = []
@@ -539,7 +603,7 @@ def main():
                 print(json.dumps(res[-1]), file=sys.stderr, flush=True)
         out["sweep"] = res
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline()
     if eng is not None:
         eng.close()

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=${1:-r6v}; O=$R/gpu
 for ROUND in 1 2 3; do
   for V in ${AB_VARIANTS:-exj noexj}; do
     if [ $V = exj ] || [ $V = default ]; then unset TIDY3D_AMD_LIBRARY; else export TIDY3D_AMD_LIBRARY=$R/variants/libfdtd_hip_$V.so; fi
-    timeout 400 python bench.py --no-cpu ${AB_BENCH_ARGS:-} > $O/bench_${V}_$ROUND.json 2> $O/bench_${V}_$ROUND.err
+    timeout 400 python bench.py --full --no-cpu ${AB_BENCH_ARGS:-} > $O/bench_${V}_$ROUND.json 2> $O/bench_${V}_$ROUND.err
     python - <<PY
 import json
 d = json.load(open("$O/bench_${V}_$ROUND.json"))

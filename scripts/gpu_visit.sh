@@ -4,7 +4,7 @@
 # Output goes to gpurun_out/TAG/ (merged back by gpurun); what is to be judged is copied from there into profiles/<round>/.
 # Stages:
 #   tests        the whole GPU suite (pytest -m gpu)
-#   bench        the driver's default bench line
+#   bench        the full bench line (bench.py --full: roofline, single steps, workloads, CPU baseline)
 #   stats        rocprofv3 --kernel-trace --stats of the bench workloads v0 (step pairs), v0 single steps, v2 (placement probe off)
 #   pmc          HBM traffic (FETCH_SIZE / WRITE_SIZE in separate passes) of v0, v0 single steps, v1, va, v2 -> pmc_*_summary.json
 #   shell        shell pairs against single steps inside one engine (scripts/probe_shell.py), 512^3 v2
@@ -22,7 +22,7 @@ for S in "$@"; do
     tests)
       timeout 2400 python -m pytest tests -q -m gpu -x --durations=15 > $O/pytest_gpu.log 2>&1; tail -4 $O/pytest_gpu.log;;
     bench)
-      timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+      timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
       python - <<PY
 import json
 d = json.load(open("$O/bench.json")); r = d["roofline"]
@@ -88,7 +88,7 @@ PY
       find $O -name '*counter_collection*' -size +4M -delete
       cd $R; head -c 1500 $O/sq_counters.json;;
     bench1024)
-      timeout 600 python bench.py --size 1024 --steps 20 --warmup 4 --repeats 3 --no-cpu --no-workloads > $O/bench_1024.json 2> $O/bench_1024.err; cut -c1-200 $O/bench_1024.json;;
+      timeout 600 python bench.py --full --size 1024 --steps 20 --warmup 4 --repeats 3 --no-cpu --no-workloads > $O/bench_1024.json 2> $O/bench_1024.err; cut -c1-200 $O/bench_1024.json;;
     *) echo "unknown stage $S";;
   esac
 done
