@@ -199,10 +199,16 @@ int fdtd_add_ade(FdtdSolver* h, int comp, int64_t n_cells, const uint32_t* cell_
  * at n nodes.  The sweep advances every component with the diagonal of eps^-1 (table media); behind it
  *     E_comp[cell[i]] += sum_{s<8} w_new[8i+s] * Eb^{n+1}[nbr[8i+s]] - w_old[8i+s] * Eb^n[nbr[8i+s]],
  * slots 0-3: component (comp+1)%3, slots 4-7: (comp+2)%3; nbr = 0xFFFFFFFF: no node (weight ignored).  The host forms
- * w_new = (dt/eps0) g / Cb(nbr), w_old = w_new * Ca(nbr) (tidy3d_amd/spec.py AnisoSet).  Single steps only; not on z-slabs,
- * not with Bloch boundaries. */
+ * w_new = (dt/eps0) g / Cb(nbr), w_old = w_new * Ca(nbr) (tidy3d_amd/spec.py AnisoSet).  Single steps only; not on z-slabs. */
 int fdtd_add_aniso(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t* cell_index, const uint32_t* nbr_index,
                    const float* w_new, const float* w_old);
+/* the same list for a pair of handles advanced by fdtd_run_bloch (give both handles the same lists, in the same order).  A slot whose
+ * neighbour lies one period away across a periodic / Bloch face names the real node on the far side (not a ghost cell; its Ca / Cb
+ * in the weights) and carries a wrap code: bits 2a, 2a+1 = the period crossed along axis a (0 = none, 1 = +1 beyond the upper
+ * face, 2 = -1 beyond the lower face).  fdtd_run_bloch multiplies that neighbour's term by exp(i sum_a s_a phase[a]) and so mixes
+ * the two parts; fdtd_run ignores the codes (phase 0). */
+int fdtd_add_aniso_bloch(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t* cell_index, const uint32_t* nbr_index,
+                         const float* w_new, const float* w_old, const uint8_t* wrap);
 
 /* current source: F[comp[p]][index[p]] += w_re[p]*Re(wave[n]) - w_im[p]*Im(wave[n]);
  * E components use wave_e (sampled at t_n + dt/2), H components wave_h (t_n);
@@ -262,7 +268,8 @@ int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user
  * cells on that axis); a Bloch z uses the ghost planes of FDTD_BC_PERIODIC z faces.  On a z-slab
  * (FDTD_BC_NEIGHBOR faces) the first handle carries the communicator (fdtd_comm_init) and both parts
  * exchange their ghost planes through it; planes that wrap around a Bloch z axis are rotated where they
- * arrive.  Monitors of the pair are read per handle; a value is re + i im. */
+ * arrive.  Fully anisotropic lists (fdtd_add_aniso_bloch) are coupled across the Bloch faces with their phases; not on
+ * z-slabs.  Monitors of the pair are read per handle; a value is re + i im. */
 int fdtd_run_bloch(FdtdSolver* h_re, FdtdSolver* h_im, int64_t n_steps, const double phase[3], const int n_real[3],
                    FdtdProgressFn progress, void* user);
 /* ref web/api/webapi.py:370 (task status incl. "diverged"), web/core/task_core.py:537 (run info) */

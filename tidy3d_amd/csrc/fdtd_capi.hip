@@ -85,6 +85,7 @@ struct AnisoGroup {                 // fdtd_aniso.hpp: the off-diagonal coupling
   long long n;
   uint32_t *cell, *nbr;
   float *w_new, *w_old, *old, *delta;
+  uint8_t* wrap;                    // [8n] wrap codes of the slots (fdtd_add_aniso_bloch), nullptr = none: read by fdtd_run_bloch only
 };
 
 struct PointSrc {
@@ -2268,6 +2269,34 @@ void aniso_apply(FdtdSolver* h, hipStream_t st) {
                        (const float*)a.delta, a.n);
 }
 
+// the same two under Bloch boundaries (fdtd_run_bloch): the Re and Im handles carry the same lists; one launch per list saves E^n
+// of both parts, one forms the deltas of both parts (slots across a Bloch face rotated by their wrap code's phase)
+void aniso_save_bloch(FdtdSolver* hr, FdtdSolver* hi, hipStream_t st) {
+  dbg_sync(hr);
+  for (size_t k = 0; k < hr->aniso.size(); ++k) {
+    AnisoGroup &ar = hr->aniso[k], &ai = hi->aniso[k];
+    const int b1 = (ar.comp + 1) % 3, b2 = (ar.comp + 2) % 3;
+    hipLaunchKernelGGL(aniso_save_bloch_kernel, dim3(nblk(8 * ar.n)), dim3(256), 0, st, (const float*)field_ptr(hr, b1),
+                       (const float*)field_ptr(hr, b2), (const float*)field_ptr(hi, b1), (const float*)field_ptr(hi, b2),
+                       (const uint32_t*)ar.nbr, ar.old, ai.old, 8 * ar.n);
+  }
+}
+void aniso_apply_bloch(FdtdSolver* hr, FdtdSolver* hi, const AnisoPhaseTab& tab, hipStream_t st) {
+  dbg_sync(hr);
+  for (size_t k = 0; k < hr->aniso.size(); ++k) {
+    AnisoGroup &ar = hr->aniso[k], &ai = hi->aniso[k];
+    const int b1 = (ar.comp + 1) % 3, b2 = (ar.comp + 2) % 3;
+    hipLaunchKernelGGL(aniso_delta_bloch_kernel, dim3(nblk(ar.n)), dim3(256), 0, st, (const float*)field_ptr(hr, b1),
+                       (const float*)field_ptr(hr, b2), (const float*)field_ptr(hi, b1), (const float*)field_ptr(hi, b2),
+                       (const uint32_t*)ar.nbr, (const uint8_t*)ar.wrap, (const float*)ar.w_new, (const float*)ar.w_old,
+                       (const float*)ar.old, (const float*)ai.old, tab, ar.delta, ai.delta, ar.n);
+  }
+  for (FdtdSolver* h : {hr, hi})
+    for (AnisoGroup& a : h->aniso)
+      hipLaunchKernelGGL(aniso_apply_kernel, dim3(nblk(a.n)), dim3(256), 0, st, field_ptr(h, a.comp), (const uint32_t*)a.cell,
+                         (const float*)a.delta, a.n);
+}
+
 void launch_ade(FdtdSolver* h, int kbeg, int kend, hipStream_t st, const FieldP* fs = nullptr) {
   dbg_sync(h);
   if (kend <= kbeg) return;
@@ -3083,24 +3112,46 @@ int fdtd_add_ade(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index,
   return 0;
 }
 
-int fdtd_add_aniso(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index, const uint32_t* nbr_index, const float* w_new,
-                   const float* w_old) {
+extern "C++" {
+namespace {
+int add_aniso(FdtdSolver* h, const char* who, int comp, int64_t n, const uint32_t* cell_index, const uint32_t* nbr_index,
+              const float* w_new, const float* w_old, const uint8_t* wrap) {
   if (!h) return -1;
-  if (comp < 0 || comp > 2) return fail(h, "fdtd_add_aniso: comp must be 0..2");
+  if (comp < 0 || comp > 2) return fail(h, "%s: comp must be 0..2", who);
   if (n <= 0) return 0;
   const uint64_t ncell = (uint64_t)n_cells(h);
-  for (int64_t i = 0; i < n; ++i) if (cell_index[i] >= ncell) return fail(h, "fdtd_add_aniso: cell index out of range");
+  for (int64_t i = 0; i < n; ++i) if (cell_index[i] >= ncell) return fail(h, "%s: cell index out of range", who);
   for (int64_t q = 0; q < 8 * n; ++q)
-    if (nbr_index[q] != kNoNode && nbr_index[q] >= ncell) return fail(h, "fdtd_add_aniso: neighbour index out of range");
+    if (nbr_index[q] != kNoNode && nbr_index[q] >= ncell) return fail(h, "%s: neighbour index out of range", who);
+  if (wrap)
+    for (int64_t q = 0; q < 8 * n; ++q) {
+      const int c = wrap[q];
+      if (c >= kWrapCodes || (c & 3) == 3 || ((c >> 2) & 3) == 3 || ((c >> 4) & 3) == 3)
+        return fail(h, "%s: bad wrap code %d", who, c);
+    }
   HIPCHK(h, hipSetDevice(h->cfg.device));
   AnisoGroup a{};
   a.comp = comp; a.n = n;
   if (dev_upload(h, &a.cell, cell_index, (size_t)n) || dev_upload(h, &a.nbr, nbr_index, (size_t)8 * n) ||
       dev_upload(h, &a.w_new, w_new, (size_t)8 * n) || dev_upload(h, &a.w_old, w_old, (size_t)8 * n) ||
-      dev_alloc(h, &a.old, (size_t)8 * n) || dev_alloc(h, &a.delta, (size_t)n))
+      dev_alloc(h, &a.old, (size_t)8 * n) || dev_alloc(h, &a.delta, (size_t)n) ||
+      (wrap && dev_upload(h, &a.wrap, wrap, (size_t)8 * n)))
     return -1;
   h->aniso.push_back(a);
   return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int fdtd_add_aniso(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index, const uint32_t* nbr_index, const float* w_new,
+                   const float* w_old) {
+  return add_aniso(h, "fdtd_add_aniso", comp, n, cell_index, nbr_index, w_new, w_old, nullptr);
+}
+
+int fdtd_add_aniso_bloch(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index, const uint32_t* nbr_index,
+                         const float* w_new, const float* w_old, const uint8_t* wrap) {
+  if (h && !wrap) return fail(h, "fdtd_add_aniso_bloch: no wrap codes");
+  return add_aniso(h, "fdtd_add_aniso_bloch", comp, n, cell_index, nbr_index, w_new, w_old, wrap);
 }
 
 int fdtd_add_point_source(FdtdSolver* h, int64_t n, const int32_t* comp, const uint32_t* cell, const float* w_re,
@@ -4514,7 +4565,13 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
                    FdtdProgressFn progress, void* user) {
   if (!hr || !hi) return -1;
   if (hi->comm) return fail(hr, "fdtd_run_bloch: the communicator of a z-slab belongs to the first (real-part) handle");
-  if (!hr->aniso.empty() || !hi->aniso.empty()) return fail(hr, "fdtd_run_bloch: fully anisotropic media are not available together with Bloch boundaries");
+  // fully anisotropic bodies: the Re handle's lists (wrap codes included) drive both parts; the Im handle's carry the same rows
+  const bool aniso = !hr->aniso.empty();
+  if (hi->aniso.size() != hr->aniso.size())
+    return fail(hr, "fdtd_run_bloch: the two solvers must carry the same fully anisotropic lists");
+  for (size_t k = 0; k < hr->aniso.size(); ++k)
+    if (hi->aniso[k].comp != hr->aniso[k].comp || hi->aniso[k].n != hr->aniso[k].n)
+      return fail(hr, "fdtd_run_bloch: the two solvers must carry the same fully anisotropic lists");
   for (int a = 0; a < 3; ++a)
     if (hr->mirror_wall[a] >= 0 || hi->mirror_wall[a] >= 0) return fail(hr, "fdtd_run_bloch: PMC on a plus face is not available together with Bloch boundaries");
   // z-slab decomposition (hr->comm): both parts exchange their ghost planes through the real-part handle's
@@ -4523,6 +4580,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
   const bool multi = hr->comm != nullptr;
   const bool nb_lo = hr->cfg.bc[4] == FDTD_BC_NEIGHBOR, nb_hi = hr->cfg.bc[5] == FDTD_BC_NEIGHBOR;
   if ((nb_lo || nb_hi) && !multi) return fail(hr, "fdtd_run_bloch: neighbour faces need fdtd_comm_init on the first handle");
+  if (multi && aniso) return fail(hr, "fdtd_run_bloch: fully anisotropic media are not available on z-slabs");
   if (hi->cfg.bc[4] != hr->cfg.bc[4] || hi->cfg.bc[5] != hr->cfg.bc[5])
     return fail(hr, "fdtd_run_bloch: the two solvers must have the same z faces");
   if (hr->g.nx != hi->g.nx || hr->g.ny != hi->g.ny || hr->g.nz != hi->g.nz || hr->cfg.device != hi->cfg.device ||
@@ -4560,6 +4618,40 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
   }
   float cph[3], sph[3];
   for (int a = 0; a < 3; ++a) { cph[a] = (float)std::cos(phase[a]); sph[a] = (float)std::sin(phase[a]); }
+  // (cos, sin) of each wrap code of the coupling lists: the sum of the phases the ghost fills apply on the axes it crosses
+  AnisoPhaseTab wrap_tab{};
+  if (aniso) {
+    const double ph[3] = {n_real[0] > 0 ? phase[0] : 0.0, n_real[1] > 0 ? phase[1] : 0.0, per_z ? phase[2] : 0.0};
+    for (int c = 0; c < kWrapCodes; ++c) {
+      double p = 0.0;
+      for (int a = 0; a < 3; ++a) {
+        const int w = (c >> (2 * a)) & 3;
+        p += w == 1 ? ph[a] : (w == 2 ? -ph[a] : 0.0);
+      }
+      wrap_tab.r[c] = make_float2((float)std::cos(p), (float)std::sin(p));
+    }
+  }
+  // E-side tail of a step: CPML and sources of both parts, the coupling (it reads both parts), then damping and ADE
+  auto e_tail = [&](long long n) {
+    if (!aniso) {
+      for (FdtdSolver* h : both) {
+        launch_pml(h, true, 0, nz, st);
+        launch_sources(h, true, n, 0, nz, st);
+        launch_damp(h, true, 0, nz, st);
+        launch_ade(h, 0, nz, st);
+      }
+      return;
+    }
+    for (FdtdSolver* h : both) {
+      launch_pml(h, true, 0, nz, st);
+      launch_sources(h, true, n, 0, nz, st);
+    }
+    aniso_apply_bloch(hr, hi, wrap_tab, st);
+    for (FdtdSolver* h : both) {
+      launch_damp(h, true, 0, nz, st);
+      launch_ade(h, 0, nz, st);
+    }
+  };
   const long long pc = plane_cells(hr);
   // (pointers are taken at call time: the fused sweep swaps the field sets every step)
   auto six = [&]() { Cplx6P F; for (int c = 0; c < 6; ++c) { F.f[c].re = field_ptr(hr, c); F.f[c].im = field_ptr(hi, c); } return F; };
@@ -4605,6 +4697,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
     bool rec = false;
     for (Monitor& m : hr->mons) if (m.next < m.steps.size() && m.steps[m.next] == n) rec = true;
     if (rec) for (FdtdSolver* h : both) record_monitors(h, n, false, st);
+    if (aniso) aniso_save_bloch(hr, hi, st);     // (E^n of the nodes around fully anisotropic cells, in front of either sweep)
     // H-side corrections of both parts, then the ghost cells (they must carry the corrections too)
     for (FdtdSolver* h : both) {
       launch_damp(h, false, 0, nz, st);
@@ -4620,12 +4713,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
       }
       for (FdtdSolver* h : both) if (launch_fused(h, st, 0)) return -1;
       if (rec) for (FdtdSolver* h : both) record_monitors(h, n, true, st);
-      for (FdtdSolver* h : both) {
-        launch_pml(h, true, 0, nz, st);
-        launch_sources(h, true, n, 0, nz, st);
-        launch_damp(h, true, 0, nz, st);
-        launch_ade(h, 0, nz, st);
-      }
+      e_tail(n);
     } else {
       if (per_z) { plane(0, nz, 0, sph[2]); plane(1, nz, 0, sph[2]); }      // E ghost(nz) of E^n (first step / after set_field)
       if (multi && exchange_pair(true)) return -1;                          // ... or the upper neighbour's bottom plane
@@ -4634,12 +4722,17 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
       else if (!nb_lo) for (FdtdSolver* h : both) fill_ghost_h(h, st);
       if (multi && exchange_pair(false)) return -1;
       if (rec) for (FdtdSolver* h : both) record_monitors(h, n, true, st);
-      for (FdtdSolver* h : both) {
-        launch_e_main(h, 0, nz, st);
-        launch_pml(h, true, 0, nz, st);
-        launch_sources(h, true, n, 0, nz, st);
-        launch_damp(h, true, 0, nz, st);
-        launch_ade(h, 0, nz, st);
+      if (aniso) {
+        for (FdtdSolver* h : both) launch_e_main(h, 0, nz, st);
+        e_tail(n);
+      } else {
+        for (FdtdSolver* h : both) {
+          launch_e_main(h, 0, nz, st);
+          launch_pml(h, true, 0, nz, st);
+          launch_sources(h, true, n, 0, nz, st);
+          launch_damp(h, true, 0, nz, st);
+          launch_ade(h, 0, nz, st);
+        }
       }
       if (!per_z && !nb_hi) for (FdtdSolver* h : both) fill_ghost_e(h, st);
     }

@@ -522,16 +522,28 @@ class HipEngine:
                 from .exceptions import Tidy3dNotImplementedError
                 raise Tidy3dNotImplementedError("FullyAnisotropicMedium is not available in z-slab (multi-GPU) runs")
             from .constants import EPSILON_0
+            # Bloch device layout: the lists are on the user grid — every node moves by the ghost offset, a neighbour across a
+            # periodic face is the real node on the far side (its own Ca / Cb), and the wrap codes carry the period crossed
+            bloch = spec.bloch is not None
+            off = np.asarray(self.ghost, np.int64)
             for st_ in aniso:
                 n = len(st_.ijk)
-                cells = (st_.ijk[:, 2] * sxy + st_.ijk[:, 1] * nx + st_.ijk[:, 0]).astype(np.uint32)
+                ijk = st_.ijk + off[None, :]
+                cells = (ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32)
                 nbr = np.full((n, 8), 0xFFFFFFFF, np.uint32)
                 w_new = np.zeros((n, 8), np.float64)
                 w_old = np.zeros((n, 8), np.float64)
+                if bloch:
+                    if st_.nbr_wrap is None:
+                        raise SolverLibraryError("fully anisotropic lists without wrap signs cannot run with Bloch boundaries")
+                    s_ = np.asarray(st_.nbr_wrap, np.int64)
+                    wrap = ((s_ == 1) * 1 + (s_ == -1) * 2) @ np.array([1, 4, 16], np.int64)
+                    wrap = np.ascontiguousarray(wrap.astype(np.uint8).reshape(-1))
                 for slot in range(8):
                     b = st_.nbr_comp[slot]
                     j = st_.nbr_ijk[:, slot]
                     ok = j[:, 0] >= 0
+                    j = j + off[None, :]
                     if spec.mat_idx is not None:
                         mi = spec.mat_idx[b][j[ok, 2], j[ok, 1], j[ok, 0]]
                         ca_b, cb_b = np.asarray(mt.ca)[mi], np.asarray(mt.cb)[mi]
@@ -545,7 +557,11 @@ class HipEngine:
                     w_old[ok, slot] = wn * ca_b
                 c32, n32 = np.ascontiguousarray(cells), np.ascontiguousarray(nbr.reshape(-1))
                 wn32, wo32 = _f32(w_new.reshape(-1)), _f32(w_old.reshape(-1))
-                self._chk(d.fdtd_add_aniso(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32)), "fdtd_add_aniso")
+                if bloch:
+                    self._chk(d.fdtd_add_aniso_bloch(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32), _ptr(wrap)),
+                              "fdtd_add_aniso_bloch")
+                else:
+                    self._chk(d.fdtd_add_aniso(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32)), "fdtd_add_aniso")
         # sources
         from .spec import BC_PEC
         for s in spec.sources:

@@ -55,6 +55,9 @@ class AnisoSet:
     nbr_comp: Tuple[int, ...]         # [8]: slots 0-3 component (a+1)%3, 4-7 component (a+2)%3
     nbr_ijk: np.ndarray               # [n, 8, 3]; -1 = no node (beyond a non-periodic wall)
     g: np.ndarray                     # [n, 8] float64
+    nbr_wrap: Optional[np.ndarray] = None   # [n, 8, 3] int8: the period crossed along each axis to reach nbr_ijk (-1, 0, +1;
+                                            # periodic axes wrap nbr_ijk into the grid) — a Bloch face multiplies that node by
+                                            # exp(i s phi)
 
 
 @dataclass
