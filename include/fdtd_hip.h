@@ -101,6 +101,19 @@ typedef struct FdtdStats {
   int64_t seam_kernel_launches;
 } FdtdStats;
 
+/* Deferred seam repair of the last fdtd_run (FDTD_OPT_SEAM_DEFER).  Its own structure: the layout of FdtdStats stays what bindings built
+ * against earlier headers expect. */
+typedef struct FdtdSeamStats {
+  int64_t seam_deferred_pairs; /* of fused2_pairs: pairs whose seam_kernel left its values in the compact repair array for the next pair's
+                                  sweep instead of storing them into the fields */
+  int64_t seam_flushes;        /* launches of seam_flush_kernel: a repair array scattered into the fields because something other than the
+                                  expected plain pair was about to read them */
+  int32_t seam_pending;        /* 1: the current set's seam columns are stale (never, once fdtd_run has returned) */
+  int32_t reserved;
+  double  seam_flush_ms;       /* with FDTD_FLAG_TIME_KERNELS: summed durations of the flushes (not part of FdtdStats.seam_kernel_ms, which
+                                  keeps counting every seam_kernel launch, deferred or not) */
+} FdtdSeamStats;
+
 /* FdtdStats.fused2_off_reason: what keeps a run on single steps (the first reason found) */
 enum { FDTD_F2_OFF_NONE = 0,
        FDTD_F2_OFF_DISABLED = 1,          /* FDTD_OPT_TWOSTEP = 0 (or another schedule was asked for) */
@@ -335,10 +348,21 @@ enum { FDTD_OPT_FLAGS = 0, FDTD_OPT_VARIANT = 1, FDTD_OPT_ZCHUNK = 2, FDTD_OPT_R
                                    two-step sweep, its seam kernel and the shell's boxes add them.  -1 / 1 = default (on one GPU, where no
                                    two lists meet on a node), 0 = off: single steps (or the lists' planes as z holes) while they inject. */
        FDTD_OPT_WHATIF = 24, /* measuring aid (round 6): 1 ... 8 = a what-if instantiation of the vacuum two-step sweep that skips part of its work
-                                (csrc/fdtd_kernels2.hpp lists them) — WRONG results, meaningful times; 0 = off (default) */
+                                (csrc/fdtd_kernels2.hpp lists them) — WRONG results, meaningful times; 0 = off (default);
+                                16 ... 18 = plain pairs without the seam_kernel launch / with it skipped and the sweep reading the repair array /
+                                with seam_kernel storing into the repair array (what deferred seam repair can gain, pays and costs);
+                                19 = the vacuum sweep without its one-lane stores into the seam scratch (and without EXJ: compare with 14) */
        FDTD_OPT_SLAB_BOXES_FIRST = 26, /* z-slab ranks that carry CPML, step pairs: the shell's boxes are launched in front of the bulk sweep (1), behind it (0: round 5), beside it on a third stream (2), or 2 for slabs of 96 planes and more, else 1 (3, default) */
+       FDTD_OPT_SEAM_DEFER = 27, /* deferred seam repair: a plain step pair (whole grid, sixteen-wave plain / materials / absorber sweep) that is
+                                    followed in the same fdtd_run by another plain pair — no record, decay check, H-side source launch or ghost-plane
+                                    copy between them — leaves the seven values seam_kernel repairs per seam row in a compact array the next
+                                    sweep's edge lanes read, instead of storing them into the fields at a row stride.  -1 / 1 = on (default):
+                                    launches of sixteen-wave workgroups, which run the instantiation that reads the array anyway; 0 = off;
+                                    2 = testing aid: at every workgroup size (smaller workgroups then run the sixteen-wave instantiation —
+                                    another launch bound than their own, not a setting for production runs).  May be switched between runs of one engine (A/B inside one placement of the arrays). */
        FDTD_OPT_LDS_PAD = 10 /* measuring aid: extra dynamic LDS per workgroup of the sweep in bytes (lowers its occupancy) */ };
 int fdtd_set_option(FdtdSolver* h, int key, int value);
+int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out);
 int fdtd_reset(FdtdSolver* h);      /* zero fields, auxiliaries, monitors and the step counter */
 
 #ifdef __cplusplus

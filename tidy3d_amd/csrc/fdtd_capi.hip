@@ -207,6 +207,8 @@ struct FdtdSolver {
   SrcPaged spg;
   std::map<std::array<int, 6>, int> box_paged;       // Shell2P::paged of the shell's boxes met so far (cleared when either paging is set up)
   int spg_on = -1;                   // FDTD_OPT_SRC_PAGED: -1 / 1 = default (on), 0 = off (single steps / z holes while such lists inject, round 5)
+  // (19: the vacuum sweep without its one-lane stores into the seam scratch)
+  // (16 - 18, any plain sixteen-wave pair: 16 = no seam_kernel launch, 17 = 16 + the sweep's edge lanes read the repair array, 18 = seam_kernel stores into the repair array)
   int whatif = 0;                    // FDTD_OPT_WHATIF: a what-if instantiation of the vacuum two-step sweep (fdtd_kernels2.hpp; wrong results, meaningful times)
   int disp_on = -1;                  // FDTD_OPT_DISP: dispersive cells inside the two-step sweeps: -1 = default (on), 0 = off (their planes as z holes, round 5)
   std::vector<AnisoGroup> aniso;
@@ -310,7 +312,11 @@ struct FdtdSolver {
   int debug_sync = 0;                 // FDTD_OPT_DEBUG_SYNC: a device-wide synchronisation behind every launch group (dbg_sync) — no two launches ever overlap
   hipEvent_t ev_shell_a = nullptr, ev_shell_b = nullptr;
   hipEvent_t ev_rec = nullptr;        // z-slab ranks: a monitor record on the main stream done (the comm stream's next boundary work waits for it)
-  float* seam_buf = nullptr;          // intermediate values on the seams between x tiles
+  long long seam_deferred_pairs = 0, seam_flushes = 0;      // (of the current fdtd_run: FdtdSeamStats)
+  double seam_flush_ms = 0.0;
+  float* seam_buf = nullptr;          // intermediate values on the seams between x tiles, and behind them the compact repair array (deferred seam repair)
+  int seam_defer = -1;                // FDTD_OPT_SEAM_DEFER: -1 / 1 = plain sixteen-wave pairs followed by a plain pair leave their repaired seam values in the compact array, 0 = never, 2 = testing aid: at every workgroup size
+  bool seam_pending = false;          // the seam columns of the current set (h->f) are stale: their values lie in the repair array
   float* inj_val = nullptr;           // source terms applied between the two steps
   float* cap_val = nullptr;           // samples of the middle step (small time monitors)
   float* dump_buf = nullptr;          // H^{n+1/2} over the boxes of DFT monitors recording at the first step of a pair
@@ -1195,8 +1201,11 @@ const FdtdSolver::TileClasses* tile_classes(FdtdSolver* h, int W, int zc, const 
 // caller issues behind the launch (and behind the sources / damping of step n + 1 it applies itself).  `e2_clip`: a clipped launch
 // may apply the E-side sources of step n + 1 itself (the caller's ONE launch covers every source node).
 // `sr`: paged source terms of this pair (the caller has filled them, spg_fill; the node table then lists no sources).
+// `defer_ok` (plain_pair): the caller knows that nothing but the next plain pair will read the set this one writes — where the launch
+// allows it too, seam_kernel leaves its values in the repair array (h->seam_pending) and the next launch's edge lanes take them there.
+void flush_seams(FdtdSolver* h, hipStream_t st);
 int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb, bool* sources2_done, bool* damp2_done = nullptr,
-                  const ClipP* clip = nullptr, bool use_disp = false, bool e2_clip = false, const SrcP& sr = SrcP{}) {
+                  const ClipP* clip = nullptr, bool use_disp = false, bool e2_clip = false, const SrcP& sr = SrcP{}, bool defer_ok = false) {
   const bool inject = tb->with_sources;      // (false: the lists are spent, or — shell pairs with z holes — their planes take single steps)
   const GridP& g = h->g;
   if (ensure_second_set(h)) return -1;
@@ -1216,7 +1225,7 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   const int nbz = (box.k1 - box.k0 + zc - 1) / zc;
   const int n_seams = nbx - 1 + ((clip && h->cfg.bc[0] == FDTD_BC_PERIODIC) ? 1 : 0);        // (periodic x: the wrap is a seam too)
   if (!h->seam_buf && (nbx > 1 || h->cfg.bc[0] == FDTD_BC_PERIODIC) &&
-      dev_alloc(h, &h->seam_buf, (size_t)nbx * kSeamArrays * (size_t)(g.nz + 2) * (size_t)g.ny)) return -1;
+      dev_alloc(h, &h->seam_buf, seam_scratch_floats(g, nbx) + seam_rep_floats(g, nbx))) return -1;
   if (!h->inj_val && dev_alloc(h, &h->inj_val, (size_t)kMaxInj)) return -1;
   if (!h->cap_val && dev_alloc(h, &h->cap_val, (size_t)kMaxCap)) return -1;
   InjP inj{};
@@ -1277,6 +1286,7 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   if (use_disp) dp = DispP{h->disp.dseg, h->disp.cs, h->disp.e1};
   int opt = (h->mem_hints ? 1 : 0) | (h->mat4 ? 2 : 0) | ((tb->mons.empty() && (!tb->with_sources || h->src_h_nodes == 0) && !tb->dstart) ? 0 : 4) |
             (clip ? 16 : (h->has_damp ? 8 : 0)) | (use_disp ? 32 | 1 : 0);
+  if (h->whatif == 19 && opt == 1 && W == 16) opt |= 9 << 8;        // (the sweep without its stores into the seam scratch)
   if (h->whatif > 0 && h->whatif <= 15 && h->whatif != 9 && opt == 1 && (W == 16 || h->whatif == 13 || h->whatif == 14)) opt |= h->whatif << 8;        // (measuring aid: the vacuum sweep with part of its work skipped)
   SrcP sr_used = sr;
   if (h->whatif == 9 && !sr.sseg && !(opt & 8) && (!(opt & 32) || (opt & 16))) {
@@ -1292,6 +1302,19 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
     if (S.sseg && S.state != 1) { sr_used.sseg = S.sseg; sr_used.t = S.tab; opt |= 64 | 4 | 1; }
   }
   if (sr.sseg) { opt |= 64 | 4 | 1; *sources2_done = true; h->spg.pairs++; }
+  // deferred seam repair: the sixteen-wave plain / materials / absorber sweep of the whole grid reads and leaves the compact array
+  // (its sixteen-wave instantiation serves every workgroup size; by default only the launches that run it anyway defer)
+  const bool rep_capable = n_seams > 0 && !clip && (W == 16 || h->seam_defer == 2) && (opt & ~(1 | 2 | 8)) == 0;
+  float* const rep_arr = h->seam_buf ? h->seam_buf + seam_scratch_floats(g, nbx) : nullptr;
+  if (h->seam_pending && !rep_capable) flush_seams(h, st);      // (the set it flushes, h->f, is the one this launch reads)
+  if (h->seam_pending || (h->whatif == 17 && rep_capable)) opt |= 8192;
+  h->seam_pending = false;
+  bool defer = defer_ok && rep_capable && h->seam_defer != 0 && h->whatif == 0;
+  if (defer) {        // nothing may touch the set behind the seam kernel: E-side sources of step n + 1 and the damping of E^{n+2} are in the sweep, or absent
+    bool e_post = false;
+    for (const PointSrc& s : h->psrc) e_post = e_post || (s.n_e && n + 1 < s.n_steps);
+    if ((e_post && !*sources2_done) || (h->has_damp && !dmp.e2)) defer = false;
+  }
   const int blocks = remap ? ((total + 7) / 8) * 8 : total;
   // background-only tiles take the plain sweep inside the materials launch (fdtd_kernels2.hpp, tile classes)
   const FdtdSolver::TileClasses* tc = tile_classes(h, W, zc, box, nbx, nby, nbz, use_disp, sr_used.sseg != nullptr);
@@ -1299,14 +1322,25 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   launch_fused2_step(st, W, opt, blocks, g, h->f, h->f2, sp, mp, zc, nbx, nby, nbz, remap, inj, h->seam_buf, dmp, box,
                      TileClassP{split ? tc->dev : nullptr}, dp, sr_used);
   time_end(h, st);
-  if (n_seams > 0) {
+  if (n_seams > 0 && !(rep_capable && (h->whatif == 16 || h->whatif == 17))) {
     time_begin(h, 4, st);
-    launch_seams(st, g, h->f2, sp, mp, h->seam_buf, n_seams, dmp, box, inj, sr);
+    launch_seams(st, g, h->f2, sp, mp, h->seam_buf, n_seams, dmp, box, inj, sr, (defer || (h->whatif == 18 && rep_capable)) ? rep_arr : nullptr);
     time_end(h, st);
   }
   if (use_disp) h->disp.pairs++;
   if (!clip) swap_sets(h);
+  if (defer) { h->seam_pending = true; h->seam_deferred_pairs++; }
   return 0;
+}
+// the repair array into the seam columns of the current set, in front of whatever reads them there (kind 5 of the kernel timers)
+void flush_seams(FdtdSolver* h, hipStream_t st) {
+  if (!h->seam_pending) return;
+  const int nbx = (h->g.nx + 255) / 256;
+  time_begin(h, 5, st);
+  launch_seam_flush(st, h->g, h->f, h->seam_buf + seam_scratch_floats(h->g, nbx), nbx - 1);
+  time_end(h, st);
+  h->seam_pending = false;
+  h->seam_flushes++;
 }
 
 // ---- shell pairs: two steps per sweep on grids walled by CPML ------------------------------------------------------------
@@ -3315,6 +3349,7 @@ int fdtd_set_field(FdtdSolver* h, int comp, const float* host, size_t bytes) {
   if (comp < 0 || comp > 5) return fail(h, "fdtd_set_field: bad component");
   if (bytes != (size_t)n_cells(h) * 4) return fail(h, "fdtd_set_field: expected %zu bytes", (size_t)n_cells(h) * 4);
   HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (h->seam_pending) { flush_seams(h, h->stream); HIPCHK(h, hipStreamSynchronize(h->stream)); }      // (only behind a run that ended in an error)
   HIPCHK(h, hipMemcpy(field_ptr(h, comp), host, bytes, hipMemcpyHostToDevice));
   // the ADE recursion forms Q^{n+1} from E^{n+1} + E^n: E^n of its cells is the value just uploaded
   for (AdeGroup& a : h->ade)
@@ -3339,6 +3374,7 @@ int fdtd_get_field(FdtdSolver* h, int comp, float* host, size_t bytes) {
   if (comp < 0 || comp > 5) return fail(h, "fdtd_get_field: bad component");
   if (bytes != (size_t)n_cells(h) * 4) return fail(h, "fdtd_get_field: expected %zu bytes", (size_t)n_cells(h) * 4);
   HIPCHK(h, hipSetDevice(h->cfg.device));
+  flush_seams(h, h->stream);                 // (only behind a run that ended in an error: fdtd_run returns with nothing pending)
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(host, field_ptr(h, comp), bytes, hipMemcpyDeviceToHost));
   return 0;
@@ -3377,6 +3413,7 @@ int fdtd_reset(FdtdSolver* h) {
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->seam_pending = false;
   for (int c = 0; c < 6; ++c) HIPCHK(h, hipMemset(h->fbase[c], 0, h->field_bytes));
   for (int c = 0; c < 6; ++c) if (h->fbase2[c]) HIPCHK(h, hipMemset(h->fbase2[c], 0, h->field_bytes));
   for (int c = 0; c < 6; ++c) if (h->fbase3[c]) HIPCHK(h, hipMemset(h->fbase3[c], 0, h->field_bytes));
@@ -3902,6 +3939,7 @@ struct Run {
       h->f2_off_reason = why;
     }
     h->fused2_pairs = 0;
+    h->seam_deferred_pairs = h->seam_flushes = 0;
     h->shell_pairs = 0;
     h->shell2_pairs = 0;
     done = 0;
@@ -4092,6 +4130,7 @@ struct Run {
   int begin_step() {
     n = h->step;
     rec = !fused_multi && rec_at(n);
+    if (rec) flush_seams(h, st);
     if (rec && multi) {
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));
@@ -4343,7 +4382,13 @@ struct Run {
     bool sources2_done = false, damp2_done = true;
     launch_sources(h, false, n, 0, nz, st);              // H-side sources of step n act on H^{n-1/2}, as before a single step
     if (pair_spg) spg_fill(h, n, st);                    // (the other source terms of the pair into paged storage, the incident grids through both steps)
-    if (launch_fused2(h, n, st, tb, &sources2_done, &damp2_done, nullptr, pair_disp, false, pair_spg ? spg_params(h) : SrcP{})) return -1;
+    // deferred seam repair: only when the NEXT two steps are known to be a plain pair of this run with nothing in front of, between or behind
+    // the two sweeps that reads or writes the fields — no record, no decay check, no H-side source launch, no ghost planes to copy
+    const auto decay_at = [&](long long m) { return h->decay_every > 0 && (m % h->decay_every) == 0; };
+    const bool defer_ok = done + 4 <= n_steps && !decay_at(n + 2) && !decay_at(n + 3) && !rec_at(n + 1) && !rec_at(n + 2) && !rec_at(n + 3) &&
+                          !pair_disp && !pair_spg && h->tfsf.empty() && h->src_h_nodes == 0 && h->cfg.bc[4] != FDTD_BC_PERIODIC && !multi &&
+                          !h->step_dev_mode && !h->debug_sync;
+    if (launch_fused2(h, n, st, tb, &sources2_done, &damp2_done, nullptr, pair_disp, false, pair_spg ? spg_params(h) : SrcP{}, defer_ok)) return -1;
     pair_record(h, tb, n, st);                           // (H^{n+3/2} is not touched by the E-side sources that follow)
     if (rec_at(n + 1)) record_monitors(h, n + 1, true, st);      // DFT records at the middle step: their H terms, from the write set
     if (!sources2_done) launch_sources(h, true, n + 1, 0, nz, st);
@@ -4457,6 +4502,7 @@ struct Run {
   }
   // joins the streams, reads the timers
   int finish() {
+    flush_seams(h, st);          // (a run never returns with stale seam columns)
     if (multi) {
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));
@@ -4471,7 +4517,7 @@ struct Run {
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
     h->stats.run_ms = ms;
     h->stats.steps_done = h->step;
-    h->stats.h_kernel_ms = h->stats.e_kernel_ms = h->stats.fused_kernel_ms = h->stats.shell_kernel_ms = h->stats.seam_kernel_ms = 0.0;
+    h->stats.h_kernel_ms = h->stats.e_kernel_ms = h->stats.fused_kernel_ms = h->stats.shell_kernel_ms = h->stats.seam_kernel_ms = h->seam_flush_ms = 0.0;
     h->stats.h_kernel_launches = h->stats.e_kernel_launches = h->stats.fused_kernel_launches = h->stats.shell_kernel_launches = h->stats.seam_kernel_launches = 0;
     for (size_t i = 0; i < h->kev_kind.size(); ++i) {
       float t = 0.f;
@@ -4480,6 +4526,7 @@ struct Run {
       else if (h->kev_kind[i] == 1) { h->stats.e_kernel_ms += t; h->stats.e_kernel_launches++; }
       else if (h->kev_kind[i] == 3) { h->stats.shell_kernel_ms += t; h->stats.shell_kernel_launches++; }
       else if (h->kev_kind[i] == 4) { h->stats.seam_kernel_ms += t; h->stats.seam_kernel_launches++; }
+      else if (h->kev_kind[i] == 5) h->seam_flush_ms += t;
       else { h->stats.fused_kernel_ms += t; h->stats.fused_kernel_launches++; }
     }
     return 0;
@@ -4487,6 +4534,7 @@ struct Run {
   int loop() {
     for (; done < n_steps; ++done) {
       if (begin_step()) return -1;
+      if (h->seam_pending && !(!fused_multi && pair && !use_s2 && !f2s_ok && f2_ok)) flush_seams(h, st);      // (not the plain pair that was expected)
       if (fused_multi) {
         const int rc = slab_rank_step();
         if (rc < 0) return -1;
@@ -4551,7 +4599,7 @@ int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user
   HIPCHK(h, hipSetDevice(h->cfg.device));
   Run r{h, n_steps, progress, user};
   if (r.setup() || r.setup_schedules() || r.setup_pairs()) return -1;
-  if (r.loop()) return -1;
+  if (r.loop()) { flush_seams(h, h->stream); return -1; }      // (an error leaves no stale seam columns either)
   return r.finish();
 }
 // Complex (Bloch-periodic) fields: two solvers carry Re and Im of the same simulation (identical grid,
@@ -4819,7 +4867,8 @@ int fdtd_set_option(FdtdSolver* h, int key, int value) {
       if (h->spg.state == -1 && value != 0) h->spg.state = 0;
       return 0;
     case FDTD_OPT_SLAB_BOXES_FIRST: if (value < 0 || value > 3) break; h->slab_boxes_first = value; return 0;
-    case FDTD_OPT_WHATIF: if (value < 0 || value > 15) break; h->whatif = value; return 0;
+    case FDTD_OPT_WHATIF: if (value < 0 || value > 19) break; h->whatif = value; return 0;
+    case FDTD_OPT_SEAM_DEFER: if (value > 2) break; h->seam_defer = value < 0 ? -1 : value; return 0;
     case FDTD_OPT_DISP:
       if (h->disp.state == 1 && value == 0) break;       // (every ADE launch keeps the paged memory terms by now: set it before the first run)
       h->disp_on = value < 0 ? -1 : (value != 0);
@@ -4866,6 +4915,16 @@ int fdtd_get_stats(FdtdSolver* h, FdtdStats* out) {
   out->single_step_reason = h->f2_dyn_reason;
   out->src_paged_pairs = (int32_t)std::min<long long>(h->spg.pairs, 0x7fffffff);
   out->struct_bytes = (int32_t)sizeof(FdtdStats);
+  return 0;
+}
+
+int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out) {
+  if (!h || !out) return -1;
+  out->seam_deferred_pairs = h->seam_deferred_pairs;
+  out->seam_flushes = h->seam_flushes;
+  out->seam_pending = h->seam_pending ? 1 : 0;
+  out->reserved = 0;
+  out->seam_flush_ms = h->seam_flush_ms;
   return 0;
 }
 

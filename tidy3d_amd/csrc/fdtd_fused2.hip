@@ -1,6 +1,8 @@
 // Translation unit of the two-steps-per-sweep kernels (fdtd_kernels2.hpp) and their host-side launchers.
 // Built with -fno-slp-vectorize (tidy3d_amd/build.py): see fdtd_fused2.hpp.
 #include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstdlib>
 // fdtd_kernels.hpp defines its kernels in the header (it was written for one translation unit).  This second unit only
 // needs its types and device helpers: here every kernel gets internal linkage, and the ones not launched from this
 // file are dropped.
@@ -26,7 +28,7 @@ void launch_fused2_step(hipStream_t st, int waves, int opt, int grid_blocks, con
     launch_fused2_step_src(st, waves, opt, grid_blocks, g, a, b, s, m, zchunk, nbx, nby, nbz, xcd_remap, inj, seam, dmp, clip, tcl, dp, sr);
     return;
   }
-  if (opt >> 8) {
+  if ((opt >> 8) & 15) {
     launch_fused2_step_whatif(st, waves, opt, grid_blocks, g, a, b, s, m, zchunk, nbx, nby, nbz, xcd_remap, inj, seam, dmp, clip);
     return;
   }
@@ -39,6 +41,15 @@ void launch_fused2_step(hipStream_t st, int waves, int opt, int grid_blocks, con
     return;
   }
   const dim3 grid(grid_blocks, 1, 1), block(64, waves, 1);
+  if (opt & 8192) {          // deferred seam repair: the sixteen-wave sweeps a run of plain pairs uses (fdtd_capi.hip asks for no other)
+#define FDTD_F2_R(OV) \
+  case OV: hipLaunchKernelGGL((fused2_step_kernel<1024, OV | 8192>), grid, block, fused2_lds_bytes(1024, OV, waves), st, g, a, b, s, m, zchunk, nbx, \
+                              nby, nbz, xcd_remap, inj, seam, dmp, clip, tcl, dp, sr); break
+    switch (opt & 15) { FDTD_F2_R(0); FDTD_F2_R(1); FDTD_F2_R(2); FDTD_F2_R(3); FDTD_F2_R(8); FDTD_F2_R(9); FDTD_F2_R(10); FDTD_F2_R(11);
+      default: fprintf(stderr, "launch_fused2_step: no deferred-seam instantiation of the sweep for opt %d\n", opt); abort(); }
+#undef FDTD_F2_R
+    return;
+  }
 #define FDTD_F2_O(LBV, OV)                                                                                             \
   hipLaunchKernelGGL((fused2_step_kernel<LBV, OV>), grid, block, fused2_lds_bytes(LBV, OV, waves), st, g, a, b, s, m, zchunk, nbx, nby, nbz,     \
                      xcd_remap, inj, seam, dmp, clip, tcl, dp, sr)
@@ -79,11 +90,17 @@ void launch_dft_record_dump(hipStream_t st, const DftDumpP& r, const float* dump
 }
 
 void launch_seams(hipStream_t st, const GridP& g, const FieldP& b, const StepP& s, const MatP& m, const float* seam,
-                  int n_seams, const DampT& dmp, const ClipP& clip, const InjP& inj, const SrcP& sr) {
+                  int n_seams, const DampT& dmp, const ClipP& clip, const InjP& inj, const SrcP& sr, float* rep) {
   const long long nt = (long long)n_seams * (clip.j1 - clip.j0) * (clip.k1 - clip.k0);
   if (nt <= 0) return;
   const unsigned blocks = (unsigned)((nt + 255) / 256);
-  hipLaunchKernelGGL(seam_kernel, dim3(blocks), dim3(256), 0, st, g, b, s, m, seam, n_seams, dmp, clip, inj, sr);
+  hipLaunchKernelGGL(seam_kernel, dim3(blocks), dim3(256), 0, st, g, b, s, m, seam, n_seams, dmp, clip, inj, sr, rep);
+}
+
+void launch_seam_flush(hipStream_t st, const GridP& g, const FieldP& b, const float* rep, int n_seams) {
+  const long long nt = (long long)n_seams * g.ny * g.nz;
+  if (nt <= 0) return;
+  hipLaunchKernelGGL(seam_flush_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, g, b, rep, n_seams);
 }
 
 }  // namespace fdtd

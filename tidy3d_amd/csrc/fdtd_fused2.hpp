@@ -100,6 +100,7 @@ constexpr int kSeamArrays = 13;  // of step one: H1_y, H1_z, E1_x, E1_y, E1_z [c
 // host-side launchers (fdtd_fused2.hip)
 void launch_inject_values(hipStream_t st, float* val, const float* w_re, const float* w_im, const float2* wave,
                           long long step, int n);
+// bit 13: the seam columns of set a are read from the repair array (plain, materials and absorber sweeps of the whole grid, 16 waves)
 // waves = rows per workgroup (W - 3 of them written); opt: bit 0 non-temporal stores, bit 1 materials (m.m4 set), bit 2 monitor
 // samples in the table, bit 3 absorber layers (dmp.fb[0] set), bit 4 the launch covers the box `clip` only (not with bit 3),
 // bit 5 the memory terms of dispersive cells subtracted from E^{n+1} in the sweep (dp.dseg set; with bit 1; always non-temporal stores)
@@ -144,7 +145,14 @@ struct DftDumpP { int n; int slot[3]; int off[3]; };
 void launch_dft_record_dump(hipStream_t st, const DftDumpP& r, const float* dump, float2* acc, long long cells, long long fstride,
                             const float2* phase, int nf);
 // (inj: the seam kernel adds the E-side source terms of step n+1 when the sweep did — inj.e2_in_sweep)
+// (rep: deferred seam repair — the repaired values go into the compact array, not into set b)
 void launch_seams(hipStream_t st, const GridP& g, const FieldP& b, const StepP& s, const MatP& m, const float* seam,
-                  int n_seams, const DampT& dmp, const ClipP& clip, const InjP& inj, const SrcP& sr = SrcP{});
+                  int n_seams, const DampT& dmp, const ClipP& clip, const InjP& inj, const SrcP& sr = SrcP{}, float* rep = nullptr);
+// deferred seam repair (fdtd_kernels2.hpp): the compact array [seam][kRepArrays][nz][ny] lies behind the scratch arrays of the seam buffer
+constexpr int kRepArraysHost = 7;
+inline size_t seam_scratch_floats(const GridP& g, int n_tiles_x) { return (size_t)n_tiles_x * kSeamArrays * (size_t)(g.nz + 2) * (size_t)g.ny; }
+inline size_t seam_rep_floats(const GridP& g, int n_tiles_x) { return (size_t)n_tiles_x * kRepArraysHost * (size_t)g.nz * (size_t)g.ny; }
+// scatters the repair array into the seam columns of set b
+void launch_seam_flush(hipStream_t st, const GridP& g, const FieldP& b, const float* rep, int n_seams);
 
 }  // namespace fdtd

@@ -35,6 +35,7 @@
 //   4  every plane load reads the same (cached) row: no HBM reads, same instructions    5  no field stores
 //   6  no barriers and no LDS exchange (own values instead of the neighbour rows')      7  loads + stores only (the copy floor of this tiling)
 //   8  no barriers, LDS traffic kept
+//   9  the edge lanes' stores into the seam scratch dropped (no EXJ either: its A/B partner is 14)
 // PREFETCH instantiations (OPT bits 8 - 11 = 10 ... 12; CORRECT results, the same bits): part of plane k+1 travels global memory -> LDS
 // by LDS-DMA (global_load_lds_dwordx4) while plane k is computed — the one way to keep a second batch of loads in flight that costs
 // no registers (the sweep has 3 of 128 left).  The LDS for it comes from the E1 exchange arrays: published BEHIND the second barrier
@@ -120,6 +121,28 @@ __global__ __launch_bounds__(256) void inject_values_kernel(float* val, const fl
 
 __device__ __forceinline__ long long seam_at(const GridP& g, int seam, int arr, int j, int k) {
   return (((long long)seam * kSeamArrays + arr) * (g.nz + 2) + (k + 1)) * g.ny + j;
+}
+
+// Deferred seam repair (OPT bit 13, REP): in a run of plain step pairs the seven values seam_kernel repairs per seam row do not go
+// into the field arrays (seven 4-byte stores at a row stride each: partial writes to lines long gone from L2) but, coalesced, into a
+// compact array [seam][kRepArrays][nz][ny] behind the scratch arrays of `seam`; the next sweep's edge lanes take them from there
+// instead of the seam columns of its read set, and seam_flush_kernel scatters them into the fields when somebody else reads those.
+//   arrays: 0 H_y  1 H_z  2 E_x  3 E_y  4 E_z of column c-1;  5 E_y  6 E_z of column c  (c = first column of the right tile)
+// Every read of a seam column of the read set in fused2_step_tile — each of them takes the repaired value when REP is set:
+//   lane 63 of a tile with a right neighbour (column c-1 = its element V-1): the plane's loads of E_x E_y [k+1], E_z H_y H_z [k],
+//     E_x E_z of the row above [k] (E_x: where it is loaded — the workgroup's top row, a chunk's first iteration — else the wave above
+//     publishes its own, repaired, value), its right-hand neighbours E_y E_z [k] of column c; in front of the march E_x E_y [kA] and
+//     the prologue's E_x E_y E_z H_y [kA-1], E_z of the row above and of column c
+//   lane 0 of a tile with a left neighbour (column c = its element 0): the plane's loads of E_y [k+1], E_z [k], E_z of the row above,
+//     and all it loads of column c-1 for H1_{y,z} there (E_x [k+1], E_x E_y E_z H_y H_z [k], E_x of the row above); in front of the
+//     march E_y [kA], E_x [kA] of column c-1 and the prologue's E_y E_z [kA-1], E_z of the row above
+// (H_x is right on both columns; the ghost plane nz is not repaired: it is read from the fields.)
+constexpr int kRepArrays = 7;
+__device__ __forceinline__ long long rep_base(const GridP& g, int n_tiles_x) {
+  return (long long)n_tiles_x * kSeamArrays * (g.nz + 2) * g.ny;
+}
+__device__ __forceinline__ long long rep_at(const GridP& g, int seam, int arr, int j, int k) {
+  return (((long long)seam * kRepArrays + arr) * g.nz + k) * g.ny + j;
 }
 
 // OPT: bit 0 = non-temporal stores, bit 1 = materials (packed medium words + (Ca, Cb) table, as fused_step_kernel<MAT>),
@@ -230,6 +253,8 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
   // stored outside it, and the seam scratch is written for every row / plane this workgroup computes (the seam kernel
   // differentiates the row and plane below the box's first ones, which no workgroup owns).
   constexpr bool CLIP = (OPT & 16) != 0;
+  constexpr bool REP = (OPT & 8192) != 0;  // the seam columns of the read set come from the compact repair array (deferred seam repair, above)
+  static_assert(!REP || (!CLIP && !PF && !EZL && !DISP && !SRC), "deferred seam repair: plain, materials and absorber sweeps of the whole grid");
   // periodic x (clipped launches only; periodic y / z faces are part of the shell: the box stays two cells clear of them): the
   // first lane of a row takes column nx - 1 as its x-halo column, the last one column 0 as its right neighbour — step one is
   // exact — and the wrap is one more seam for step two (the row's last column | its first), repaired by seam_kernel
@@ -315,6 +340,14 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
   }
   const float ipy = s.ipy[j], idy = s.idy[j];
 
+  // deferred seam repair: this row in array 0, plane 0 of the seam on the right / on the left of the tile
+  [[maybe_unused]] long long rep_arr = 0;
+  [[maybe_unused]] const float *rpl = nullptr, *rpr = nullptr;
+  if constexpr (REP) {
+    rep_arr = (long long)g.nz * g.ny;
+    rpl = seam + rep_base(g, nbx) + rep_at(g, tile_x, 0, j, 0);
+    rpr = seam + rep_base(g, nbx) + rep_at(g, tile_x > 0 ? tile_x - 1 : 0, 0, j, 0);
+  }
   // carried along the march
   float exk[V], eyk[V];                    // E^n_{x,y}[k]
   float h1x[V], h1y[V], h1z[V];            // H1[k-1]
@@ -331,6 +364,10 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
     ldf<V, true>(exk, uni(a.ex + p0), ubc);
     ldf<V, true>(eyk, uni(a.ey + p0), ubc);
     if (xh) exk_m = a.ex[p0 + im];
+    if constexpr (REP) {
+      if (act && tx == 63 && !last_x) { const float* r = rpl + (long long)kA * g.ny; exk[V - 1] = r[2 * rep_arr]; eyk[V - 1] = r[3 * rep_arr]; }
+      if (xh) { const float* r = rpr + (long long)kA * g.ny; eyk[0] = r[5 * rep_arr]; exk_m = r[2 * rep_arr]; }
+    }
   }
   // ---- prologue: H1_{x,y}[kA-1] (a chunk that starts on the z-min wall needs none: E1_{x,y}[0] = 0 there) ----------
   if (kA > 0 && do_e1) {
@@ -346,6 +383,18 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
     const float ipz = s.ipz[kA - 1];
     ldf<V, true>(ho, uni(a.hx + pb), ubc);
     ldf<V, true>(hoy, uni(a.hy + pb), ubc);
+    if constexpr (REP) {
+      if (act && tx == 63 && !last_x) {
+        const float* r = rpl + (long long)(kA - 1) * g.ny;
+        hoy[V - 1] = r[0]; exm[V - 1] = r[2 * rep_arr]; eym[V - 1] = r[3 * rep_arr]; ezm[V - 1] = r[4 * rep_arr]; ezx = r[6 * rep_arr];
+        if (use_jp) ezj[V - 1] = r[4 * rep_arr + 1];
+      }
+      if (xh) {
+        const float* r = rpr + (long long)(kA - 1) * g.ny;
+        eym[0] = r[5 * rep_arr]; ezm[0] = r[6 * rep_arr];
+        if (use_jp) ezj[0] = r[6 * rep_arr + 1];
+      }
+    }
     if constexpr (DAMP) {
       const float czp = dmp.fc[2][kA - 1];
       const float4 b4 = xdm[tx], c4 = xdm[64 + tx];
@@ -440,15 +489,43 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
     else if constexpr (PF != 10 && PF != 11) ldf<V, true>(L.hyn, uni(a.hy + pb), ubc);
     if constexpr (PF != 10) ldf<V, true>(L.hzn, uni(a.hz + pb), ubc);
     L.eyx_g = 0.f; L.ezx_g = 0.f;
-    if (act && txo == 63 && !last_x) { L.eyx_g = a.ey[pb + ux + V]; L.ezx_g = a.ez[pb + ux + V]; }
+    const bool from_rep = REP && k < g.nz;     // (the seam columns of this plane come from the repair array, below)
+    if (act && txo == 63 && !last_x && !from_rep) { L.eyx_g = a.ey[pb + ux + V]; L.ezx_g = a.ez[pb + ux + V]; }
     if (per_x && act && last_x) { L.eyx_g = a.ey[pb]; L.ezx_g = a.ez[pb]; }        // (the row's first column)
     L.exn_m = 0.f; L.ez_mm = 0.f; L.ey_mm = 0.f; L.ex_jm = 0.f; L.hy_o = 0.f; L.hz_o = 0.f;
-    if (xh && do_e1) {
+    if (xh && do_e1 && !from_rep) {
       const long long pm = pb + im;
       L.exn_m = a.ex[pm + up];
       L.ez_mm = a.ez[pm]; L.ey_mm = a.ey[pm];
       L.ex_jm = use_jp ? a.ex[pjb + im] : 0.f;
       L.hy_o = a.hy[pm]; L.hz_o = a.hz[pm];
+    }
+    if constexpr (REP) {              // the seam columns: the repaired values (planes 0 .. nz-1; iteration nz uses nothing of them)
+      if (k < g.nz) {
+        const bool up1 = k + 1 < g.nz;
+        if (act && txo == 63 && !last_x) {
+          const float* r = rpl + (long long)k * g.ny;
+          L.hyn[V - 1] = r[0]; L.hzn[V - 1] = r[rep_arr]; L.ezk[V - 1] = r[4 * rep_arr];
+          L.eyx_g = r[5 * rep_arr]; L.ezx_g = r[6 * rep_arr];
+          if (up1) { L.exn[V - 1] = r[2 * rep_arr + g.ny]; L.eyn[V - 1] = r[3 * rep_arr + g.ny]; }
+          if (use_jp) {
+            L.ezj[V - 1] = r[4 * rep_arr + 1];
+            if (!EXJ || ty == W - 1 || k == kA) L.exj[V - 1] = r[2 * rep_arr + 1];
+          }
+        }
+        if (xh) {
+          const float* r = rpr + (long long)k * g.ny;
+          L.ezk[0] = r[6 * rep_arr];
+          if (up1) L.eyn[0] = r[5 * rep_arr + g.ny];
+          if (use_jp) L.ezj[0] = r[6 * rep_arr + 1];
+          if (do_e1) {
+            L.exn_m = up1 ? r[2 * rep_arr + g.ny] : a.ex[pb + im + up];       // (plane nz: the ghost plane of the fields)
+            L.ez_mm = r[4 * rep_arr]; L.ey_mm = r[3 * rep_arr];
+            if (use_jp) L.ex_jm = r[2 * rep_arr + 1];
+            L.hy_o = r[0]; L.hz_o = r[rep_arr];
+          }
+        }
+      }
     }
     if constexpr (PF != 0) {          // what came through LDS (requested a plane ago; every load of this plane is out by now)
       lds_dma_wait();
@@ -747,7 +824,7 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
           }
         }
         // what the neighbouring x tile needs of this step: repaired on the seam by seam_kernel
-        if ((CLIP || (own && k >= k0 && k < k1)) && act) {
+        if (WHATIF != 9 && (CLIP || (own && k >= k0 && k < k1)) && act) {
           float* sp = seam + seam_row + (long long)k * g.ny;
           if (seam_l) {
             sp[0] = hyn[V - 1];
@@ -1000,12 +1077,12 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
       if (act && (!CLIP || (i0o >= clip.i0 && i0o < clip.i1))) {
         // H2 next to the seams, for seam_kernel (so that it reads nothing but the scratch array, row-contiguous)
         float* sq = seam + seam_row + (long long)(k - 1) * g.ny;
-        if (!CLIP && txo == 63 && !last_x) {
+        if (!CLIP && WHATIF != 9 && txo == 63 && !last_x) {
           sq[7 * seam_arr] = h2x[V - 1];
           sq[8 * seam_arr] = h2y[V - 2];
           sq[9 * seam_arr] = h2z[V - 2];
         }
-        if (!CLIP && txo == 0 && tile_x > 0) {
+        if (!CLIP && WHATIF != 9 && txo == 0 && tile_x > 0) {
           sq[10 * seam_arr - kSeamArrays * seam_arr] = h2x[0];
           sq[11 * seam_arr - kSeamArrays * seam_arr] = h2y[0];
           sq[12 * seam_arr - kSeamArrays * seam_arr] = h2z[0];
@@ -1110,8 +1187,11 @@ __global__ __launch_bounds__(LB, (LB == 512 ? 4 : 1)) void fused2_step_kernel(Gr
 // stay zero).  H2_{y,z}[c-1] of the row below and of the plane below are recomputed rather than exchanged: one launch.
 // Round 6: the E-side source terms of step n+1 on a seam column are added here when the sweep added the others (inj.e2_in_sweep):
 // a node next to a seam no longer sends all of them behind the launch.
+// `rep` (deferred seam repair, whole-grid launches): the seven values go — the same bits, consecutive threads to consecutive
+// addresses — into the compact repair array instead of set `b`; the next sweep reads them there, seam_flush_kernel scatters them.
 __global__ __launch_bounds__(256) void seam_kernel(GridP g, FieldP b, StepP s, MatP m,
-                                                   const float* __restrict__ seam, int n_seams, DampT dmp, ClipP clip, InjP inj, SrcP sr) {
+                                                   const float* __restrict__ seam, int n_seams, DampT dmp, ClipP clip, InjP inj, SrcP sr,
+                                                   float* __restrict__ rep) {
   // (clip: the box the sweep wrote — the whole grid, or the bulk of a grid whose shell takes single steps; rows and planes
   //  are those of the box, and a seam column that lies outside it is left alone)
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1159,7 +1239,7 @@ __global__ __launch_bounds__(256) void seam_kernel(GridP g, FieldP b, StepP s, M
   const bool mir_y = (j == 0) && pmc_y0, mir_z = (k == 0) && pmc_z0;
   const long long pr = (long long)k * g.sxy + (long long)j * g.nx;
   const long long p = pr + cc, pl = pr + c - 1;                              // the right column (c, or the row's first) / the left one
-  if (wl) { b.hy[pl] = hy_m; b.hz[pl] = hz_m; }
+  if (!rep && wl) { b.hy[pl] = hy_m; b.hz[pl] = hz_m; }
   const float idy = s.idy[j], idz = s.idz[k], idx_m = s.idx[c - 1], idx_c = s.idx[cc];
   const float hx_m = A(7, j, k), hy_mm = A(8, j, k), hz_mm = A(9, j, k);
   const float hx_c = A(10, j, k), hy_c = A(11, j, k), hz_c = A(12, j, k);
@@ -1215,8 +1295,27 @@ __global__ __launch_bounds__(256) void seam_kernel(GridP g, FieldP b, StepP s, M
     ex_m *= cxm * byv * bzv; ey_m *= bxm * cyv * bzv; ez_m *= bxm * byv * czv;
     ey_c *= bxc * cyv * bzv; ez_c *= bxc * byv * czv;
   }
+  if (rep) {
+    float* r = rep + rep_at(g, sm, 0, j, k);
+    const long long ra = (long long)g.nz * g.ny;
+    r[0] = hy_m; r[ra] = hz_m; r[2 * ra] = ex_m; r[3 * ra] = ey_m; r[4 * ra] = ez_m; r[5 * ra] = ey_c; r[6 * ra] = ez_c;
+    return;
+  }
   if (wl) { b.ex[pl] = ex_m; b.ey[pl] = ey_m; b.ez[pl] = ez_m; }
   if (wr) { b.ey[p] = ey_c; b.ez[p] = ez_c; }
+}
+
+// the repair array into the seam columns of set `b`: what seam_kernel would have stored there (whole grid, no periodic x)
+__global__ __launch_bounds__(256) void seam_flush_kernel(GridP g, FieldP b, const float* __restrict__ rep, int n_seams) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long per = (long long)g.ny * g.nz;
+  if (t >= per * n_seams) return;
+  const int sm = (int)(t / per), k = (int)((t % per) / g.ny), j = (int)(t % g.ny);
+  const float* r = rep + rep_at(g, sm, 0, j, k);
+  const long long ra = per;
+  const long long p = (long long)k * g.sxy + (long long)j * g.nx + (sm + 1) * 256, pl = p - 1;
+  b.hy[pl] = r[0]; b.hz[pl] = r[ra]; b.ex[pl] = r[2 * ra]; b.ey[pl] = r[3 * ra]; b.ez[pl] = r[4 * ra];
+  b.ey[p] = r[5 * ra]; b.ez[p] = r[6 * ra];
 }
 
 }  // namespace fdtd

@@ -664,6 +664,12 @@ class HipEngine:
                                      f"{C.sizeof(L.FdtdStats)}: rebuild the library (python -m tidy3d_amd.build)")
         return st
 
+    def seam_stats(self) -> L.FdtdSeamStats:
+        """Deferred seam repair of the last run (FDTD_OPT_SEAM_DEFER): deferred pairs, flushes, flush time."""
+        st = L.FdtdSeamStats()
+        self._chk(self.lib.dll.fdtd_get_seam_stats(self.handle, C.byref(st)), "fdtd_get_seam_stats")
+        return st
+
     def set_option(self, key: int, value: int):
         self._chk(self.lib.dll.fdtd_set_option(self.handle, key, value), "fdtd_set_option")
 

@@ -38,14 +38,14 @@ SYMBOLS = (
     "fdtd_add_point_source", "fdtd_add_tfsf", "fdtd_add_monitor", "fdtd_get_monitor",
     "fdtd_set_field", "fdtd_get_field", "fdtd_set_shutoff", "fdtd_comm_unique_id",
     "fdtd_comm_init", "fdtd_run", "fdtd_run_bloch", "fdtd_get_stats", "fdtd_reset", "fdtd_set_option",
-    "fdtd_far_field", "fdtd_set_mirror_plus", "fdtd_add_aniso", "fdtd_add_aniso_bloch",
+    "fdtd_far_field", "fdtd_set_mirror_plus", "fdtd_add_aniso", "fdtd_add_aniso_bloch", "fdtd_get_seam_stats",
 )
 
 BC_PEC, BC_PMC, BC_PERIODIC, BC_NEIGHBOR = 0, 1, 2, 3
 MON_TIME, MON_DFT = 0, 1
 VARIANT_AUTO, VARIANT_SIMPLE, VARIANT_ZMARCH, VARIANT_FUSED = 0, 1, 2, 3
 FLAG_TIME_KERNELS = 1
-OPT_FLAGS, OPT_VARIANT, OPT_ZCHUNK, OPT_ROWS, OPT_XCD_REMAP, OPT_FUSED_LB, OPT_PML_FUSED, OPT_BND_PLANES, OPT_AUTOTUNE, OPT_PML_SPLIT, OPT_LDS_PAD, OPT_MEM_HINTS, OPT_PLACEMENT_TRIES, OPT_TBLOCK, OPT_EDGE_ZCHUNK, OPT_GRAPH, OPT_TWOSTEP, OPT_SHELL_PAIRS, OPT_STRIP, OPT_SHELL2, OPT_SHELL2_SHAPE, OPT_DEBUG_SYNC, OPT_TILE_SPLIT, OPT_DISP, OPT_WHATIF, OPT_SRC_PAGED, OPT_SLAB_BOXES_FIRST = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26
+OPT_FLAGS, OPT_VARIANT, OPT_ZCHUNK, OPT_ROWS, OPT_XCD_REMAP, OPT_FUSED_LB, OPT_PML_FUSED, OPT_BND_PLANES, OPT_AUTOTUNE, OPT_PML_SPLIT, OPT_LDS_PAD, OPT_MEM_HINTS, OPT_PLACEMENT_TRIES, OPT_TBLOCK, OPT_EDGE_ZCHUNK, OPT_GRAPH, OPT_TWOSTEP, OPT_SHELL_PAIRS, OPT_STRIP, OPT_SHELL2, OPT_SHELL2_SHAPE, OPT_DEBUG_SYNC, OPT_TILE_SPLIT, OPT_DISP, OPT_WHATIF, OPT_SRC_PAGED, OPT_SLAB_BOXES_FIRST, OPT_SEAM_DEFER = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27
 # FdtdStats.fused2_off_reason (include/fdtd_hip.h FDTD_F2_OFF_*)
 F2_OFF_REASONS = {0: "", 1: "switched off", 2: "grid too small", 3: "z-slab rank", 4: "CPML (shell pairs not possible)",
                   5: "dispersive media not confined to a few planes along z", 6: "TFSF box while it injects", 7: "Bloch / PMC-plus faces (or rows not a multiple of 4 cells)", 8: "magnetic sources with absorber layers",
@@ -80,6 +80,11 @@ class FdtdStats(C.Structure):
                 ("seam_kernel_ms", C.c_double), ("seam_kernel_launches", C.c_int64)]
 
 
+class FdtdSeamStats(C.Structure):
+    _fields_ = [("seam_deferred_pairs", C.c_int64), ("seam_flushes", C.c_int64), ("seam_pending", C.c_int32),
+                ("reserved", C.c_int32), ("seam_flush_ms", C.c_double)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_int64, C.c_double, C.c_double, C.c_void_p)
 
 
@@ -101,6 +106,7 @@ class FdtdLib:
         d.fdtd_create.argtypes = [C.POINTER(FdtdConfig), C.POINTER(vp)]
         d.fdtd_destroy.argtypes = [vp]
         d.fdtd_destroy.restype = None
+        d.fdtd_get_seam_stats.argtypes = [vp, C.POINTER(FdtdSeamStats)]
         d.fdtd_set_steps.argtypes = [vp, C.c_int, vp, vp, C.c_int]
         d.fdtd_set_media.argtypes = [vp, vp, vp, C.c_int]
         d.fdtd_set_material.argtypes = [vp, vp, C.c_size_t]
