@@ -287,80 +287,86 @@ int fdtd_run_bloch(FdtdSolver* h_re, FdtdSolver* h_im, int64_t n_steps, const do
                    FdtdProgressFn progress, void* user);
 /* ref web/api/webapi.py:370 (task status incl. "diverged"), web/core/task_core.py:537 (run info) */
 int fdtd_get_stats(FdtdSolver* h, FdtdStats* out);
-/* tuning knobs that may change between runs of one handle (bench A/B without re-upload) */
-enum { FDTD_OPT_FLAGS = 0, FDTD_OPT_VARIANT = 1, FDTD_OPT_ZCHUNK = 2, FDTD_OPT_ROWS = 3, FDTD_OPT_XCD_REMAP = 4 /* tile order of the sweep: -1 = default (runs of 8 tiles per XCD), 0 = plain, 1 = a contiguous eighth per XCD, G > 1 = runs of G tiles */,
-       FDTD_OPT_FUSED_LB = 5,
-       FDTD_OPT_PML_FUSED = 6 /* axes (bit mask) whose CPML recursions run inside the fused sweep: -1 = default (one GPU: all; z-slab ranks: slab kernels), 0 = slab kernels, 6 / 7 = y z / all inside the sweep — on z-slab ranks too (set it on every rank) */,
-       FDTD_OPT_BND_PLANES = 7 /* planes per boundary chunk of the fused z-slab schedule, 0 = default (2) */,
-       FDTD_OPT_AUTOTUNE = 8 /* 1: time a few tile shapes of the fused sweep on the first run of grids >= 2^20 cells (default 0) */,
-       FDTD_OPT_PML_SPLIT = 9 /* CPML-carrying step as three launches over interior / edge tiles: -1 = by grid size (default), 0, 1 */,
-       FDTD_OPT_PLACEMENT_TRIES = 12, /* alternative placements of the field arrays the first large one-GPU run samples (0 ... 8, default 6; 0 = keep the first allocations): each costs six sweeps and a further copy of the field memory until the probe ends (candidates that lose are held so that the next one lands elsewhere) */
-       FDTD_OPT_MEM_HINTS = 11, /* 1 (default): the measured store placement of the sweep (without CPML: non-temporal field stores, H ahead of the row exchange; with CPML: the H-side psi behind the E update); 0: plain stores, fields at the end of the plane, H-side psi in the H phase */
+/* tuning knobs that may change between runs of one handle (bench A/B without re-upload).  Each key's comment ends with what the
+ * tests establish for it.  "Switched between runs: lifecycle tests" = tests/test_emu_lifecycle.py / tests/test_gpu_lifecycle.py switch
+ * it A / B / A inside one engine; the engine ends on the bits of a fresh handle that took single steps, and its per-run counters show
+ * the path change and change back.  fdtd_add_point_source, fdtd_add_tfsf and fdtd_add_monitor are accepted between runs as well (a
+ * monitor's first record step lies behind the steps done): node tables and paged source tables are rebuilt for the lists of the next
+ * run.  fdtd_add_ade is refused once the memory terms are paged. */
+enum { FDTD_OPT_FLAGS = 0 /* Not switched between runs by any test. */, FDTD_OPT_VARIANT = 1 /* Switched between runs: lifecycle tests. */, FDTD_OPT_ZCHUNK = 2 /* Switched between runs: lifecycle tests. */, FDTD_OPT_ROWS = 3 /* Switched between runs: lifecycle tests. */, FDTD_OPT_XCD_REMAP = 4 /* tile order of the sweep: -1 = default (runs of 8 tiles per XCD), 0 = plain, 1 = a contiguous eighth per XCD, G > 1 = runs of G tiles. Switched between runs: lifecycle tests. */,
+       FDTD_OPT_FUSED_LB = 5 /* Not switched between runs by any test. */,
+       FDTD_OPT_PML_FUSED = 6 /* axes (bit mask) whose CPML recursions run inside the fused sweep: -1 = default (one GPU: all; z-slab ranks: slab kernels), 0 = slab kernels, 6 / 7 = y z / all inside the sweep — on z-slab ranks too (set it on every rank). Switched between runs: lifecycle tests. */,
+       FDTD_OPT_BND_PLANES = 7 /* planes per boundary chunk of the fused z-slab schedule, 0 = default (2). Not switched between runs by any test. */,
+       FDTD_OPT_AUTOTUNE = 8 /* 1: time a few tile shapes of the fused sweep on the first run of grids >= 2^20 cells (default 0). Not switched between runs by any test. */,
+       FDTD_OPT_PML_SPLIT = 9 /* CPML-carrying step as three launches over interior / edge tiles: -1 = by grid size (default), 0, 1. Switched between runs: lifecycle tests. */,
+       FDTD_OPT_PLACEMENT_TRIES = 12, /* alternative placements of the field arrays the first large one-GPU run samples (0 ... 8, default 6; 0 = keep the first allocations): each costs six sweeps and a further copy of the field memory until the probe ends (candidates that lose are held so that the next one lands elsewhere). Not switched between runs by any test. */
+       FDTD_OPT_MEM_HINTS = 11, /* 1 (default): the measured store placement of the sweep (without CPML: non-temporal field stores, H ahead of the row exchange; with CPML: the H-side psi behind the E update); 0: plain stores, fields at the end of the plane, H-side psi in the H phase. Switched between runs: lifecycle tests. */
        FDTD_OPT_TBLOCK = 13, /* one-GPU fused runs without CPML / TFSF / periodic z: advance TWO time steps per pass over
                                 the grid, slab by slab (slab s+1 takes step n, then slab s takes step n+1 while the
                                 intermediate planes are still in the 256 MiB Infinity Cache): planes per slab; 0 = off,
-                                -1 = default */
+                                -1 = default. Switched between runs: lifecycle tests. */
        FDTD_OPT_EDGE_ZCHUNK = 14, /* planes per workgroup of the EDGE launches of a CPML step (tiles that meet a y / z slab):
                                      -1 = default (z-slab ranks, where they share the interior launch's stream: about one wave of
-                                     workgroups, at least 2 planes; one GPU: as the interior launch), 0 = as the interior launch, N */
+                                     workgroups, at least 2 planes; one GPU: as the interior launch), 0 = as the interior launch, N. Switched between runs: lifecycle tests. */
        FDTD_OPT_GRAPH = 15, /* one-GPU fused runs on one stream: steps without monitor records / decay checks replayed as captured
                                hipGraphs of two steps: -1 = default (off: on ROCm 7.2 replaying costs ~3 us per step MORE than the
-                               launches it replaces, profiles/r3i), 0 = never, 1 = whenever possible */
+                               launches it replaces, profiles/r3i), 0 = never, 1 = whenever possible. Switched between runs: lifecycle tests (device; captured graphs live for one fdtd_run, so a change of tile shape or of the source lists between runs cannot meet a stale one). */
        FDTD_OPT_TWOSTEP = 16, /* two time steps per sweep (in-kernel temporal blocking, bit-identical to single steps; non-dispersive media, PEC
                                  walls (PMC allowed on the min faces), absorber layers, point sources while they inject (any sources once
                                  they are spent), small time monitors, DFT monitors, no decay check on the middle step; CPML and periodic
                                  faces through shell pairs (FDTD_OPT_SHELL_PAIRS), z-slab ranks without CPML with their boundary planes as
                                  the shell — everything else takes single steps, FdtdStats.fused2_off_reason says why): -1 = default (on,
                                  tile shape by grid size), 0 = off, else waves per workgroup (4 ... 16; W - 3 rows of a tile are written)
-                                 + 64 * planes per chunk (0 = by grid size) */
+                                 + 64 * planes per chunk (0 = by grid size). Switched between runs (any shape, 0, -1): lifecycle tests. */
        FDTD_OPT_SHELL_PAIRS = 17, /* step pairs on grids with CPML or periodic faces (the two-step sweep over the bulk; the shell — CPML slabs +
                                      a two-cell collar, the two rows / planes next to a periodic y / z face — as two single steps beside it
                                      on the second stream, through a third field set; periodic x wraps inside the sweep; bit-identical to
                                      single steps), and on z-slab ranks: -1 = default (on), 0 = off, 2 = shell behind the bulk on ONE stream
-                                     (a measuring aid) */
-       FDTD_OPT_STRIP = 18, /* x strips of a shell step: planes per workgroup (1 ... 63) + 64 * workgroups per CU their registers are cut for (3 or 4) */
+                                     (a measuring aid). Switched between runs: lifecycle tests. */
+       FDTD_OPT_STRIP = 18, /* x strips of a shell step: planes per workgroup (1 ... 63) + 64 * workgroups per CU their registers are cut for (3 or 4). Switched between runs: lifecycle tests. */
        FDTD_OPT_SHELL2 = 19, /* the shell of a CPML-walled grid (no periodic z, no absorber layers; a periodic x wraps through the boxes' halo
                                 lanes, the rows next to a periodic y wrap and the planes of dispersive cells take single steps beside the
                                 boxes; sources that inject three or more cells inside the bulk, or on planes that become z holes; z-slab ranks
                                 that carry CPML inside their sweeps too) by shell2_step_kernel — two steps per sweep with psi carried, both
                                 psi sides ping-ponged, no third field set; bit-identical to single steps: -1 = default (where the cost
                                 model likes it), 0 = off (two single steps beside the bulk, FDTD_OPT_SHELL_PAIRS), 1 = wherever possible, 2 / 3 = wherever possible with
-                                one launch per instantiation (x / y / z only, all axes) / per box (measuring aids) */
+                                one launch per instantiation (x / y / z only, all axes) / per box (measuring aids). Switched between runs: lifecycle tests. */
        FDTD_OPT_SHELL2_SHAPE = 20, /* tile shapes of its launches (one per instantiation: x / y / z only, all axes; each over all of its boxes): lanes
                                       per row of the wide boxes (z / y slabs; 3 ... 64, 0 = by box: the shape that wastes the fewest lane-planes)
                                       + 128 * waves per workgroup of the all-axes launch (1 ... 8, default 8) + 1024 * planes per chunk of the wide
                                       boxes (0 = by box) + 2^17 * waves per workgroup of the one-axis launches (1 ... 8, default 6) + 2^21 * planes
-                                      per chunk of the x strips (0 = by box); <= 0: defaults */
+                                      per chunk of the x strips (0 = by box); <= 0: defaults. Switched between runs: lifecycle tests. */
        FDTD_OPT_DEBUG_SYNC = 21, /* 1: a device-wide synchronisation in front of and behind every launch group of fdtd_run (no two launches ever
                                     overlap): a debugging aid — a schedule whose result then differs from the normal run's has a missing
-                                    cross-stream edge.  Default 0 */
+                                    cross-stream edge.  Default 0. A debugging aid; switched between runs: lifecycle tests. */
        FDTD_OPT_TILE_SPLIT = 22, /* the two-step sweep of a grid with bodies: workgroups whose tile (halo rows and planes included) holds only
                                     the background medium run the plain sweep inside the materials launch; same bits: -1 = default (where at
-                                    least one tile in eight is background-only), 0 = never, 1 = wherever such a tile exists */
+                                    least one tile in eight is background-only), 0 = never, 1 = wherever such a tile exists. Switched between runs: lifecycle tests. */
        FDTD_OPT_DISP = 23, /* dispersive (pole-residue ADE) cells advanced INSIDE the two-step sweeps: their pole states move into paged storage
                               (one block per 256-cell row segment that holds a dispersive cell, two sets) before the first run that may take
                               step pairs, and single steps update them there too.  -1 / 1 = default (on one GPU, where the packed medium words
                               name the ADE group of every dispersive cell), 0 = off: the planes of dispersive cells are z holes of the bulk
-                              (single steps, round 5).  Set it before the first fdtd_run. */
+                              (single steps, round 5).  Set it before the first fdtd_run. The setter refuses 0 once the memory terms are paged; the handle is unchanged and goes on: lifecycle tests. */
        FDTD_OPT_SRC_PAGED = 25, /* step pairs WHILE a TFSF box, a mode plane, a current sheet or any list of more than 256 nodes injects (round 6):
                                    in front of each pair list kernels leave what the lists add at steps n (E side), n + 1 (H side) and n + 1
                                    (E side) in paged storage — one block per 256-cell row segment that holds a source node — and the
                                    two-step sweep, its seam kernel and the shell's boxes add them.  -1 / 1 = default (on one GPU, where no
-                                   two lists meet on a node), 0 = off: single steps (or the lists' planes as z holes) while they inject. */
+                                   two lists meet on a node), 0 = off: single steps (or the lists' planes as z holes) while they inject.  May change
+                                   between runs. 0 is honoured on a handle whose tables exist (they are kept and used again when it is switched back).  Switched between runs: lifecycle tests. */
        FDTD_OPT_WHATIF = 24, /* measuring aid (round 6): 1 ... 8 = a what-if instantiation of the vacuum two-step sweep that skips part of its work
                                 (csrc/fdtd_kernels2.hpp lists them) — WRONG results, meaningful times; 0 = off (default);
                                 16 ... 18 = plain pairs without the seam_kernel launch / with it skipped and the sweep reading the repair array /
                                 with seam_kernel storing into the repair array (what deferred seam repair can gain, pays and costs);
-                                19 = the vacuum sweep without its one-lane stores into the seam scratch (and without EXJ: compare with 14) */
-       FDTD_OPT_SLAB_BOXES_FIRST = 26, /* z-slab ranks that carry CPML, step pairs: the shell's boxes are launched in front of the bulk sweep (1), behind it (0: round 5), beside it on a third stream (2), or 2 for slabs of 96 planes and more, else 1 (3, default) */
+                                19 = the vacuum sweep without its one-lane stores into the seam scratch (and without EXJ: compare with 14). A measuring aid; not switched between runs by any test. */
+       FDTD_OPT_SLAB_BOXES_FIRST = 26, /* z-slab ranks that carry CPML, step pairs: the shell's boxes are launched in front of the bulk sweep (1), behind it (0: round 5), beside it on a third stream (2), or 2 for slabs of 96 planes and more, else 1 (3, default). Not switched between runs by any test. */
        FDTD_OPT_SEAM_DEFER = 27, /* deferred seam repair: a plain step pair (whole grid, sixteen-wave plain / materials / absorber sweep) that is
                                     followed in the same fdtd_run by another plain pair — no record, decay check, H-side source launch or ghost-plane
                                     copy between them — leaves the seven values seam_kernel repairs per seam row in a compact array the next
                                     sweep's edge lanes read, instead of storing them into the fields at a row stride.  -1 / 1 = on (default):
                                     launches of sixteen-wave workgroups, which run the instantiation that reads the array anyway; 0 = off;
                                     2 = testing aid: at every workgroup size (smaller workgroups then run the sixteen-wave instantiation —
-                                    another launch bound than their own, not a setting for production runs).  May be switched between runs of one engine (A/B inside one placement of the arrays). */
-       FDTD_OPT_LDS_PAD = 10 /* measuring aid: extra dynamic LDS per workgroup of the sweep in bytes (lowers its occupancy) */ };
+                                    another launch bound than their own, not a setting for production runs).  May be switched between runs of one engine (A/B inside one placement of the arrays). (tests/test_emu_seam_defer.py switches it.) */
+       FDTD_OPT_LDS_PAD = 10 /* measuring aid: extra dynamic LDS per workgroup of the sweep in bytes (lowers its occupancy). Not switched between runs by any test. */ };
 int fdtd_set_option(FdtdSolver* h, int key, int value);
 int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out);
 int fdtd_reset(FdtdSolver* h);      /* zero fields, auxiliaries, monitors and the step counter */

@@ -170,6 +170,7 @@ struct SrcPaged {
   long long pairs = 0;
   std::vector<int> sseg_host;
   SrcT* tab = nullptr;             // the arrays' addresses, in device memory (SrcP::t)
+  size_t n_psrc = 0, n_tfsf = 0;   // the list counts spg_setup saw: lists added since then make the tables stale (spg_release)
 };
 
 struct FdtdSolver {
@@ -2426,6 +2427,7 @@ int spg_setup(FdtdSolver* h) {
   SrcPaged& S = h->spg;
   if (S.state != 0) return 0;
   S.state = -1;
+  S.n_psrc = h->psrc.size(); S.n_tfsf = h->tfsf.size();
   const GridP& g = h->g;
   if (h->spg_on == 0 || h->comm || g.nx % 4 != 0) return 0;
   long long total = 0;
@@ -2503,6 +2505,22 @@ int spg_setup(FdtdSolver* h) {
   S.state = 1;
   h->box_paged.clear();
   return 0;
+}
+// Lists were added (fdtd_add_point_source, fdtd_add_tfsf between two runs) since spg_setup laid the tables out — or gave up: the
+// new list has no slots, a row segment of its own may have no block.  Everything goes back to "not tried" (the next setup_pairs
+// builds it for the lists of now), with what was derived from the segment map: the tile classes, the boxes' flags.
+void spg_release(FdtdSolver* h) {
+  SrcPaged& S = h->spg;
+  (void)hipStreamSynchronize(h->stream);
+  auto drop = [&](auto*& p) { if (p) release_buf(h, p); p = nullptr; };
+  drop(S.sseg); drop(S.e1); drop(S.h2); drop(S.e2); drop(S.e1b); drop(S.h2b); drop(S.e2b); drop(S.tab);
+  for (Tfsf& t : h->tfsf) { drop(t.e.soff); drop(t.h.soff); t.e.layer = t.h.layer = 0; }
+  for (PointSrc& s : h->psrc) { drop(s.soff_e); drop(s.soff_h); s.layer_e = s.layer_h = 0; }
+  S.sseg_host.clear();
+  S.n_blocks = 0; S.any_h = false;
+  S.state = 0;
+  h->tile_cls.clear();
+  h->box_paged.clear();
 }
 // Shell2P::paged of a box: does a row segment it visits — rows j0 - 2 .. j1, planes k0 - 1 .. k1, columns i0 - 8 .. i1 + 7 — hold a
 // source node (bit 0) / a dispersive cell (bit 1)?  Found once per box on the host maps of the segments.
@@ -3440,7 +3458,7 @@ int fdtd_reset(FdtdSolver* h) {
   }
   for (Monitor& m : h->mons) { HIPCHK(h, hipMemset(m.data, 0, m.data_bytes)); m.next = 0; }
   h->step = 0; h->energy_max = 0.0;
-  h->stats.steps_done = 0; h->stats.diverged = 0; h->stats.stopped_early = 0; h->stats.field_decay = 1.0;
+  h->stats.steps_done = 0; h->stats.diverged = 0; h->stats.stopped_early = 0; h->stats.field_decay = 0.0;      // (what a fresh handle reports until its first decay check)
   return 0;
 }
 
@@ -3856,9 +3874,10 @@ struct Run {
         long long len = -1;
         for (const PointSrc& s : h->psrc) if (s.n_e || s.n_h) { if (len >= 0 && s.n_steps != len) needs = true; len = s.n_steps; }
       }
+      if (h->spg.state != 0 && (h->spg.n_psrc != h->psrc.size() || h->spg.n_tfsf != h->tfsf.size())) spg_release(h);      // (lists added since)
       if (needs && spg_setup(h)) return -1;
       // (absorber layers damp H^{n-1/2} inside the sweep, behind the H-side terms of step n that precede it: FDTD_F2_OFF_H_SOURCE_ABSORBER stays)
-      spg_ok = needs && h->spg.state == 1 && !(h->has_damp && h->spg.any_h);
+      spg_ok = needs && h->spg_on != 0 && h->spg.state == 1 && !(h->has_damp && h->spg.any_h);
     }
     f2_ok = fused && !tb_ok && fused2_eligible(h);
     sg = ShellGeom{};
