@@ -317,6 +317,7 @@ struct FdtdSolver {
   double seam_flush_ms = 0.0;
   float* seam_buf = nullptr;          // intermediate values on the seams between x tiles, and behind them the compact repair array (deferred seam repair)
   int seam_defer = -1;                // FDTD_OPT_SEAM_DEFER: -1 / 1 = plain sixteen-wave pairs followed by a plain pair leave their repaired seam values in the compact array, 0 = never, 2 = testing aid: at every workgroup size
+  bool no_jlo = false;                // $FDTD_NO_JLO at fdtd_create (a debugging aid): no box of a shell pair starts its tile rows on the y-min wall
   bool seam_pending = false;          // the seam columns of the current set (h->f) are stale: their values lie in the repair array
   float* inj_val = nullptr;           // source terms applied between the two steps
   float* cap_val = nullptr;           // samples of the middle step (small time monitors)
@@ -1209,6 +1210,7 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
                   const ClipP* clip = nullptr, bool use_disp = false, bool e2_clip = false, const SrcP& sr = SrcP{}, bool defer_ok = false) {
   const bool inject = tb->with_sources;      // (false: the lists are spent, or — shell pairs with z holes — their planes take single steps)
   const GridP& g = h->g;
+  if (use_disp && !h->mat4) return fail(h, "launch_fused2: dispersive cells in a pair without the materials grid");
   if (ensure_second_set(h)) return -1;
   int W = 16, zc = 32;
   const ClipP box = clip ? *clip : ClipP{0, g.nx, 0, g.ny, 0, g.nz};
@@ -1285,12 +1287,9 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   const MatP mp = mat_params(h);
   DispP dp{nullptr, nullptr, nullptr};
   if (use_disp) dp = DispP{h->disp.dseg, h->disp.cs, h->disp.e1};
-  int opt = (h->mem_hints ? 1 : 0) | (h->mat4 ? 2 : 0) | ((tb->mons.empty() && (!tb->with_sources || h->src_h_nodes == 0) && !tb->dstart) ? 0 : 4) |
-            (clip ? 16 : (h->has_damp ? 8 : 0)) | (use_disp ? 32 | 1 : 0);
-  if (h->whatif == 19 && opt == 1 && W == 16) opt |= 9 << 8;        // (the sweep without its stores into the seam scratch)
-  if (h->whatif > 0 && h->whatif <= 15 && h->whatif != 9 && opt == 1 && (W == 16 || h->whatif == 13 || h->whatif == 14)) opt |= h->whatif << 8;        // (measuring aid: the vacuum sweep with part of its work skipped)
+  const bool damp = !clip && h->has_damp;
   SrcP sr_used = sr;
-  if (h->whatif == 9 && !sr.sseg && !(opt & 8) && (!(opt & 32) || (opt & 16))) {
+  if (h->whatif == 9 && !sr.sseg && !damp && (!use_disp || clip)) {
     // measuring aid (scripts/probe_bodies.py): the instantiation that adds paged source terms over a map WITHOUT any source segment —
     // every tile dispatches to the bodies the plain launch runs: what the larger kernel costs by itself (results unchanged)
     SrcPaged& S = h->spg;
@@ -1300,15 +1299,24 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
       SrcT tab{};
       if (dev_upload(h, &S.sseg, (const int*)S.sseg_host.data(), nseg) || dev_upload(h, &S.tab, &tab, 1)) return -1;
     }
-    if (S.sseg && S.state != 1) { sr_used.sseg = S.sseg; sr_used.t = S.tab; opt |= 64 | 4 | 1; }
+    if (S.sseg && S.state != 1) { sr_used.sseg = S.sseg; sr_used.t = S.tab; }
   }
-  if (sr.sseg) { opt |= 64 | 4 | 1; *sources2_done = true; h->spg.pairs++; }
+  // the word of the launch (fdtd_fused2.hpp).  What-if variants: measuring aids, the vacuum sweep with part of its work skipped (19: the
+  // sweep without its stores into the seam scratch, variant 9 of the kernel; option 9 itself is the map above)
+  const int wv = h->whatif == 19 ? 9 : ((h->whatif >= 1 && h->whatif <= 15 && h->whatif != 9) ? h->whatif : 0);
+  const auto word = [&](bool rep) {
+    return fused2_opt(h->mem_hints != 0, h->mat4 != nullptr, !(tb->mons.empty() && (!tb->with_sources || h->src_h_nodes == 0) && !tb->dstart),
+                      clip != nullptr, damp, use_disp, sr_used.sseg != nullptr, wv, rep, W);
+  };
   // deferred seam repair: the sixteen-wave plain / materials / absorber sweep of the whole grid reads and leaves the compact array
   // (its sixteen-wave instantiation serves every workgroup size; by default only the launches that run it anyway defer)
-  const bool rep_capable = n_seams > 0 && !clip && (W == 16 || h->seam_defer == 2) && (opt & ~(1 | 2 | 8)) == 0;
+  const bool rep_capable = n_seams > 0 && !clip && (W == 16 || h->seam_defer == 2) && fused2_rep_word(word(false));
+  const int opt = word(rep_capable && (h->seam_pending || h->whatif == 17));
+  const auto no_sweep = [&] { return fail(h, "launch_fused2: no instantiation of the sweep for opt 0x%x, %d waves", opt, W); };
+  if (!fused2_instantiated(fused2_lb(W, opt), opt)) return no_sweep();       // (in front of everything that changes the handle's state)
+  if (sr.sseg) { *sources2_done = true; h->spg.pairs++; }
   float* const rep_arr = h->seam_buf ? h->seam_buf + seam_scratch_floats(g, nbx) : nullptr;
   if (h->seam_pending && !rep_capable) flush_seams(h, st);      // (the set it flushes, h->f, is the one this launch reads)
-  if (h->seam_pending || (h->whatif == 17 && rep_capable)) opt |= 8192;
   h->seam_pending = false;
   bool defer = defer_ok && rep_capable && h->seam_defer != 0 && h->whatif == 0;
   if (defer) {        // nothing may touch the set behind the seam kernel: E-side sources of step n + 1 and the damping of E^{n+2} are in the sweep, or absent
@@ -1320,9 +1328,10 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   // background-only tiles take the plain sweep inside the materials launch (fdtd_kernels2.hpp, tile classes)
   const FdtdSolver::TileClasses* tc = tile_classes(h, W, zc, box, nbx, nby, nbz, use_disp, sr_used.sseg != nullptr);
   const bool split = tc && (use_disp || sr_used.sseg || (tc->n_bg > 0 && (h->tile_split == 1 || 8 * tc->n_bg >= tc->n_all)));
-  launch_fused2_step(st, W, opt, blocks, g, h->f, h->f2, sp, mp, zc, nbx, nby, nbz, remap, inj, h->seam_buf, dmp, box,
-                     TileClassP{split ? tc->dev : nullptr}, dp, sr_used);
+  const bool launched = launch_fused2_step(Fused2Launch{st, W, opt, blocks, g, h->f, h->f2, sp, mp, zc, nbx, nby, nbz, remap, inj, h->seam_buf, dmp, box,
+                                                        TileClassP{split ? tc->dev : nullptr}, dp, sr_used});
   time_end(h, st);
+  if (!launched) return no_sweep();       // (a unit's case labels and fused2_instantiated expand the same lists)
   if (n_seams > 0 && !(rep_capable && (h->whatif == 16 || h->whatif == 17))) {
     time_begin(h, 4, st);
     launch_seams(st, g, h->f2, sp, mp, h->seam_buf, n_seams, dmp, box, inj, sr, (defer || (h->whatif == 18 && rep_capable)) ? rep_arr : nullptr);
@@ -1632,7 +1641,7 @@ void shell2_shape(const FdtdSolver* h, const Shell2Box& bx, int W, int zc_cap, S
     if (q > std::max(3, L)) break;
     const int S = (64 / q) * W;
     // (a box that starts on the y-min wall — a wall, not a periodic wrap — and fits one tile row without the two halo slots below: jlo = 0)
-    const bool wall_lo = bx.j0 == 0 && h->cfg.bc[2] != FDTD_BC_PERIODIC && rows <= S - 1 && !getenv("FDTD_NO_JLO");      // ($FDTD_NO_JLO: a debugging aid)
+    const bool wall_lo = bx.j0 == 0 && h->cfg.bc[2] != FDTD_BC_PERIODIC && rows <= S - 1 && !h->no_jlo;
     const int jlo = wall_lo ? 0 : 2;
     const int R = S - 1 - jlo;
     if (R < 1) continue;
@@ -2860,6 +2869,7 @@ int fdtd_create(const FdtdConfig* cfg, FdtdSolver** out) {
   if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, "fdtd_create: device %d out of range (%d devices)", cfg->device, ndev);
   FdtdSolver* h = new FdtdSolver();
   h->cfg = *cfg;
+  h->no_jlo = getenv("FDTD_NO_JLO") != nullptr;
   if (hipSetDevice(cfg->device) != hipSuccess) { delete h; return fail(nullptr, "hipSetDevice(%d) failed", cfg->device); }
   GridP& g = h->g;
   g.nx = cfg->nx; g.ny = cfg->ny; g.nz = cfg->nz;

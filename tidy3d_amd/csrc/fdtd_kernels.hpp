@@ -1396,7 +1396,7 @@ __global__ __launch_bounds__(256) void ade_kernel(float* e, const uint32_t* cell
   if (cs) cs[qoff[t]] = a.cc * S1;
 }
 
-// K4 twice, behind a two-step sweep that subtracted the memory term of step n itself (fused2_step_kernel, OPT bit 5) and left
+// K4 twice, behind a two-step sweep that subtracted the memory term of step n itself (fused2_step_kernel, kF2Disp) and left
 // E^{n+1} of the dispersive cells in the paged array `e1`: per entry  Q^{n+1} = kap Q^n + bet (E^{n+1} + E^n),
 // E^{n+2} <- E^{n+2} - cc S(Q^{n+1}),  Q^{n+2} = kap Q^{n+1} + bet (E^{n+2} + E^{n+1}),  and the memory term of the step after,
 // cc S(Q^{n+2}), into `cs` — the operations of two ade_kernel launches in their order, the pole states read and written once.

@@ -22,13 +22,13 @@
 // Scope (fdtd_capi.hip checks it): non-dispersive media (uniform, or packed medium words + (Ca, Cb) table), PEC walls (PMC allowed on
 // the min faces: symmetry planes), absorber layers (damped in registers), point sources (<= kMaxInj nodes while they inject; the
 // E-side ones of step n+1 are applied in S4, the H-side ones in S3), small time monitors (their samples of the middle step are
-// copied out for pair_record_kernel) and DFT monitors, one box per launch.  Round 4: the CLIP instantiations (OPT bit 4) write one
+// copied out for pair_record_kernel) and DFT monitors, one box per launch.  Round 4: the CLIP instantiations (kF2Clip) write one
 // box only — the bulk of a grid whose shell takes single steps beside it (fdtd_capi.hip: CPML slabs + collar, the rows / planes
 // next to periodic y / z faces, the boundary planes of a z-slab rank, z holes around dispersive cells and big source planes) —
 // and wrap a periodic x axis inside the sweep.  Everything else takes single steps.
 #pragma once
 #include "fdtd_fused2.hpp"
-// WHAT-IF instantiations (OPT bits 8 - 11; FDTD_OPT_WHATIF, fdtd_fused2w.hip): measuring aids that SKIP part of the work — their
+// WHAT-IF instantiations (fused2_whatif(OPT); FDTD_OPT_WHATIF, fdtd_fused2w.hip): measuring aids that SKIP part of the work — their
 // results are wrong, their times say where the sweep's time goes and bound what an optimisation could gain.  Switched inside one
 // engine (same allocations, same clocks: the only A/B this part resolves), vacuum instantiation only:
 //   1  E_y / H_y of a plane not loaded            2  no second barrier per plane        3  the three halo rows load nothing
@@ -36,7 +36,7 @@
 //   6  no barriers and no LDS exchange (own values instead of the neighbour rows')      7  loads + stores only (the copy floor of this tiling)
 //   8  no barriers, LDS traffic kept
 //   9  the edge lanes' stores into the seam scratch dropped (no EXJ either: its A/B partner is 14)
-// PREFETCH instantiations (OPT bits 8 - 11 = 10 ... 12; CORRECT results, the same bits): part of plane k+1 travels global memory -> LDS
+// PREFETCH instantiations (fused2_whatif(OPT) = 10 ... 12; CORRECT results, the same bits): part of plane k+1 travels global memory -> LDS
 // by LDS-DMA (global_load_lds_dwordx4) while plane k is computed — the one way to keep a second batch of loads in flight that costs
 // no registers (the sweep has 3 of 128 left).  The LDS for it comes from the E1 exchange arrays: published BEHIND the second barrier
 // (read behind the next first barrier) they need no second buffer, which leaves 6 exchange arrays + 3 prefetch arrays = 144 KB.
@@ -123,7 +123,7 @@ __device__ __forceinline__ long long seam_at(const GridP& g, int seam, int arr, 
   return (((long long)seam * kSeamArrays + arr) * (g.nz + 2) + (k + 1)) * g.ny + j;
 }
 
-// Deferred seam repair (OPT bit 13, REP): in a run of plain step pairs the seven values seam_kernel repairs per seam row do not go
+// Deferred seam repair (kF2Rep, REP): in a run of plain step pairs the seven values seam_kernel repairs per seam row do not go
 // into the field arrays (seven 4-byte stores at a row stride each: partial writes to lines long gone from L2) but, coalesced, into a
 // compact array [seam][kRepArrays][nz][ny] behind the scratch arrays of `seam`; the next sweep's edge lanes take them from there
 // instead of the seam columns of its read set, and seam_flush_kernel scatters them into the fields when somebody else reads those.
@@ -145,9 +145,8 @@ __device__ __forceinline__ long long rep_at(const GridP& g, int seam, int arr, i
   return (((long long)seam * kRepArrays + arr) * g.nz + k) * g.ny + j;
 }
 
-// OPT: bit 0 = non-temporal stores, bit 1 = materials (packed medium words + (Ca, Cb) table, as fused_step_kernel<MAT>),
-// bit 3 = absorber layers (the damping of damp_kernel / damp4_kernel applied in registers),
-// bit 2 = the node table holds monitor samples (8-wave workgroups run two per CU: LB = 512 asks for 4 waves per SIMD, i.e. <= 128 VGPRs)
+// OPT: the word of fdtd_fused2.hpp (kF2NT ... kF2Rep) — materials as fused_step_kernel<MAT>, absorber layers as the damping of
+// damp_kernel / damp4_kernel applied in registers.  (8-wave workgroups run two per CU: LB = 512 asks for 4 waves per SIMD, i.e. <= 128 VGPRs)
 // x neighbours across the wave: lane i takes the value of lane i+1 / i-1 (the last / first lane keeps its own, as __shfl_down /
 // __shfl_up do).  One DPP move (wave_shl:1 / wave_shr:1, GFX9) instead of a ds_bpermute through the LDS crossbar with its
 // address arithmetic and its lgkmcnt wait on the critical path of every stage.
@@ -223,16 +222,16 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
                                                  float* __restrict__ seam, const DampT& dmp, const ClipP& clip, int t,
                                                  const DispP& dp, const SrcP& sr) {
   constexpr int V = 4;
-  constexpr bool SRC = (OPT & 64) != 0;    // paged source terms (fdtd_fused2.hpp SrcP): TFSF boxes, mode planes, sheets while they inject
-  constexpr bool NT = (OPT & 1) != 0, MAT = (OPT & 2) != 0, MON = (OPT & 4) != 0;     // MON: the node table may hold monitor samples
+  constexpr bool SRC = (OPT & kF2Src) != 0;    // paged source terms (fdtd_fused2.hpp SrcP): TFSF boxes, mode planes, sheets while they inject
+  constexpr bool NT = (OPT & kF2NT) != 0, MAT = (OPT & kF2Mat) != 0, MON = (OPT & kF2Mon) != 0;     // MON: the node table may hold monitor samples
   // DISP (round 6): the grid holds dispersive cells and the pair advances them (K4 twice).  What the sweep needs of step n's ADE
   // update is E^{n+1} <- E^{n+1} - cc S(Q^n) at those cells — H^{n+3/2} differentiates it — and that memory term is known before
   // the sweep starts: it lies in paged storage (DispP::cs, one block per row segment that holds a dispersive cell, zero at the
   // segment's other cells), kept up to date by the ADE kernels.  S2 subtracts it last of all (as launch_ade follows the damping
   // launch) and leaves E^{n+1} of the rows it owns in DispP::e1; ade2_kernel behind the sweep forms Q^{n+1} from it, corrects
   // E^{n+2} and forms Q^{n+2} — ade_kernel's operations in its order, twice.
-  constexpr bool DISP = (OPT & 32) != 0;
-  constexpr int WHATIF = (OPT >> 8) & 15;
+  constexpr bool DISP = (OPT & kF2Disp) != 0;
+  constexpr int WHATIF = fused2_whatif(OPT);
   constexpr int PF = (WHATIF >= 10 && WHATIF <= 12) ? WHATIF : 0;            // prefetch instantiation (correct results)
   // EXJ: E_x of the row above comes from the wave above through a ninth exchange array (fused2_xch_arrays) instead of a second global
   // load of a line the workgroup has already fetched — 512^3 vacuum inside one engine 0.690 -> 0.675 ms per step (profiles/r6/r6u): the
@@ -241,19 +240,19 @@ __device__ __forceinline__ void fused2_step_tile(const GridP& g, const FieldP& a
   // leave one) nor with absorber layers (below); WHATIF 14 = the sweep without it, for A/B inside one engine.  Whole bench lines of two builds, three rounds
   // interleaved (profiles/r6/r6v): V1 + 3 %, V2 / V3 / V4 + 2 %, the absorber instantiation - 5 % (two more spilled registers) — left out there.
   constexpr bool EZL = WHATIF == 15;                                         // E_z through LDS (variant 15)
-  constexpr bool EXJ = (WHATIF == 0 && (OPT & 4096) == 0) || WHATIF == 13 || EZL;      // (bit 12: the KERNEL's instantiation has no room for it — set by fused2_step_kernel, which sized the LDS)
+  constexpr bool EXJ = (WHATIF == 0 && (OPT & kF2NoExj) == 0) || WHATIF == 13 || EZL;      // (kF2NoExj: the KERNEL's instantiation has no room for it — set by fused2_step_kernel, which sized the LDS)
   constexpr bool E1S = PF != 0 || EZL;                                       // E1 exchanged through ONE buffer (published behind the second barrier)
   constexpr int XE = E1S ? 6 : 8, XZ = 7;                                    // exchange arrays of E_x[k+1] (EXJ) and E_z[k+1] (EZL)
   [[maybe_unused]] constexpr int NPF = PF == 11 ? 2 : (PF ? 3 : 0);                           // arrays of the next plane that travel through LDS
   constexpr int NXCH = E1S ? 6 : 8;                                           // exchange arrays (PF: E1 single-buffered)
-  static_assert((!PF && !EZL) || (OPT & 0xfe) == 0, "prefetch instantiations: the vacuum sweep only");
-  constexpr bool DAMP = (OPT & 8) != 0;   // absorber layers: both fields of both steps are damped in registers (damp_kernel's factors)
+  static_assert((!PF && !EZL) || (OPT & 0xff & ~kF2NT) == 0, "prefetch instantiations: the vacuum sweep only");
+  constexpr bool DAMP = (OPT & kF2Damp) != 0;   // absorber layers: both fields of both steps are damped in registers (damp_kernel's factors)
   // CLIP: the launch covers the box `clip` only — the bulk of a grid whose shell (CPML slabs + a two-cell collar, the boundary
   // planes of a z-slab rank) is advanced by single steps beside it.  Tile rows and chunks start at the box's origin, nothing is
   // stored outside it, and the seam scratch is written for every row / plane this workgroup computes (the seam kernel
   // differentiates the row and plane below the box's first ones, which no workgroup owns).
-  constexpr bool CLIP = (OPT & 16) != 0;
-  constexpr bool REP = (OPT & 8192) != 0;  // the seam columns of the read set come from the compact repair array (deferred seam repair, above)
+  constexpr bool CLIP = (OPT & kF2Clip) != 0;
+  constexpr bool REP = (OPT & kF2Rep) != 0;  // the seam columns of the read set come from the compact repair array (deferred seam repair, above)
   static_assert(!REP || (!CLIP && !PF && !EZL && !DISP && !SRC), "deferred seam repair: plain, materials and absorber sweeps of the whole grid");
   // periodic x (clipped launches only; periodic y / z faces are part of the shell: the box stays two cells clear of them): the
   // first lane of a row takes column nx - 1 as its x-halo column, the last one column 0 as its right neighbour — step one is
@@ -1131,16 +1130,16 @@ template <int LB, int OPT>
 __device__ __forceinline__ void fused2_tile_by_class(const GridP& g, const FieldP& a, const FieldP& b, const StepP& s, const MatP& m,
                                                      int zchunk, int nbx, int nby, int nbz, const InjP& inj, float* __restrict__ seam,
                                                      const DampT& dmp, const ClipP& clip, int t, const DispP& dp, const SrcP& sr, const TileClassP& tcl) {
-  if constexpr ((OPT & 2) != 0) {
+  if constexpr ((OPT & kF2Mat) != 0) {
     if (tcl.cls) {
       const int cl = tcl.cls[t] & 3;
       if (cl == 0) {
-        fused2_step_tile<LB, (OPT & ~(2 | 32))>(g, a, b, s, m, zchunk, nbx, nby, nbz, inj, seam, dmp, clip, t, dp, sr);
+        fused2_step_tile<LB, (OPT & ~(kF2Mat | kF2Disp))>(g, a, b, s, m, zchunk, nbx, nby, nbz, inj, seam, dmp, clip, t, dp, sr);
         return;
       }
-      if constexpr ((OPT & 32) != 0) {       // (a tile without dispersive cells in a launch that carries them: the materials sweep)
+      if constexpr ((OPT & kF2Disp) != 0) {       // (a tile without dispersive cells in a launch that carries them: the materials sweep)
         if (cl == 1) {
-          fused2_step_tile<LB, (OPT & ~32)>(g, a, b, s, m, zchunk, nbx, nby, nbz, inj, seam, dmp, clip, t, dp, sr);
+          fused2_step_tile<LB, (OPT & ~kF2Disp)>(g, a, b, s, m, zchunk, nbx, nby, nbz, inj, seam, dmp, clip, t, dp, sr);
           return;
         }
       }
@@ -1170,10 +1169,10 @@ __global__ __launch_bounds__(LB, (LB == 512 ? 4 : 1)) void fused2_step_kernel(Gr
   // (bit 2 of a tile's class, launches that add paged source terms: a row segment of the tile holds a source node — the others run
   //  the instantiation without those lines: the mode plane of BASELINE config 3 crosses 1 tile row in 64, and the lines cost 8 %)
   // (every tile body of this kernel shares the LDS the launcher sized from the kernel's own OPT word: fused2_xch_arrays)
-  constexpr int OPTK = OPT | (fused2_exj(LB, OPT) ? 0 : 4096);
-  if constexpr ((OPT & 64) != 0) {
+  constexpr int OPTK = OPT | (fused2_exj(LB, OPT) ? 0 : kF2NoExj);
+  if constexpr ((OPT & kF2Src) != 0) {
     if (tcl.cls && !(tcl.cls[t] & 4)) {
-      fused2_tile_by_class<LB, (OPTK & ~64)>(g, a, b, s, m, zchunk, nbx, nby, nbz, inj, seam, dmp, clip, t, dp, sr, tcl);
+      fused2_tile_by_class<LB, (OPTK & ~kF2Src)>(g, a, b, s, m, zchunk, nbx, nby, nbz, inj, seam, dmp, clip, t, dp, sr, tcl);
       return;
     }
   }

@@ -1,13 +1,7 @@
 // Translation unit of shell2_step_kernel (fdtd_shell2.hpp): two time steps per sweep with the CPML recursions carried through
 // both — the shell launches of a step pair on a CPML-walled grid (fdtd_capi.hip).  Own unit, built like fdtd_fused2.hip
 // (-fno-slp-vectorize): it compiles beside the others.
-#include <hip/hip_runtime.h>
-#undef __global__
-#if defined(__HIPCC__)
-#define __global__ static __attribute__((global))
-#else
-#define __global__ static
-#endif
+#include "fdtd_static_kernels.hpp"
 #include "fdtd_shell2.hpp"
 
 namespace fdtd {

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(512, (AXES == 7 ? 2 : 3)) void shell2_step_kernel(G
           }
         }
       }
-      // dispersive cells inside the shell (round 6, as fused2_step_kernel's OPT bit 5): E^{n+1} <- E^{n+1} - cc S(Q^n) from the paged
+      // dispersive cells inside the shell (round 6, as fused2_step_kernel's kF2Disp): E^{n+1} <- E^{n+1} - cc S(Q^n) from the paged
       // memory terms, last of all; the lane that owns the cells leaves E^{n+1} for ade2_kernel
       if (box_disp && act && in_z) {
         const int ds = dp.dseg[((long long)k * g.ny + j) * ((g.nx + 255) >> 8) + (i0 >> 8)];
