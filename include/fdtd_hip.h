@@ -371,6 +371,21 @@ int fdtd_set_option(FdtdSolver* h, int key, int value);
 int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out);
 int fdtd_reset(FdtdSolver* h);      /* zero fields, auxiliaries, monitors and the step counter */
 
+/* Which instantiations of the two-step sweep ran.  fused2_step_kernel<LB, OPT> exists once per listed (LB, OPT) pair (launch bound in
+ * threads: 512 / 768 / 1024; OPT: the feature word of tidy3d_amd/csrc/fdtd_fused2.hpp — 1 non-temporal stores, 2 materials, 4 monitor
+ * table, 8 absorber layers, 16 clipped to the bulk of a shell pair, 32 dispersive cells, 64 paged source terms, bits 8 - 11 a what-if
+ * variant, 8192 deferred seam repair), and a launch runs exactly one of them with W waves (rows) per workgroup.  One int64 per entry:
+ * bits 0 - 31 OPT, bits 32 - 47 LB, bits 48 - 55 W. */
+#define FDTD_SWEEP_WORD(lb, opt, w) (((int64_t)(w) << 48) | ((int64_t)(lb) << 32) | (int64_t)(opt))
+#define FDTD_SWEEP_WORD_OPT(word) ((int)((word) & 0xffffffff))
+#define FDTD_SWEEP_WORD_LB(word) ((int)(((word) >> 32) & 0xffff))
+#define FDTD_SWEEP_WORD_W(word) ((int)(((word) >> 48) & 0xff))
+/* The distinct (LB, OPT, W) this handle has launched since fdtd_create or the last fdtd_reset, in the order of their first launch: returns
+ * their number (negative: error) and fills min(number, cap) entries of `out`.  Host bookkeeping only; like FdtdSeamStats, outside FdtdStats. */
+int fdtd_get_sweep_words(FdtdSolver* h, int64_t* out, int cap);
+/* Every instantiation the library holds, with W = 0: returns their number and fills min(number, cap) entries.  Needs no handle and no device. */
+int fdtd_sweep_table(int64_t* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,20 @@ def test_header_and_binding_agree():
     assert set(_declared()) == set(L.SYMBOLS)
 
 
+def test_sweep_word_getters_are_declared_and_bound():
+    assert {"fdtd_get_sweep_words", "fdtd_sweep_table"} <= set(_declared()) & set(L.SYMBOLS)
+
+
+def test_sweep_table_needs_no_handle(emu_lib):
+    n = emu_lib.dll.fdtd_sweep_table(None, 0)
+    table = emu_lib.sweep_table()
+    assert n == len(table) == len(set(table)) > 0
+    assert all(lb in (512, 768, 1024) for lb, _ in table)
+    buf = (ctypes.c_int64 * 3)()
+    assert emu_lib.dll.fdtd_sweep_table(buf, 3) == n and [L.unpack_sweep_word(buf[i])[:2] for i in range(3)] == table[:3]
+    assert emu_lib.dll.fdtd_sweep_table(None, 3) < 0 and emu_lib.dll.fdtd_get_sweep_words(None, buf, 3) < 0
+
+
 def test_product_library_exports_every_symbol():
     from tidy3d_amd import build
     path = build.build()                      # hipcc cross-compiles for gfx950 without a GPU

@@ -315,6 +315,7 @@ struct FdtdSolver {
   hipEvent_t ev_rec = nullptr;        // z-slab ranks: a monitor record on the main stream done (the comm stream's next boundary work waits for it)
   long long seam_deferred_pairs = 0, seam_flushes = 0;      // (of the current fdtd_run: FdtdSeamStats)
   double seam_flush_ms = 0.0;
+  std::vector<int64_t> sweep_words;   // distinct (LB, OPT, W) of the two-step sweeps launched since fdtd_create / fdtd_reset (fdtd_get_sweep_words)
   float* seam_buf = nullptr;          // intermediate values on the seams between x tiles, and behind them the compact repair array (deferred seam repair)
   int seam_defer = -1;                // FDTD_OPT_SEAM_DEFER: -1 / 1 = plain sixteen-wave pairs followed by a plain pair leave their repaired seam values in the compact array, 0 = never, 2 = testing aid: at every workgroup size
   bool no_jlo = false;                // $FDTD_NO_JLO at fdtd_create (a debugging aid): no box of a shell pair starts its tile rows on the y-min wall
@@ -1332,6 +1333,10 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
                                                         TileClassP{split ? tc->dev : nullptr}, dp, sr_used});
   time_end(h, st);
   if (!launched) return no_sweep();       // (a unit's case labels and fused2_instantiated expand the same lists)
+  {
+    const int64_t word = FDTD_SWEEP_WORD(fused2_lb(W, opt), opt, W);
+    if (std::find(h->sweep_words.begin(), h->sweep_words.end(), word) == h->sweep_words.end()) h->sweep_words.push_back(word);
+  }
   if (n_seams > 0 && !(rep_capable && (h->whatif == 16 || h->whatif == 17))) {
     time_begin(h, 4, st);
     launch_seams(st, g, h->f2, sp, mp, h->seam_buf, n_seams, dmp, box, inj, sr, (defer || (h->whatif == 18 && rep_capable)) ? rep_arr : nullptr);
@@ -3442,6 +3447,7 @@ int fdtd_reset(FdtdSolver* h) {
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->seam_pending = false;
+  h->sweep_words.clear();
   for (int c = 0; c < 6; ++c) HIPCHK(h, hipMemset(h->fbase[c], 0, h->field_bytes));
   for (int c = 0; c < 6; ++c) if (h->fbase2[c]) HIPCHK(h, hipMemset(h->fbase2[c], 0, h->field_bytes));
   for (int c = 0; c < 6; ++c) if (h->fbase3[c]) HIPCHK(h, hipMemset(h->fbase3[c], 0, h->field_bytes));
@@ -4955,6 +4961,25 @@ int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out) {
   out->reserved = 0;
   out->seam_flush_ms = h->seam_flush_ms;
   return 0;
+}
+
+int fdtd_get_sweep_words(FdtdSolver* h, int64_t* out, int cap) {
+  if (!h || (cap > 0 && !out)) return -1;
+  const int n = (int)h->sweep_words.size();
+  for (int i = 0; i < n && i < cap; ++i) out[i] = h->sweep_words[i];
+  return n;
+}
+
+int fdtd_sweep_table(int64_t* out, int cap) {
+  if (cap > 0 && !out) return -1;
+  static const int64_t table[] = {
+#define FDTD_F2_X(LBV, OV) FDTD_SWEEP_WORD(LBV, OV, 0),
+      FDTD_F2_LIST_ALL(FDTD_F2_X)
+#undef FDTD_F2_X
+  };
+  const int n = (int)(sizeof(table) / sizeof(table[0]));
+  for (int i = 0; i < n && i < cap; ++i) out[i] = table[i];
+  return n;
 }
 
 }  // extern "C"

@@ -670,6 +670,14 @@ class HipEngine:
         self._chk(self.lib.dll.fdtd_get_seam_stats(self.handle, C.byref(st)), "fdtd_get_seam_stats")
         return st
 
+    def sweep_words(self):
+        """The distinct (LB, OPT, W) of the two-step sweeps this engine has launched since it was created or reset
+        (``fdtd_get_sweep_words``): launch bound, OPT word (csrc/fdtd_fused2.hpp) and waves per workgroup, in order of first launch."""
+        n = self._chk(self.lib.dll.fdtd_get_sweep_words(self.handle, None, 0), "fdtd_get_sweep_words")
+        buf = (C.c_int64 * max(n, 1))()
+        self._chk(self.lib.dll.fdtd_get_sweep_words(self.handle, buf, n), "fdtd_get_sweep_words")
+        return [L.unpack_sweep_word(buf[i]) for i in range(n)]
+
     def set_option(self, key: int, value: int):
         self._chk(self.lib.dll.fdtd_set_option(self.handle, key, value), "fdtd_set_option")
 

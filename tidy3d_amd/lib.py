@@ -39,6 +39,7 @@ SYMBOLS = (
     "fdtd_set_field", "fdtd_get_field", "fdtd_set_shutoff", "fdtd_comm_unique_id",
     "fdtd_comm_init", "fdtd_run", "fdtd_run_bloch", "fdtd_get_stats", "fdtd_reset", "fdtd_set_option",
     "fdtd_far_field", "fdtd_set_mirror_plus", "fdtd_add_aniso", "fdtd_add_aniso_bloch", "fdtd_get_seam_stats",
+    "fdtd_get_sweep_words", "fdtd_sweep_table",
 )
 
 BC_PEC, BC_PMC, BC_PERIODIC, BC_NEIGHBOR = 0, 1, 2, 3
@@ -85,6 +86,12 @@ class FdtdSeamStats(C.Structure):
                 ("reserved", C.c_int32), ("seam_flush_ms", C.c_double)]
 
 
+def unpack_sweep_word(word: int):
+    """(LB, OPT, W) of one entry of ``fdtd_get_sweep_words`` / ``fdtd_sweep_table`` (include/fdtd_hip.h, FDTD_SWEEP_WORD)."""
+    word = int(word)
+    return (word >> 32) & 0xffff, word & 0xffffffff, (word >> 48) & 0xff
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_int64, C.c_double, C.c_double, C.c_void_p)
 
 
@@ -107,6 +114,8 @@ class FdtdLib:
         d.fdtd_destroy.argtypes = [vp]
         d.fdtd_destroy.restype = None
         d.fdtd_get_seam_stats.argtypes = [vp, C.POINTER(FdtdSeamStats)]
+        d.fdtd_get_sweep_words.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
+        d.fdtd_sweep_table.argtypes = [C.POINTER(C.c_int64), C.c_int]
         d.fdtd_set_steps.argtypes = [vp, C.c_int, vp, vp, C.c_int]
         d.fdtd_set_media.argtypes = [vp, vp, vp, C.c_int]
         d.fdtd_set_material.argtypes = [vp, vp, C.c_size_t]
@@ -149,6 +158,13 @@ class FdtdLib:
                                            float(np.real(k)), float(np.imag(k)), int(r_u.size), p(r_u), p(r_v), p(r_w), p(out)),
                    None, "fdtd_far_field")
         return out
+
+    def sweep_table(self):
+        """Every instantiation (LB, OPT) of the two-step sweep this library holds (``fdtd_sweep_table``), in list order."""
+        n = self.check(self.dll.fdtd_sweep_table(None, 0), None, "fdtd_sweep_table")
+        buf = (C.c_int64 * max(n, 1))()
+        self.check(self.dll.fdtd_sweep_table(buf, n), None, "fdtd_sweep_table")
+        return [unpack_sweep_word(buf[i])[:2] for i in range(n)]
 
     def error(self, handle) -> str:
         msg = self.dll.fdtd_last_error(handle)
