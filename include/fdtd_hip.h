@@ -36,7 +36,7 @@ extern "C" {
 typedef struct FdtdSolver FdtdSolver;
 
 enum { FDTD_BC_PEC = 0, FDTD_BC_PMC = 1, FDTD_BC_PERIODIC = 2, FDTD_BC_NEIGHBOR = 3 };
-enum { FDTD_MON_TIME = 0, FDTD_MON_DFT = 1 };
+enum { FDTD_MON_TIME = 0, FDTD_MON_DFT = 1, FDTD_MON_FLUX_TIME = 2 /* added by fdtd_add_flux_time_monitor only */ };
 /* kernel variants of the two main update kernels (A/B-tested by bench.py --variant) */
 /* AUTO = FUSED on one GPU (single-sweep E+H update, 48 B/cell-step), two-pass ZMARCH otherwise */
 enum { FDTD_VARIANT_AUTO = 0, FDTD_VARIANT_SIMPLE = 1, FDTD_VARIANT_ZMARCH = 2, FDTD_VARIANT_FUSED = 3 };
@@ -249,8 +249,29 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
                      const int32_t lo[3], const int32_t hi[3],
                      int64_t n_rec, const int64_t* steps,
                      int nf, const float* phase_e, const float* phase_h);
-/* time: float [n_rec][n_comps][bz][by][bx];  dft: complex64 [nf][n_comps][bz][by][bx] */
+/* FDTD_MON_FLUX_TIME (ref monitor.py FluxTimeMonitor, one planar surface): the flux through a plane normal to `axis` at every step of
+ * `steps`, reduced on the device — the result is float[n_rec], and the device holds a ring of records instead of n_rec of them.
+ * The monitor records like the FDTD_MON_TIME monitor of the box [lo, hi) with the components E_t1, E_t2, H_t1, H_t2, t1 = axis + 1,
+ * t2 = axis + 2 (cyclic), in every schedule, into a staging buffer of R = staging_bytes / (record bytes) records (at least 2, at most
+ * n_rec; staging_bytes <= 0: 32 MiB), slot = record index mod R; when the ring is full, at the end of fdtd_run and in front of
+ * fdtd_get_monitor one launch turns every complete record of every such monitor into
+ *     flux[rec] = sign * sum over nodes (E_t1 H_t2 - E_t2 H_t1) * weight(node)        (fp32, fixed summation order, no atomics)
+ * on the n_nodes[0] x n_nodes[1] x n_nodes[2] primal nodes of the surface (n_nodes[axis] == 1).  Each component is colocated to a node by
+ * separable linear interpolation: tap_index / tap_weight hold, axis after axis (x, y, z), [4 components][n_nodes[a]][2] taps — the index
+ * into the box along that axis and its weight; a tap of weight 0 is not read, every other index must lie inside the box.
+ * weight(node) = wu[i_u] * wv[i_v], u < v the two tangential axes (wu[n_nodes[u]], wv[n_nodes[v]]).
+ * Added between runs, the steps already done are skipped (their entries stay 0 until fdtd_reset, after which it records them all).
+ * Refused on z-slab handles (FDTD_BC_NEIGHBOR faces, fdtd_comm_init); fdtd_run_bloch refuses handles that carry one.
+ * Returns the monitor id (>= 0) or <0. */
+int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_t lo[3], const int32_t hi[3],
+                               int64_t n_rec, const int64_t* steps, const int32_t n_nodes[3],
+                               const int32_t* tap_index, const float* tap_weight,
+                               const float* wu, const float* wv, int64_t staging_bytes);
+/* time: float [n_rec][n_comps][bz][by][bx];  dft: complex64 [nf][n_comps][bz][by][bx];  flux-time: float [n_rec] */
 int fdtd_get_monitor(FdtdSolver* h, int monitor_id, void* host, size_t bytes);
+/* device memory a monitor holds, as allocated: out[0] = all of it, out[1] = its record buffer (flux-time: the staging ring),
+ * out[2] = the reduced series of a flux-time monitor (else 0), out[3] = tables (phase tables; taps, weights, per-tile partial sums) */
+int fdtd_get_monitor_bytes(FdtdSolver* h, int monitor_id, int64_t out[4]);
 
 /* whole-volume field access [nz][ny][nx] (tests, benchmarks, checkpointing); the reference exposes
  * fields only through monitors (ref monitor.py:363), so this has no cloud counterpart */

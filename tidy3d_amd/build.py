@@ -15,7 +15,7 @@ SOURCES = [os.path.join(CSRC, "fdtd_capi.hip"), os.path.join(CSRC, "fdtd_fused2.
 SOURCE_FLAGS = {"fdtd_fused2.hip": ["-fno-slp-vectorize"], "fdtd_fused2c.hip": ["-fno-slp-vectorize"], "fdtd_fused2d.hip": ["-fno-slp-vectorize"], "fdtd_fused2w.hip": ["-fno-slp-vectorize"], "fdtd_fused2s.hip": ["-fno-slp-vectorize"],
                 "fdtd_shell2.hip": ["-fno-slp-vectorize"]}
 DEPS = SOURCES + [os.path.join(CSRC, "fdtd_kernels.hpp"), os.path.join(CSRC, "fdtd_kernels2.hpp"),
-                  os.path.join(CSRC, "fdtd_fused2.hpp"), os.path.join(CSRC, "fdtd_static_kernels.hpp"), os.path.join(CSRC, "fdtd_shell2.hpp"), os.path.join(CSRC, "fdtd_shell2_host.hpp"), os.path.join(CSRC, "fdtd_strip.hpp"), os.path.join(CSRC, "fdtd_aniso.hpp"),
+                  os.path.join(CSRC, "fdtd_fused2.hpp"), os.path.join(CSRC, "fdtd_static_kernels.hpp"), os.path.join(CSRC, "fdtd_shell2.hpp"), os.path.join(CSRC, "fdtd_shell2_host.hpp"), os.path.join(CSRC, "fdtd_strip.hpp"), os.path.join(CSRC, "fdtd_aniso.hpp"), os.path.join(CSRC, "fdtd_flux_time.hpp"),
                   os.path.join(HERE, "..", "include", "fdtd_hip.h"), os.path.abspath(__file__)]
 
 

@@ -22,6 +22,7 @@
 #include "fdtd_strip.hpp"
 #include "fdtd_shell2_host.hpp"
 #include "fdtd_aniso.hpp"
+#include "fdtd_flux_time.hpp"
 
 using namespace fdtd;
 
@@ -132,6 +133,15 @@ struct Monitor {
   void* data = nullptr;
   size_t data_bytes = 0;
   long long cells = 0;
+  size_t dev_bytes = 0;            // device memory the monitor holds, tables included (fdtd_get_monitor_bytes)
+  // FDTD_MON_FLUX_TIME: kind stays FDTD_MON_TIME — every schedule treats the monitor as the time monitor of its box — and `data` is
+  // a ring of `ring` records (slot = record index mod ring) that flux_reduce turns into result[n_rec] (fdtd_flux_time.hpp)
+  bool flux = false;
+  size_t ring = 0;                 // records the staging buffer holds (0: one slot per recorded step)
+  size_t reduced = 0;              // records [0, reduced) are in `result`, their slots zero again
+  FluxMonP fp{};                   // addresses and shapes of its tables
+  size_t aux_bytes = 0;            // tap / weight tables and per-tile partial sums
+  long long slot(size_t rec) const { return (long long)(ring ? rec % ring : rec); }
 };
 
 // node table of one kind of step pair of the two-step sweep: the E-side source nodes and the nodes small time monitors
@@ -1764,6 +1774,38 @@ int shell2_why_not(const FdtdSolver* h, ShellGeom* G) {
   return 0;
 }
 
+// Flux-time monitors (fdtd_flux_time.hpp): every complete record not reduced yet — records [reduced, next) of each ring — becomes
+// one value of its monitor's series, all monitors in one launch (kFluxMaxJobs per launch), and its slot is zeroed again (the H
+// half-samples are accumulated into a record).  Issued on the stream the records were written on, behind them: no other edge.
+void flux_reduce(FdtdSolver* h, hipStream_t st) {
+  size_t q = 0;
+  while (q < h->mons.size()) {
+    FluxLaunchP L{};
+    int tiles = 0, cnt = 0;
+    for (; q < h->mons.size() && L.n < kFluxMaxJobs; ++q) {
+      Monitor& m = h->mons[q];
+      if (!m.flux || m.reduced >= m.next) continue;
+      FluxMonP& p = L.m[L.n++];
+      p = m.fp;
+      p.r0 = (long long)m.reduced;
+      p.cnt = (int)(m.next - m.reduced);
+      tiles = std::max(tiles, p.tiles); cnt = std::max(cnt, p.cnt);
+    }
+    if (!L.n) break;
+    dbg_sync(h);
+    hipLaunchKernelGGL(flux_time_reduce_kernel, dim3(tiles, cnt, L.n), dim3(256), 0, st, L);
+    hipLaunchKernelGGL(flux_time_final_kernel, dim3((cnt + 255) / 256, L.n), dim3(256), 0, st, L);
+  }
+  for (Monitor& m : h->mons) {
+    if (!m.flux || m.reduced >= m.next) continue;
+    const size_t rec_bytes = 4 * (size_t)m.cells * sizeof(float);
+    const size_t s0 = m.reduced % m.ring, cnt = m.next - m.reduced, first = std::min(cnt, m.ring - s0);
+    hipMemsetAsync(reinterpret_cast<char*>(m.data) + s0 * rec_bytes, 0, first * rec_bytes, st);
+    if (cnt > first) hipMemsetAsync(m.data, 0, (cnt - first) * rec_bytes, st);
+    m.reduced = m.next;
+  }
+}
+
 // H-side source terms of step n act on H^{n-1/2} in place in FRONT of a pair's sweep: then the small time monitors of the pair take
 // E^n and their first H half-sample in front of those (record_monitors at the top of the step) and pair_record adds the rest.
 // Round 6: the H-side corrections of a TFSF box count too — since such boxes inject inside pairs (paged source terms) a probe on
@@ -1797,6 +1839,14 @@ void pair_record(FdtdSolver* h, const F2Table* tb, long long n, hipStream_t st) 
   PairRecP r{};
   r.pre_done = h_terms_in_front(h);            // (then fdtd_run has not skipped them at the top of the step)
   long long max_cells = 0;
+  for (size_t q = 0; q < tb->mons.size(); ++q) {      // flux-time rings: room for the (at most two) records of this pair
+    const Monitor& m = h->mons[(size_t)tb->mons[q]];
+    if (!m.ring) continue;
+    size_t last = m.next;
+    if (last < m.steps.size() && m.steps[last] == n) ++last;
+    if (last < m.steps.size() && m.steps[last] == n + 1) ++last;
+    if (last > m.next && last - 1 - m.reduced >= m.ring) { flux_reduce(h, st); break; }
+  }
   for (size_t q = 0; q < tb->mons.size(); ++q) {
     Monitor& m = h->mons[(size_t)tb->mons[q]];
     const long long rs = (long long)m.comps.size() * m.cells;
@@ -1804,8 +1854,8 @@ void pair_record(FdtdSolver* h, const F2Table* tb, long long n, hipStream_t st) 
     r.nc[q] = (int)m.comps.size();
     for (size_t ic = 0; ic < m.comps.size(); ++ic) r.comp[q][ic] = m.comps[ic];
     r.cap_off[q] = tb->cap_off[q];
-    if (m.next < m.steps.size() && m.steps[m.next] == n) { r.out_n[q] = reinterpret_cast<float*>(m.data) + (long long)m.next * rs; m.next++; }
-    if (m.next < m.steps.size() && m.steps[m.next] == n + 1) { r.out_m[q] = reinterpret_cast<float*>(m.data) + (long long)m.next * rs; m.next++; }
+    if (m.next < m.steps.size() && m.steps[m.next] == n) { r.out_n[q] = reinterpret_cast<float*>(m.data) + m.slot(m.next) * rs; m.next++; }
+    if (m.next < m.steps.size() && m.steps[m.next] == n + 1) { r.out_m[q] = reinterpret_cast<float*>(m.data) + m.slot(m.next) * rs; m.next++; }
     max_cells = std::max(max_cells, m.cells);
   }
   r.n_mon = (int)tb->mons.size();
@@ -2797,7 +2847,8 @@ void record_monitors(FdtdSolver* h, long long n, bool post, hipStream_t st, cons
     if (r.n > 0 && m.cells > 0) {
       const dim3 grid(nblk(m.cells), r.n);
       if (m.kind == FDTD_MON_TIME) {
-        float* out = reinterpret_cast<float*>(m.data) + rec * nc * m.cells;
+        if (m.ring && (size_t)rec - m.reduced >= m.ring) flux_reduce(h, st);      // (a full flux-time ring: its complete records first)
+        float* out = reinterpret_cast<float*>(m.data) + m.slot((size_t)rec) * nc * m.cells;
         hipLaunchKernelGGL(time_record_multi_kernel, grid, dim3(256), 0, st, r, h->g, m.box, out, (long long)m.cells);
       } else {
         const long long fstride = (long long)nc * m.cells;
@@ -3330,6 +3381,7 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
                      const int32_t hi[3], int64_t n_rec, const int64_t* steps, int nf, const float* phase_e,
                      const float* phase_h) {
   if (!h) return -1;
+  if (kind == FDTD_MON_FLUX_TIME) return fail(h, "fdtd_add_monitor: FDTD_MON_FLUX_TIME monitors are added by fdtd_add_flux_time_monitor");
   if (kind != FDTD_MON_TIME && kind != FDTD_MON_DFT) return fail(h, "fdtd_add_monitor: bad kind %d", kind);
   const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
   for (int a = 0; a < 3; ++a)
@@ -3337,6 +3389,7 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
   if (n_comps < 1 || n_comps > 6) return fail(h, "fdtd_add_monitor: n_comps must be 1..6");
   if (kind == FDTD_MON_DFT && nf < 1) return fail(h, "fdtd_add_monitor: a DFT monitor needs frequencies");
   HIPCHK(h, hipSetDevice(h->cfg.device));
+  const int64_t bytes_before = h->stats.device_bytes;
   Monitor m;
   m.kind = kind;
   m.comps.assign(comps, comps + n_comps);
@@ -3362,14 +3415,110 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
         dev_upload(h, &m.phase_h, reinterpret_cast<const float2*>(phase_h), (size_t)n_rec * nf))
       return -1;
   }
+  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
   h->mons.push_back(m);
   return (int)h->mons.size() - 1;
+}
+
+int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_t lo[3], const int32_t hi[3], int64_t n_rec,
+                               const int64_t* steps, const int32_t n_nodes[3], const int32_t* tap_index, const float* tap_weight,
+                               const float* wu, const float* wv, int64_t staging_bytes) {
+  if (!h) return -1;
+  if (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR)
+    return fail(h, "fdtd_add_flux_time_monitor: not available on z-slab handles (the surface would be cut between ranks)");
+  if (axis < 0 || axis > 2) return fail(h, "fdtd_add_flux_time_monitor: bad axis %d", axis);
+  if (!lo || !hi || !n_nodes || !tap_index || !tap_weight || !wu || !wv || n_rec < 0 || (n_rec && !steps))
+    return fail(h, "fdtd_add_flux_time_monitor: bad argument");
+  const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
+  for (int a = 0; a < 3; ++a)
+    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "fdtd_add_flux_time_monitor: box [%d,%d) outside axis %d of %d cells", lo[a], hi[a], a, N[a]);
+  const int u = axis == 0 ? 1 : 0;                             // the lower tangential axis (wu), the other one takes wv
+  for (int a = 0; a < 3; ++a)
+    if (n_nodes[a] < 1 || (a == axis && n_nodes[a] != 1)) return fail(h, "fdtd_add_flux_time_monitor: %d nodes along axis %d", n_nodes[a], a);
+  // every tap that is read (weight != 0) must lie inside the box
+  const int ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+  size_t tap_off[3], n_taps = 0;
+  for (int a = 0; a < 3; ++a) {
+    tap_off[a] = n_taps;
+    for (size_t t = 0; t < (size_t)8 * n_nodes[a]; ++t) {
+      const float w = tap_weight[n_taps + t];
+      if (!(w == w) || (w != 0.0f && (tap_index[n_taps + t] < 0 || tap_index[n_taps + t] >= ext[a])))
+        return fail(h, "fdtd_add_flux_time_monitor: tap %zu of axis %d (index %d, weight %g) outside the box of %d cells", t, a, tap_index[n_taps + t], (double)w, ext[a]);
+    }
+    n_taps += (size_t)8 * n_nodes[a];
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  const int64_t bytes_before = h->stats.device_bytes;
+  Monitor m;
+  m.kind = FDTD_MON_TIME;
+  m.flux = true;
+  const int t1 = (axis + 1) % 3, t2 = (axis + 2) % 3;
+  m.comps = {t1, t2, 3 + t1, 3 + t2};
+  m.box.lo0 = lo[0]; m.box.lo1 = lo[1]; m.box.lo2 = lo[2];
+  m.box.nx = ext[0]; m.box.ny = ext[1]; m.box.nz = ext[2];
+  m.cells = (long long)ext[0] * ext[1] * ext[2];
+  m.steps.assign(steps, steps + n_rec);
+  for (size_t i = 1; i < m.steps.size(); ++i)
+    if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_flux_time_monitor: steps must be strictly increasing");
+  // added between runs: the steps already done are skipped — their entries of the series stay zero — until fdtd_reset
+  while (m.next < m.steps.size() && m.steps[m.next] < h->step) ++m.next;
+  m.reduced = m.next;
+  // (like fdtd_add_monitor: what a failure below has allocated already stays with the handle until fdtd_destroy)
+  // the ring: as many records as the budget holds, at least two (a step pair records two steps), no more than there are
+  const size_t rec_bytes = 4 * (size_t)m.cells * sizeof(float);
+  const size_t budget = staging_bytes > 0 ? (size_t)staging_bytes : ((size_t)32 << 20);
+  m.ring = std::max<size_t>(2, std::min<size_t>(std::min<size_t>(budget / rec_bytes, (size_t)kFluxMaxRing), std::max<size_t>((size_t)n_rec, 2)));
+  m.data_bytes = m.ring * rec_bytes;
+  float *stage = nullptr, *result = nullptr, *partial = nullptr;
+  if (dev_alloc(h, &stage, m.ring * 4 * (size_t)m.cells)) return -1;
+  m.data = stage;
+  if (dev_alloc(h, &result, (size_t)n_rec)) return -1;
+  const int64_t bytes_aux = h->stats.device_bytes;
+  FluxMonP& p = m.fp;
+  const long long nodes = (long long)n_nodes[0] * n_nodes[1] * n_nodes[2];
+  p.tiles = (int)((nodes + kFluxTile - 1) / kFluxTile);
+  if (dev_alloc(h, &partial, m.ring * (size_t)p.tiles)) return -1;
+  const float one = 1.0f;
+  for (int a = 0; a < 3; ++a) {
+    int* di = nullptr; float *dw = nullptr, *dwi = nullptr;
+    if (dev_upload(h, &di, (const int*)(tap_index + tap_off[a]), (size_t)8 * n_nodes[a]) ||
+        dev_upload(h, &dw, tap_weight + tap_off[a], (size_t)8 * n_nodes[a]) ||
+        dev_upload(h, &dwi, a == axis ? &one : (a == u ? wu : wv), (size_t)n_nodes[a])) return -1;
+    p.idx[a] = di; p.w[a] = dw; p.wi[a] = dwi;
+    p.nt[a] = n_nodes[a]; p.b[a] = ext[a];
+  }
+  p.stage = stage; p.partial = partial; p.result = result;
+  p.ring = (int)m.ring;
+  p.sign = sign;
+  m.aux_bytes = (size_t)(h->stats.device_bytes - bytes_aux);
+  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
+  h->mons.push_back(m);
+  return (int)h->mons.size() - 1;
+}
+
+int fdtd_get_monitor_bytes(FdtdSolver* h, int id, int64_t out[4]) {
+  if (!h) return -1;
+  if (id < 0 || id >= (int)h->mons.size() || !out) return fail(h, "fdtd_get_monitor_bytes: bad id %d", id);
+  const Monitor& m = h->mons[id];
+  out[0] = (int64_t)m.dev_bytes;
+  out[1] = (int64_t)m.data_bytes;
+  out[2] = m.flux ? (int64_t)(m.dev_bytes - m.data_bytes - m.aux_bytes) : 0;
+  out[3] = m.flux ? (int64_t)m.aux_bytes : (int64_t)(m.dev_bytes - m.data_bytes);
+  return 0;
 }
 
 int fdtd_get_monitor(FdtdSolver* h, int id, void* host, size_t bytes) {
   if (!h) return -1;
   if (id < 0 || id >= (int)h->mons.size()) return fail(h, "fdtd_get_monitor: bad id %d", id);
   Monitor& m = h->mons[id];
+  if (m.flux) {                        // the reduced series
+    if (bytes != m.steps.size() * sizeof(float)) return fail(h, "fdtd_get_monitor: expected %zu bytes, got %zu", m.steps.size() * sizeof(float), bytes);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    flux_reduce(h, h->stream);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (bytes) HIPCHK(h, hipMemcpy(host, m.fp.result, bytes, hipMemcpyDeviceToHost));
+    return 0;
+  }
   if (bytes != m.data_bytes) return fail(h, "fdtd_get_monitor: expected %zu bytes, got %zu", m.data_bytes, bytes);
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3432,6 +3581,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   HIPCHK(h, hipSetDevice(h->cfg.device));
   ncclUniqueId u;
   std::memcpy(&u, id, 128);
+  for (const Monitor& m : h->mons) if (m.flux) return fail(h, "fdtd_comm_init: flux-time monitors are not available on z-slab handles");
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)
@@ -3472,7 +3622,11 @@ int fdtd_reset(FdtdSolver* h) {
     HIPCHK(h, hipMemset(t.e1, 0, ((size_t)t.n_aux + 1) * 4));
     HIPCHK(h, hipMemset(t.h1, 0, (size_t)t.n_aux * 4));
   }
-  for (Monitor& m : h->mons) { HIPCHK(h, hipMemset(m.data, 0, m.data_bytes)); m.next = 0; }
+  for (Monitor& m : h->mons) {
+    HIPCHK(h, hipMemset(m.data, 0, m.data_bytes));
+    m.next = 0;
+    if (m.flux) { HIPCHK(h, hipMemset(m.fp.result, 0, std::max<size_t>(m.steps.size(), 1) * sizeof(float))); m.reduced = 0; }
+  }
   h->step = 0; h->energy_max = 0.0;
   h->stats.steps_done = 0; h->stats.diverged = 0; h->stats.stopped_early = 0; h->stats.field_decay = 0.0;      // (what a fresh handle reports until its first decay check)
   return 0;
@@ -4538,6 +4692,7 @@ struct Run {
   // joins the streams, reads the timers
   int finish() {
     flush_seams(h, st);          // (a run never returns with stale seam columns)
+    flux_reduce(h, st);          // (nor with flux-time records waiting in their rings)
     if (multi) {
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));
@@ -4632,6 +4787,7 @@ extern "C" {
 int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user) {
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (h->comm) for (const Monitor& m : h->mons) if (m.flux) return fail(h, "fdtd_run: flux-time monitors are not available on z-slab handles");
   Run r{h, n_steps, progress, user};
   if (r.setup() || r.setup_schedules() || r.setup_pairs()) return -1;
   if (r.loop()) { flush_seams(h, h->stream); return -1; }      // (an error leaves no stale seam columns either)
@@ -4647,6 +4803,8 @@ int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user
 int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double phase[3], const int n_real[3],
                    FdtdProgressFn progress, void* user) {
   if (!hr || !hi) return -1;
+  for (const FdtdSolver* hh : {hr, hi})
+    for (const Monitor& m : hh->mons) if (m.flux) return fail(hr, "fdtd_run_bloch: flux-time monitors are not available with Bloch boundaries (complex fields)");
   if (hi->comm) return fail(hr, "fdtd_run_bloch: the communicator of a z-slab belongs to the first (real-part) handle");
   // fully anisotropic bodies: the Re handle's lists (wrap codes included) drive both parts; the Im handle's carry the same rows
   const bool aniso = !hr->aniso.empty();

@@ -121,6 +121,26 @@ class DataArray:
         return f"DataArray(dims={self.dims}, shape={self.shape}, dtype={self.dtype})"
 
 
+def _interp_jw(src: np.ndarray, dst: np.ndarray):
+    """Left sample j and weight w of the right one, j + 1, for every target: the numbers ``interp_axis`` interpolates with."""
+    j = np.clip(np.searchsorted(src, dst, side="right") - 1, 0, len(src) - 2)
+    w = np.clip((dst - src[j]) / (src[j + 1] - src[j]), 0.0, 1.0)
+    return j, w
+
+
+def interp_taps(src: np.ndarray, dst: np.ndarray):
+    """``interp_axis`` as a table: (index [n_dst, 2], weight [n_dst, 2]) with
+    interp_axis(arr, src, dst)[t] == weight[t, 0] * arr[index[t, 0]] + weight[t, 1] * arr[index[t, 1]], its shortcuts included
+    (identical coordinates and one-sample sources: weight (1, 0))."""
+    src = np.asarray(src, float)
+    dst = np.asarray(dst, float)
+    if (len(src) == len(dst) and np.array_equal(src, dst)) or len(src) == 1:
+        j = np.arange(len(dst)) if len(src) > 1 else np.zeros(len(dst), dtype=np.int64)
+        return np.stack([j, j], axis=1), np.stack([np.ones(len(dst)), np.zeros(len(dst))], axis=1)
+    j, w = _interp_jw(src, dst)
+    return np.stack([j, j + 1], axis=1), np.stack([1 - w, w], axis=1)
+
+
 def interp_axis(arr: np.ndarray, src: np.ndarray, dst: np.ndarray, axis: int) -> np.ndarray:
     """Linear interpolation of ``arr`` from coordinates ``src`` to ``dst`` along ``axis``; values
     are held constant beyond the ends (the raw boxes are clipped at the domain walls)."""
@@ -130,8 +150,7 @@ def interp_axis(arr: np.ndarray, src: np.ndarray, dst: np.ndarray, axis: int) ->
         return arr
     if len(src) == 1:
         return np.repeat(arr, len(dst), axis=axis)
-    j = np.clip(np.searchsorted(src, dst, side="right") - 1, 0, len(src) - 2)
-    w = np.clip((dst - src[j]) / (src[j + 1] - src[j]), 0.0, 1.0)
+    j, w = _interp_jw(src, dst)
     a0 = np.take(arr, j, axis=axis)
     a1 = np.take(arr, j + 1, axis=axis)
     shp = [1] * arr.ndim
@@ -277,33 +296,64 @@ def _colocate_box(raw: np.ndarray, spec: SolverSpec, fp: FieldPlan, ic: int, fna
     both the colocation to the primal nodes, ref dataset.py:83-147 / CHANGELOG:467-470, and the
     snapping of zero-size dimensions to the exact plane position, ref simulation.py:1019-1026)."""
     comp = COMP_ID[fname]
-    yee = spec.yee_coords(comp)
     arr = raw[:, ic]
     for a in range(3):
-        lo = fp.lo[a]
         n = arr.shape[3 - a]
-        src = yee[a][lo:lo + n]
-        on_boundary = (a == comp % 3) == (comp >= 3)      # nodes on the grid lines along a
-        if on_boundary and lo + n == spec.shape[a] and spec.bc[a][1] != BC_PERIODIC and n > 1:
-            # the top wall is not stored: wall-tangential E / wall-normal H are zero on it
-            src = np.append(src, spec.boundaries[a][-1])
+        src, closed = _box_axis(spec, fp, comp, a, n)
+        if closed == "wall":
             pad = [(0, 0)] * arr.ndim
             pad[3 - a] = (0, 1)
             arr = np.pad(arr, pad)
-        elif lo == 0 and n == spec.shape[a] and n > 1 and spec.bc[a][0] == BC_PERIODIC and spec.bc[a][1] == BC_PERIODIC:
-            # a box that spans a whole PERIODIC axis: the samples one period away close the interpolation at both ends (the
-            # node on the plus face IS node 0; without this the last target took the value of its neighbour — 1e-3 of a flux
-            # through a unit cell, found against the symmetric half-cell run, tests/test_symmetry.py)
-            period = float(spec.boundaries[a][-1] - spec.boundaries[a][0])
+        elif closed == "periodic":
             first = np.take(arr, [0], axis=3 - a)
             last = np.take(arr, [n - 1], axis=3 - a)
             phi = 0.0 if getattr(spec, "bloch", None) is None else float(spec.bloch[a])
             if phi != 0.0:                      # Bloch axis: F(r + L) = exp(i phi) F(r)   (ref boundary.py:55-79)
                 first, last = first * np.exp(1j * phi), last * np.exp(-1j * phi)
-            src = np.concatenate([[src[-1] - period], src, [src[0] + period]])
             arr = np.concatenate([last, arr, first], axis=3 - a)
         arr = interp_axis(arr, src, fp.target[fname][a], axis=3 - a)
     return arr
+
+
+def _box_axis(spec: SolverSpec, fp: FieldPlan, comp: int, a: int, n: int):
+    """Coordinates of the samples component ``comp`` is interpolated from along axis ``a`` of a recorded box of ``n`` samples,
+    and how the box was closed: "wall" = one more sample, zero, on the top wall; "periodic" = one sample of the neighbouring
+    period in front and one behind; None = the box's own samples."""
+    lo = fp.lo[a]
+    src = spec.yee_coords(comp)[a][lo:lo + n]
+    on_boundary = (a == comp % 3) == (comp >= 3)      # nodes on the grid lines along a
+    if on_boundary and lo + n == spec.shape[a] and spec.bc[a][1] != BC_PERIODIC and n > 1:
+        # the top wall is not stored: wall-tangential E / wall-normal H are zero on it
+        return np.append(src, spec.boundaries[a][-1]), "wall"
+    if lo == 0 and n == spec.shape[a] and n > 1 and spec.bc[a][0] == BC_PERIODIC and spec.bc[a][1] == BC_PERIODIC:
+        # a box that spans a whole PERIODIC axis: the samples one period away close the interpolation at both ends (the
+        # node on the plus face IS node 0; without this the last target took the value of its neighbour — 1e-3 of a flux
+        # through a unit cell, found against the symmetric half-cell run, tests/test_symmetry.py)
+        period = float(spec.boundaries[a][-1] - spec.boundaries[a][0])
+        return np.concatenate([[src[-1] - period], src, [src[0] + period]]), "periodic"
+    return src, None
+
+
+def colocation_taps(spec: SolverSpec, fp: FieldPlan, fname: str, extents):
+    """``_colocate_box`` of real fields as tables: per axis (index int32 [n_target, 2], weight float64 [n_target, 2]) into a raw
+    box of ``extents`` = (bx, by, bz) samples — the interpolation weights ``_colocate_box`` applies, with the closing samples
+    folded in (the zero on a top wall drops out, a neighbouring period's sample is the one at the other end).  A tap of weight
+    0 carries an index inside the box.  What the device's flux reduction colocates with (csrc/fdtd_flux_time.hpp)."""
+    comp = COMP_ID[fname]
+    out = []
+    for a in range(3):
+        n = int(extents[a])
+        src, closed = _box_axis(spec, fp, comp, a, n)
+        j, w = interp_taps(src, fp.target[fname][a])
+        if closed == "wall":
+            w = np.where(j == n, 0.0, w)
+        elif closed == "periodic":
+            j = (j - 1) % n
+        j = np.where(w == 0.0, np.clip(j, 0, n - 1), j)
+        if j.min() < 0 or j.max() >= n:
+            raise DataError(f"colocation tap outside the recorded box of '{fp.spec_name}' along axis {a}")
+        out.append((j.astype(np.int32), np.asarray(w, np.float64)))
+    return out
 
 
 def _extended_subspace(coords: np.ndarray, ind_beg: int, ind_end: int, periodic: bool) -> np.ndarray:
@@ -356,19 +406,23 @@ def _diff_area(plan_box: td.Box, coords1: np.ndarray, coords2: np.ndarray, axis:
                gb1: np.ndarray, gb2: np.ndarray) -> np.ndarray:
     """Integration weights for values colocated to the grid boundaries gb1 x gb2, truncated to
     the monitor bounds (ref monitor_data.py:426-463)."""
+    return np.outer(*_diff_sizes(plan_box, axis, gb1, gb2))
+
+
+def _diff_sizes(plan_box: td.Box, axis: int, gb1: np.ndarray, gb2: np.ndarray):
+    """The two factors of ``_diff_area``: the 1-D integration weights along the two tangential axes (ascending)."""
     (lo, hi) = plan_box.bounds
     t = [a for a in range(3) if a != axis]
 
     def sizes(gb, mlo, mhi):
+        gb = np.asarray(gb, float)
         if gb.size <= 1:
             return np.array([1.0])
         c = 0.5 * (gb[1:] + gb[:-1])
         c = np.concatenate(([gb[0]], c, [gb[-1]]))
         c = np.clip(c, mlo, mhi)
         return c[1:] - c[:-1]
-    s1 = sizes(gb1, lo[t[0]], hi[t[0]])
-    s2 = sizes(gb2, lo[t[1]], hi[t[1]])
-    return np.outer(s1, s2)
+    return sizes(gb1, lo[t[0]], hi[t[0]]), sizes(gb2, lo[t[1]], hi[t[1]])
 
 
 def plane_flux(fd: _FieldLike, axis: int, mon, sign: float = 1.0, box: Optional[td.Box] = None,
@@ -557,6 +611,13 @@ def assemble(disc: Discretization, raw: Dict[str, np.ndarray], log: str = "", di
             lead_coords = disc.tmesh[plan.steps[:nk]] if is_time else np.asarray(mon.freqs, float)
             total = None
             from .discretize import flux_surfaces
+            if is_time and all(np.ndim(raw[fp.spec_name]) == 1 for fp in plan.fields):
+                # reduced on the device (MonitorSpec kind "flux_time"): one float32 series per surface; the surfaces are added here
+                series = np.zeros(nk, dtype=np.float64)
+                for fp in plan.fields:
+                    series += np.asarray(raw[fp.spec_name][:nk], dtype=np.float64)
+                out.append(FluxTimeData(monitor=mon, flux=DataArray(series.astype(np.float32), {"t": lead_coords})))
+                continue
             for isurf, (fp, (sname, box, axis, sign)) in enumerate(zip(plan.fields, flux_surfaces(mon))):
                 class _M:
                     pass

@@ -133,16 +133,22 @@ def gather_results(eng: HipEngine) -> Optional[Dict[str, np.ndarray]]:
     return out
 
 
+def slab_discretization(sim, n_steps: Optional[int] = None):
+    """The discretization of a z-slab run.  FluxTimeMonitors stay on the host path whatever their size: the device reduction
+    (MonitorSpec kind "flux_time") needs the whole surface on one GPU, and the engine refuses it on a slab."""
+    from .discretize import discretize
+    return discretize(sim, n_steps=n_steps, flux_time_device=False)
+
+
 def run(simulation, verbose: bool = True, n_steps: Optional[int] = None, lib=None, **kw):
     """Distributed counterpart of ``tidy3d_amd.web.run``: every rank calls it with the same
     Simulation; rank 0 returns the SimulationData, the others None."""
     import torch.distributed as dist
     from .data import assemble
-    from .discretize import discretize
     from .web import _as_mirror
     sim, _ = _as_mirror(simulation)
     sim.validate_pre_upload(source_required=True)
-    disc = discretize(sim, n_steps=n_steps)
+    disc = slab_discretization(sim, n_steps)
     eng = make_engine(disc.spec, lib=lib, **kw)
     try:
         stats = eng.run()

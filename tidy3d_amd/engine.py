@@ -218,6 +218,9 @@ def permute_spec(spec: SolverSpec, s: int) -> SolverSpec:
             for t in spec.tfsf]
     monitors = [dataclasses.replace(m, comps=tuple(int(v) for v in comp_map(m.comps)), lo=pick(m.lo), hi=pick(m.hi))
                 for m in spec.monitors]
+    # flux-time surfaces: the normal and the per-axis tables are renamed with the axes (their components stay in cyclic order)
+    monitors = [m if m.kind != "flux_time" else dataclasses.replace(m, axis=inv[m.axis], taps=pick(m.taps), weights=pick(m.weights))
+                for m in monitors]
     return dataclasses.replace(
         spec, shape=pick(spec.shape), boundaries=pick(spec.boundaries), bc=pick(spec.bc), pml=pick(spec.pml),
         mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors,
@@ -603,7 +606,20 @@ class HipEngine:
                                       _ptr(haux)), "fdtd_add_tfsf")
         # monitors (intersected with the slab)
         self.mon_ids: List[Tuple[MonitorSpec, int, Tuple[int, int]]] = []
-        for m in spec.monitors:
+        self.add_monitors(spec.monitors)
+        self._chk(d.fdtd_set_shutoff(h, int(spec.decay_every), float(spec.shutoff),
+                                     int(spec.decay_ref_step)), "fdtd_set_shutoff")
+
+    def add_monitors(self, monitors):
+        """Add ``monitors`` (MonitorSpecs on the device's axes and index layout, as ``self.spec.monitors`` are) to the handle — at
+        set-up, or between runs.  Between runs a time or DFT monitor's first record step must lie behind the steps done (the
+        library waits for its first step for ever otherwise); a flux-time monitor skips the steps already done — their entries
+        of the series stay zero — and records the rest: the tail of the series of a monitor present from the start."""
+        d, h, spec = self.lib.dll, self.handle, self.spec
+        z0, z1, nz = self.z0, self.z1, spec.shape[2]
+        uz = (2 - self.axis_shift) % 3            # the device axis that holds the user's z
+        for m in monitors:
+            self.user_zrange.setdefault(m.name, (int(m.lo[uz]), int(m.hi[uz])))
             lo2, hi2 = max(m.lo[2], z0), min(m.hi[2], z1)
             if hi2 <= lo2:
                 self.mon_ids.append((m, -1, (0, 0)))
@@ -612,6 +628,20 @@ class HipEngine:
             lo = np.asarray([m.lo[0], m.lo[1], lo2 - z0], dtype=np.int32)
             hi = np.asarray([m.hi[0], m.hi[1], hi2 - z0], dtype=np.int32)
             steps = np.ascontiguousarray(m.steps, dtype=np.int64)
+            if m.kind == "flux_time":
+                if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz) or spec.bloch is not None:
+                    raise SolverLibraryError(f"monitor '{m.name}': a FluxTimeMonitor reduced on the device is not available on z-slabs "
+                                             "(more than one GPU, force_comm) or with Bloch boundaries")
+                n_nodes = np.asarray([len(w) for w in m.weights], dtype=np.int32)
+                tidx = np.ascontiguousarray(np.concatenate([np.asarray(t[0], dtype=np.int32).ravel() for t in m.taps]))
+                tw = _f32(np.concatenate([np.asarray(t[1], dtype=np.float64).ravel() for t in m.taps]))
+                u, v = [a for a in range(3) if a != m.axis]
+                wu, wv = _f32(m.weights[u]), _f32(m.weights[v])
+                mid = d.fdtd_add_flux_time_monitor(h, int(m.axis), float(m.sign), _ptr(lo), _ptr(hi), len(steps), _ptr(steps),
+                                                   _ptr(n_nodes), _ptr(tidx), _ptr(tw), _ptr(wu), _ptr(wv), int(m.staging_bytes))
+                self._chk(mid, "fdtd_add_flux_time_monitor")
+                self.mon_ids.append((m, mid, (lo2, hi2)))
+                continue
             if m.kind == "dft":
                 pe, ph = _cplx_f32(m.phase_e), _cplx_f32(m.phase_h)
                 mid = d.fdtd_add_monitor(h, L.MON_DFT, len(comps), _ptr(comps), _ptr(lo), _ptr(hi),
@@ -621,8 +651,6 @@ class HipEngine:
                                          len(steps), _ptr(steps), 0, None, None)
             self._chk(mid, "fdtd_add_monitor")
             self.mon_ids.append((m, mid, (lo2, hi2)))
-        self._chk(d.fdtd_set_shutoff(h, int(spec.decay_every), float(spec.shutoff),
-                                     int(spec.decay_ref_step)), "fdtd_set_shutoff")
 
     # ------------------------------------------------------------------ multi-GPU
     def unique_id(self) -> bytes:
@@ -738,7 +766,9 @@ class HipEngine:
             if mid < 0:
                 continue
             bz, by, bx = hi2 - lo2, m.hi[1] - m.lo[1], m.hi[0] - m.lo[0]
-            if m.kind == "dft":
+            if m.kind == "flux_time":
+                arr = np.empty(len(m.steps), dtype=np.float32)
+            elif m.kind == "dft":
                 arr = np.empty((len(m.freqs), len(m.comps), bz, by, bx), dtype=np.complex64)
             else:
                 arr = np.empty((len(m.steps), len(m.comps), bz, by, bx), dtype=np.float32)
@@ -751,8 +781,24 @@ class HipEngine:
                 if mid >= 0:
                     out[m.name] = (out[m.name][0] + 1j * im[m.name][0], out[m.name][1])
         if self.axis_shift:                 # back to the user's axes (single slab: the z range is the box's own)
-            out = {k: (unpermute_array(v[0], self.axis_shift), self.user_zrange[k]) for k, v in out.items()}
+            out = {k: (v[0] if v[0].ndim < 3 else unpermute_array(v[0], self.axis_shift), self.user_zrange[k]) for k, v in out.items()}
         return out
+
+    def monitor_bytes(self, name: str, detail: bool = False):
+        """Device memory, as allocated, of the monitor ``name`` (all surfaces ``name::*`` of a flux monitor): bytes, or with ``detail``
+        a dict total / records (time and DFT buffers, the staging ring of a flux-time surface) / series (reduced flux) / tables."""
+        tot = np.zeros(4, dtype=np.int64)
+        hit = False
+        for m, mid, _ in self.mon_ids:
+            if mid < 0 or not (m.name == name or m.name.startswith(name + "::")):
+                continue
+            buf = (C.c_int64 * 4)()
+            self._chk(self.lib.dll.fdtd_get_monitor_bytes(self.handle, mid, buf), "fdtd_get_monitor_bytes")
+            tot += np.asarray(list(buf), dtype=np.int64)
+            hit = True
+        if not hit:
+            raise KeyError(name)
+        return dict(zip(("total", "records", "series", "tables"), (int(v) for v in tot))) if detail else int(tot[0])
 
     def results(self) -> Dict[str, np.ndarray]:
         """Single-slab convenience: name -> full array (same layout as the oracle's results())."""

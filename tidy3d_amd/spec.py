@@ -143,7 +143,11 @@ class MonitorSpec:
     kind "time": every recorded step stores the raw component values (H averaged to t_n).
     kind "dft" : running DFT  acc[f] += field * phase[n, f];  E uses phase_e (time t_n),
                  H uses phase_h (time t_n + dt/2).  ``steps`` lists the time-step indices
-                 on which the monitor records."""
+                 on which the monitor records.
+    kind "flux_time": the flux through one planar surface at every recorded step, reduced on the device (float32 [n_rec];
+                 csrc/fdtd_flux_time.hpp): flux = sign * sum over the primal nodes of the surface of (E x H) . n_axis times the
+                 node's integration weight, each component colocated to the node from the raw box [lo, hi) by ``taps``.
+                 ``comps`` = (E_t1, E_t2, H_t1, H_t2) with t1, t2 = axis + 1, axis + 2 (cyclic)."""
 
     kind: str
     comps: Tuple[int, ...]
@@ -158,6 +162,12 @@ class MonitorSpec:
     # and the apodisation window (start, end, width) or None
     stride: Optional[int] = None
     apod: Optional[Tuple[Optional[float], Optional[float], Optional[float]]] = None
+    # kind "flux_time"
+    axis: Optional[int] = None                          # normal of the surface
+    sign: float = 1.0                                   # its orientation
+    taps: Optional[Tuple] = None                        # per axis (index int32 [4, n_t, 2], weight float64 [4, n_t, 2]) into the box, components as ``comps``
+    weights: Optional[Tuple] = None                     # per axis float64 [n_t] integration weights ([1.] along the normal)
+    staging_bytes: int = 0                              # device staging budget (0: the library's default)
 
     @property
     def shape(self) -> Tuple[int, int, int]:
