@@ -2,6 +2,7 @@
 fiber-based HIP emulator (tests/hipemu/hip/hip_runtime.h) -> tests/hipemu/libfdtd_emu.so."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -11,11 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 CSRC = os.path.join(ROOT, "tidy3d_amd", "csrc")
 LIB = os.path.join(HERE, "libfdtd_emu.so")
-DEPS = [os.path.join(CSRC, "fdtd_capi.hip"), os.path.join(CSRC, "fdtd_kernels.hpp"), os.path.join(CSRC, "fdtd_kernels2.hpp"), os.path.join(CSRC, "fdtd_fused2.hpp"), os.path.join(CSRC, "fdtd_static_kernels.hpp"), os.path.join(CSRC, "fdtd_fused2.hip"),
-        os.path.join(CSRC, "fdtd_fused2c.hip"), os.path.join(CSRC, "fdtd_fused2d.hip"), os.path.join(CSRC, "fdtd_fused2w.hip"), os.path.join(CSRC, "fdtd_fused2s.hip"), os.path.join(CSRC, "fdtd_shell2.hip"), os.path.join(CSRC, "fdtd_shell2.hpp"), os.path.join(CSRC, "fdtd_shell2_host.hpp"), os.path.join(CSRC, "fdtd_strip.hpp"), os.path.join(CSRC, "fdtd_aniso.hpp"),
-        os.path.join(ROOT, "include", "fdtd_hip.h"), os.path.join(HERE, "hip_emu.cpp"),
-        os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "rccl", "rccl.h"),
-        os.path.abspath(__file__)]
+# every .hip and .hpp under csrc/ (a header added there is picked up without an edit here), and the files outside it
+DEPS = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))) + [
+    os.path.join(ROOT, "include", "fdtd_hip.h"), os.path.join(HERE, "hip_emu.cpp"),
+    os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "rccl", "rccl.h"),
+    os.path.abspath(__file__)]
 
 
 def build(force: bool = False) -> str:

@@ -1,4 +1,4 @@
-"""Shell pairs (fdtd_capi.hip): step pairs on grids walled by CPML — the two-step sweep over the bulk, the shell (CPML slabs +
+"""Shell pairs (fdtd_run.hpp, fdtd_capi.hip): step pairs on grids walled by CPML — the two-step sweep over the bulk, the shell (CPML slabs +
 collar) as two single steps of the production kernels beside it (z slabs and y slabs through fused_step_kernel with its row
 exclusion, x strips through strip_step_kernel) — against single steps of the same library on the CPU emulator: the same
 formulas in the same order -> the same bits.  Layer counts that are odd, different per face or absent on a face (a PEC or PMC

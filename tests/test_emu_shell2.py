@@ -1,4 +1,4 @@
-"""shell2 pairs (fdtd_shell2.hpp, fdtd_capi.hip): step pairs on grids walled by CPML with the shell advanced by
+"""shell2 pairs (fdtd_shell2.hpp, fdtd_run.hpp, fdtd_capi.hip): step pairs on grids walled by CPML with the shell advanced by
 shell2_step_kernel — TWO steps per sweep with the CPML recursions (psi, both sides ping-ponged) carried through both — against
 single steps of the same library on the CPU emulator: the same formulas in the same order -> the same bits.  Random initial
 fields fill the layers from the first step on; layer counts that are odd, different per face or absent on a face (a PEC or PMC

@@ -1,4 +1,4 @@
-"""Shell pairs on the device (fdtd_capi.hip): step pairs on grids walled by CPML — the two-step sweep over the bulk, the shell
+"""Shell pairs on the device (fdtd_run.hpp, fdtd_capi.hip): step pairs on grids walled by CPML — the two-step sweep over the bulk, the shell
 (CPML slabs + collar) as two single steps beside it on the second stream — held to single steps bit for bit and to the fp64
 oracle directly:
 

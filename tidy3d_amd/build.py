@@ -1,6 +1,7 @@
 """Build libfdtd_hip.so (gfx950) in-tree with hipcc.  Used by __graft_entry__.build()."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -14,9 +15,9 @@ SOURCES = [os.path.join(CSRC, "fdtd_capi.hip"), os.path.join(CSRC, "fdtd_fused2.
 # per-source flags: the two-steps-per-sweep kernels are built with the SLP vectorizer off (fdtd_fused2.hpp)
 SOURCE_FLAGS = {"fdtd_fused2.hip": ["-fno-slp-vectorize"], "fdtd_fused2c.hip": ["-fno-slp-vectorize"], "fdtd_fused2d.hip": ["-fno-slp-vectorize"], "fdtd_fused2w.hip": ["-fno-slp-vectorize"], "fdtd_fused2s.hip": ["-fno-slp-vectorize"],
                 "fdtd_shell2.hip": ["-fno-slp-vectorize"]}
-DEPS = SOURCES + [os.path.join(CSRC, "fdtd_kernels.hpp"), os.path.join(CSRC, "fdtd_kernels2.hpp"),
-                  os.path.join(CSRC, "fdtd_fused2.hpp"), os.path.join(CSRC, "fdtd_static_kernels.hpp"), os.path.join(CSRC, "fdtd_shell2.hpp"), os.path.join(CSRC, "fdtd_shell2_host.hpp"), os.path.join(CSRC, "fdtd_strip.hpp"), os.path.join(CSRC, "fdtd_aniso.hpp"), os.path.join(CSRC, "fdtd_flux_time.hpp"),
-                  os.path.join(HERE, "..", "include", "fdtd_hip.h"), os.path.abspath(__file__)]
+# every .hip and .hpp under csrc/ (a header added there is picked up without an edit here), and the two files outside it
+DEPS = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))) + [
+    os.path.join(HERE, "..", "include", "fdtd_hip.h"), os.path.abspath(__file__)]
 
 
 HOST_LIB = os.path.join(HERE, "libfdtd_host.so")
