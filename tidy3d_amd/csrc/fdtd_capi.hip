@@ -23,6 +23,7 @@
 #include "fdtd_shell2_host.hpp"
 #include "fdtd_aniso.hpp"
 #include "fdtd_flux_time.hpp"
+#include "fdtd_field_time.hpp"
 
 using namespace fdtd;
 
@@ -135,12 +136,17 @@ struct Monitor {
   long long cells = 0;
   size_t dev_bytes = 0;            // device memory the monitor holds, tables included (fdtd_get_monitor_bytes)
   // FDTD_MON_FLUX_TIME: kind stays FDTD_MON_TIME — every schedule treats the monitor as the time monitor of its box — and `data` is
-  // a ring of `ring` records (slot = record index mod ring) that flux_reduce turns into result[n_rec] (fdtd_flux_time.hpp)
+  // a ring of `ring` records (slot = record index mod ring) that ring_drain turns into result[n_rec] (fdtd_flux_time.hpp)
   bool flux = false;
   size_t ring = 0;                 // records the staging buffer holds (0: one slot per recorded step)
   size_t reduced = 0;              // records [0, reduced) are in `result`, their slots zero again
   FluxMonP fp{};                   // addresses and shapes of its tables
   size_t aux_bytes = 0;            // tap / weight tables and per-tile partial sums
+  // FDTD_MON_TIME_SPARSE: the same ring, all of `comps`; ring_drain gathers every complete record onto the kept nodes (fdtd_field_time.hpp)
+  bool sparse = false;
+  FieldTimeP gp{};
+  size_t result_bytes = 0;         // what fdtd_get_monitor returns of a ring monitor: the series / the gathered array
+  float* result() const { return flux ? fp.result : gp.out; }
   long long slot(size_t rec) const { return (long long)(ring ? rec % ring : rec); }
 };
 
@@ -327,6 +333,7 @@ struct FdtdSolver {
   double seam_flush_ms = 0.0;
   std::vector<int64_t> sweep_words;   // distinct (LB, OPT, W) of the two-step sweeps launched since fdtd_create / fdtd_reset (fdtd_get_sweep_words)
   float* seam_buf = nullptr;          // intermediate values on the seams between x tiles, and behind them the compact repair array (deferred seam repair)
+  int axis_shift = 0;                 // FDTD_OPT_AXIS_SHIFT: the cyclic renaming the caller applied (device axis a = the caller's axis (a + s) % 3)
   int seam_defer = -1;                // FDTD_OPT_SEAM_DEFER: -1 / 1 = plain sixteen-wave pairs followed by a plain pair leave their repaired seam values in the compact array, 0 = never, 2 = testing aid: at every workgroup size
   bool no_jlo = false;                // $FDTD_NO_JLO at fdtd_create (a debugging aid): no box of a shell pair starts its tile rows on the y-min wall
   bool seam_pending = false;          // the seam columns of the current set (h->f) are stale: their values lie in the repair array
@@ -1778,10 +1785,12 @@ int shell2_why_not(const FdtdSolver* h, ShellGeom* G) {
   return 0;
 }
 
-// Flux-time monitors (fdtd_flux_time.hpp): every complete record not reduced yet — records [reduced, next) of each ring — becomes
-// one value of its monitor's series, all monitors in one launch (kFluxMaxJobs per launch), and its slot is zeroed again (the H
-// half-samples are accumulated into a record).  Issued on the stream the records were written on, behind them: no other edge.
-void flux_reduce(FdtdSolver* h, hipStream_t st) {
+// Ring monitors: every complete record not consumed yet — records [reduced, next) of each ring — is turned into its part of the
+// monitor's result and its slot is zeroed again (the H half-samples are accumulated into a record).  Issued on the stream the
+// records were written on, behind them: no other edge.
+// Flux-time monitors (fdtd_flux_time.hpp): one value of the series per record, all monitors in one launch (kFluxMaxJobs per launch).
+// Sparse field-time monitors (fdtd_field_time.hpp): the values on the kept nodes, one launch per monitor.
+void ring_drain(FdtdSolver* h, hipStream_t st) {
   size_t q = 0;
   while (q < h->mons.size()) {
     FluxLaunchP L{};
@@ -1800,9 +1809,30 @@ void flux_reduce(FdtdSolver* h, hipStream_t st) {
     hipLaunchKernelGGL(flux_time_reduce_kernel, dim3(tiles, cnt, L.n), dim3(256), 0, st, L);
     hipLaunchKernelGGL(flux_time_final_kernel, dim3((cnt + 255) / 256, L.n), dim3(256), 0, st, L);
   }
+  for (const Monitor& m : h->mons) {
+    if (!m.sparse || m.reduced >= m.next) continue;
+    dbg_sync(h);
+    int nx = 1;
+    long long rows = 1;
+    for (size_t c = 0; c < m.comps.size(); ++c) {
+      nx = std::max(nx, m.gp.nt[c][0]);
+      rows = std::max(rows, (long long)m.gp.nt[c][1] * m.gp.nt[c][2]);
+    }
+    const unsigned gy = (unsigned)std::min<long long>((rows + kFieldTimeRows - 1) / kFieldTimeRows, kFieldTimeMaxRowBlocks);
+    const size_t per_launch = (size_t)65535 / m.comps.size();          // (grid z: record x component)
+    for (size_t r = m.reduced; r < m.next; r += per_launch) {
+      FieldTimeP p = m.gp;
+      p.r0 = (long long)r;
+      p.cnt = (int)std::min(per_launch, m.next - r);
+      const dim3 grid((unsigned)((nx + 63) / 64), gy, (unsigned)(p.cnt * p.n_comps)), block(64, kFieldTimeRows);
+      if (h->axis_shift == 1) hipLaunchKernelGGL(field_time_gather_kernel<1>, grid, block, 0, st, p);
+      else if (h->axis_shift == 2) hipLaunchKernelGGL(field_time_gather_kernel<2>, grid, block, 0, st, p);
+      else hipLaunchKernelGGL(field_time_gather_kernel<0>, grid, block, 0, st, p);
+    }
+  }
   for (Monitor& m : h->mons) {
-    if (!m.flux || m.reduced >= m.next) continue;
-    const size_t rec_bytes = 4 * (size_t)m.cells * sizeof(float);
+    if (!m.ring || m.reduced >= m.next) continue;
+    const size_t rec_bytes = m.comps.size() * (size_t)m.cells * sizeof(float);
     const size_t s0 = m.reduced % m.ring, cnt = m.next - m.reduced, first = std::min(cnt, m.ring - s0);
     hipMemsetAsync(reinterpret_cast<char*>(m.data) + s0 * rec_bytes, 0, first * rec_bytes, st);
     if (cnt > first) hipMemsetAsync(m.data, 0, (cnt - first) * rec_bytes, st);
@@ -1843,13 +1873,13 @@ void pair_record(FdtdSolver* h, const F2Table* tb, long long n, hipStream_t st) 
   PairRecP r{};
   r.pre_done = h_terms_in_front(h);            // (then fdtd_run has not skipped them at the top of the step)
   long long max_cells = 0;
-  for (size_t q = 0; q < tb->mons.size(); ++q) {      // flux-time rings: room for the (at most two) records of this pair
+  for (size_t q = 0; q < tb->mons.size(); ++q) {      // rings: room for the (at most two) records of this pair
     const Monitor& m = h->mons[(size_t)tb->mons[q]];
     if (!m.ring) continue;
     size_t last = m.next;
     if (last < m.steps.size() && m.steps[last] == n) ++last;
     if (last < m.steps.size() && m.steps[last] == n + 1) ++last;
-    if (last > m.next && last - 1 - m.reduced >= m.ring) { flux_reduce(h, st); break; }
+    if (last > m.next && last - 1 - m.reduced >= m.ring) { ring_drain(h, st); break; }
   }
   for (size_t q = 0; q < tb->mons.size(); ++q) {
     Monitor& m = h->mons[(size_t)tb->mons[q]];
@@ -2851,7 +2881,7 @@ void record_monitors(FdtdSolver* h, long long n, bool post, hipStream_t st, cons
     if (r.n > 0 && m.cells > 0) {
       const dim3 grid(nblk(m.cells), r.n);
       if (m.kind == FDTD_MON_TIME) {
-        if (m.ring && (size_t)rec - m.reduced >= m.ring) flux_reduce(h, st);      // (a full flux-time ring: its complete records first)
+        if (m.ring && (size_t)rec - m.reduced >= m.ring) ring_drain(h, st);      // (a full ring: its complete records first)
         float* out = reinterpret_cast<float*>(m.data) + m.slot((size_t)rec) * nc * m.cells;
         hipLaunchKernelGGL(time_record_multi_kernel, grid, dim3(256), 0, st, r, h->g, m.box, out, (long long)m.cells);
       } else {
@@ -3386,6 +3416,7 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
                      const float* phase_h) {
   if (!h) return -1;
   if (kind == FDTD_MON_FLUX_TIME) return fail(h, "fdtd_add_monitor: FDTD_MON_FLUX_TIME monitors are added by fdtd_add_flux_time_monitor");
+  if (kind == FDTD_MON_TIME_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_TIME_SPARSE monitors are added by fdtd_add_field_time_monitor");
   if (kind != FDTD_MON_TIME && kind != FDTD_MON_DFT) return fail(h, "fdtd_add_monitor: bad kind %d", kind);
   const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
   for (int a = 0; a < 3; ++a)
@@ -3423,6 +3454,26 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
   h->mons.push_back(m);
   return (int)h->mons.size() - 1;
 }
+
+}  // extern "C"
+namespace {
+// The staging ring of a ring monitor (comps, cells and steps set): as many records as the budget holds, at least two (a step pair
+// records two steps), no more than there are.  Added between runs, the steps already done are skipped — their part of the result
+// stays zero — until fdtd_reset.  (Like fdtd_add_monitor: what a failure has allocated stays with the handle until fdtd_destroy.)
+int ring_setup(FdtdSolver* h, Monitor& m, int64_t staging_bytes) {
+  while (m.next < m.steps.size() && m.steps[m.next] < h->step) ++m.next;
+  m.reduced = m.next;
+  const size_t rec_floats = m.comps.size() * (size_t)m.cells, rec_bytes = rec_floats * sizeof(float);
+  const size_t budget = staging_bytes > 0 ? (size_t)staging_bytes : ((size_t)32 << 20);
+  m.ring = std::max<size_t>(2, std::min<size_t>(std::min<size_t>(budget / rec_bytes, (size_t)kFluxMaxRing), std::max<size_t>(m.steps.size(), 2)));
+  m.data_bytes = m.ring * rec_bytes;
+  float* stage = nullptr;
+  if (dev_alloc(h, &stage, m.ring * rec_floats)) return -1;
+  m.data = stage;
+  return 0;
+}
+}  // namespace
+extern "C" {
 
 int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_t lo[3], const int32_t hi[3], int64_t n_rec,
                                const int64_t* steps, const int32_t n_nodes[3], const int32_t* tap_index, const float* tap_weight,
@@ -3464,19 +3515,10 @@ int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_
   m.steps.assign(steps, steps + n_rec);
   for (size_t i = 1; i < m.steps.size(); ++i)
     if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_flux_time_monitor: steps must be strictly increasing");
-  // added between runs: the steps already done are skipped — their entries of the series stay zero — until fdtd_reset
-  while (m.next < m.steps.size() && m.steps[m.next] < h->step) ++m.next;
-  m.reduced = m.next;
-  // (like fdtd_add_monitor: what a failure below has allocated already stays with the handle until fdtd_destroy)
-  // the ring: as many records as the budget holds, at least two (a step pair records two steps), no more than there are
-  const size_t rec_bytes = 4 * (size_t)m.cells * sizeof(float);
-  const size_t budget = staging_bytes > 0 ? (size_t)staging_bytes : ((size_t)32 << 20);
-  m.ring = std::max<size_t>(2, std::min<size_t>(std::min<size_t>(budget / rec_bytes, (size_t)kFluxMaxRing), std::max<size_t>((size_t)n_rec, 2)));
-  m.data_bytes = m.ring * rec_bytes;
-  float *stage = nullptr, *result = nullptr, *partial = nullptr;
-  if (dev_alloc(h, &stage, m.ring * 4 * (size_t)m.cells)) return -1;
-  m.data = stage;
+  if (ring_setup(h, m, staging_bytes)) return -1;
+  float *stage = reinterpret_cast<float*>(m.data), *result = nullptr, *partial = nullptr;
   if (dev_alloc(h, &result, (size_t)n_rec)) return -1;
+  m.result_bytes = (size_t)n_rec * sizeof(float);
   const int64_t bytes_aux = h->stats.device_bytes;
   FluxMonP& p = m.fp;
   const long long nodes = (long long)n_nodes[0] * n_nodes[1] * n_nodes[2];
@@ -3500,14 +3542,78 @@ int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_
   return (int)h->mons.size() - 1;
 }
 
+int fdtd_add_field_time_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
+                                int64_t n_rec, const int64_t* steps, const int32_t* n_targets, const int32_t* tap_index,
+                                const float* tap_weight, int64_t staging_bytes) {
+  if (!h) return -1;
+  if (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR)
+    return fail(h, "fdtd_add_field_time_monitor: not available on z-slab handles (the box would be cut between ranks)");
+  if (n_comps < 1 || n_comps > 6) return fail(h, "fdtd_add_field_time_monitor: n_comps must be 1..6");
+  if (!comps || !lo || !hi || !n_targets || !tap_index || !tap_weight || n_rec < 0 || (n_rec && !steps))
+    return fail(h, "fdtd_add_field_time_monitor: bad argument");
+  for (int c = 0; c < n_comps; ++c) if (comps[c] < 0 || comps[c] > 5) return fail(h, "fdtd_add_field_time_monitor: bad component %d", comps[c]);
+  const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
+  for (int a = 0; a < 3; ++a)
+    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "fdtd_add_field_time_monitor: box [%d,%d) outside axis %d of %d cells", lo[a], hi[a], a, N[a]);
+  // every tap that is read (weight != 0) must lie inside the box
+  const int ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+  FieldTimeP p{};
+  size_t n_taps = 0;
+  for (int c = 0; c < n_comps; ++c) {
+    long long nodes = 1;
+    for (int a = 0; a < 3; ++a) {
+      const int nt = n_targets[3 * c + a];
+      if (nt < 1 || nt > (1 << 24)) return fail(h, "fdtd_add_field_time_monitor: %d nodes of component %d along axis %d", nt, comps[c], a);
+      p.off[c][a] = (int)n_taps; p.nt[c][a] = nt;
+      for (size_t t = 0; t < (size_t)2 * nt; ++t) {
+        const float w = tap_weight[n_taps + t];
+        if (!(w == w) || (w != 0.0f && (tap_index[n_taps + t] < 0 || tap_index[n_taps + t] >= ext[a])))
+          return fail(h, "fdtd_add_field_time_monitor: tap %zu of component %d, axis %d (index %d, weight %g) outside the box of %d cells", t, comps[c], a,
+                      tap_index[n_taps + t], (double)w, ext[a]);
+      }
+      n_taps += (size_t)2 * nt;
+      nodes *= nt;
+    }
+    p.out_off[c] = p.rec_nodes;
+    p.rec_nodes += nodes;
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  const int64_t bytes_before = h->stats.device_bytes;
+  Monitor m;
+  m.kind = FDTD_MON_TIME;
+  m.sparse = true;
+  m.comps.assign(comps, comps + n_comps);
+  m.box.lo0 = lo[0]; m.box.lo1 = lo[1]; m.box.lo2 = lo[2];
+  m.box.nx = ext[0]; m.box.ny = ext[1]; m.box.nz = ext[2];
+  m.cells = (long long)ext[0] * ext[1] * ext[2];
+  m.steps.assign(steps, steps + n_rec);
+  for (size_t i = 1; i < m.steps.size(); ++i)
+    if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_field_time_monitor: steps must be strictly increasing");
+  if (ring_setup(h, m, staging_bytes)) return -1;
+  float* out = nullptr;
+  if (dev_alloc(h, &out, (size_t)n_rec * (size_t)p.rec_nodes)) return -1;
+  m.result_bytes = (size_t)n_rec * (size_t)p.rec_nodes * sizeof(float);
+  const int64_t bytes_aux = h->stats.device_bytes;
+  int* di = nullptr; float* dw = nullptr;
+  if (dev_upload(h, &di, (const int*)tap_index, n_taps) || dev_upload(h, &dw, tap_weight, n_taps)) return -1;
+  p.stage = reinterpret_cast<const float*>(m.data); p.out = out; p.idx = di; p.w = dw;
+  for (int a = 0; a < 3; ++a) p.b[a] = ext[a];
+  p.n_comps = n_comps; p.ring = (int)m.ring;
+  m.gp = p;
+  m.aux_bytes = (size_t)(h->stats.device_bytes - bytes_aux);
+  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
+  h->mons.push_back(m);
+  return (int)h->mons.size() - 1;
+}
+
 int fdtd_get_monitor_bytes(FdtdSolver* h, int id, int64_t out[4]) {
   if (!h) return -1;
   if (id < 0 || id >= (int)h->mons.size() || !out) return fail(h, "fdtd_get_monitor_bytes: bad id %d", id);
   const Monitor& m = h->mons[id];
   out[0] = (int64_t)m.dev_bytes;
   out[1] = (int64_t)m.data_bytes;
-  out[2] = m.flux ? (int64_t)(m.dev_bytes - m.data_bytes - m.aux_bytes) : 0;
-  out[3] = m.flux ? (int64_t)m.aux_bytes : (int64_t)(m.dev_bytes - m.data_bytes);
+  out[2] = m.ring ? (int64_t)(m.dev_bytes - m.data_bytes - m.aux_bytes) : 0;
+  out[3] = m.ring ? (int64_t)m.aux_bytes : (int64_t)(m.dev_bytes - m.data_bytes);
   return 0;
 }
 
@@ -3515,12 +3621,12 @@ int fdtd_get_monitor(FdtdSolver* h, int id, void* host, size_t bytes) {
   if (!h) return -1;
   if (id < 0 || id >= (int)h->mons.size()) return fail(h, "fdtd_get_monitor: bad id %d", id);
   Monitor& m = h->mons[id];
-  if (m.flux) {                        // the reduced series
-    if (bytes != m.steps.size() * sizeof(float)) return fail(h, "fdtd_get_monitor: expected %zu bytes, got %zu", m.steps.size() * sizeof(float), bytes);
+  if (m.ring) {                        // the reduced series / the gathered nodes
+    if (bytes != m.result_bytes) return fail(h, "fdtd_get_monitor: expected %zu bytes, got %zu", m.result_bytes, bytes);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    flux_reduce(h, h->stream);
+    ring_drain(h, h->stream);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (bytes) HIPCHK(h, hipMemcpy(host, m.fp.result, bytes, hipMemcpyDeviceToHost));
+    if (bytes) HIPCHK(h, hipMemcpy(host, m.result(), bytes, hipMemcpyDeviceToHost));
     return 0;
   }
   if (bytes != m.data_bytes) return fail(h, "fdtd_get_monitor: expected %zu bytes, got %zu", m.data_bytes, bytes);
@@ -3585,7 +3691,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   HIPCHK(h, hipSetDevice(h->cfg.device));
   ncclUniqueId u;
   std::memcpy(&u, id, 128);
-  for (const Monitor& m : h->mons) if (m.flux) return fail(h, "fdtd_comm_init: flux-time monitors are not available on z-slab handles");
+  for (const Monitor& m : h->mons) if (m.ring) return fail(h, "fdtd_comm_init: flux-time and sparse field-time monitors are not available on z-slab handles");
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)
@@ -3629,7 +3735,7 @@ int fdtd_reset(FdtdSolver* h) {
   for (Monitor& m : h->mons) {
     HIPCHK(h, hipMemset(m.data, 0, m.data_bytes));
     m.next = 0;
-    if (m.flux) { HIPCHK(h, hipMemset(m.fp.result, 0, std::max<size_t>(m.steps.size(), 1) * sizeof(float))); m.reduced = 0; }
+    if (m.ring) { HIPCHK(h, hipMemset(m.result(), 0, std::max<size_t>(m.result_bytes, sizeof(float)))); m.reduced = 0; }
   }
   h->step = 0; h->energy_max = 0.0;
   h->stats.steps_done = 0; h->stats.diverged = 0; h->stats.stopped_early = 0; h->stats.field_decay = 0.0;      // (what a fresh handle reports until its first decay check)
@@ -3647,7 +3753,7 @@ extern "C" {
 int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user) {
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  if (h->comm) for (const Monitor& m : h->mons) if (m.flux) return fail(h, "fdtd_run: flux-time monitors are not available on z-slab handles");
+  if (h->comm) for (const Monitor& m : h->mons) if (m.ring) return fail(h, "fdtd_run: flux-time and sparse field-time monitors are not available on z-slab handles");
   Run r{h, n_steps, progress, user};
   if (r.setup() || r.setup_schedules() || r.setup_pairs()) return -1;
   if (r.loop()) { flush_seams(h, h->stream); return -1; }      // (an error leaves no stale seam columns either)
@@ -3664,7 +3770,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
                    FdtdProgressFn progress, void* user) {
   if (!hr || !hi) return -1;
   for (const FdtdSolver* hh : {hr, hi})
-    for (const Monitor& m : hh->mons) if (m.flux) return fail(hr, "fdtd_run_bloch: flux-time monitors are not available with Bloch boundaries (complex fields)");
+    for (const Monitor& m : hh->mons) if (m.ring) return fail(hr, "fdtd_run_bloch: flux-time and sparse field-time monitors (fdtd_add_flux_time_monitor, fdtd_add_field_time_monitor) are not available with Bloch boundaries (complex fields)");
   if (hi->comm) return fail(hr, "fdtd_run_bloch: the communicator of a z-slab belongs to the first (real-part) handle");
   // fully anisotropic bodies: the Re handle's lists (wrap codes included) drive both parts; the Im handle's carry the same rows
   const bool aniso = !hr->aniso.empty();
@@ -3922,6 +4028,7 @@ int fdtd_set_option(FdtdSolver* h, int key, int value) {
     case FDTD_OPT_SLAB_BOXES_FIRST: if (value < 0 || value > 3) break; h->slab_boxes_first = value; return 0;
     case FDTD_OPT_WHATIF: if (value < 0 || value > 19) break; h->whatif = value; return 0;
     case FDTD_OPT_SEAM_DEFER: if (value > 2) break; h->seam_defer = value < 0 ? -1 : value; return 0;
+    case FDTD_OPT_AXIS_SHIFT: if (value < 0 || value > 2) break; h->axis_shift = value; return 0;
     case FDTD_OPT_DISP:
       if (h->disp.state == 1 && value == 0) break;       // (every ADE launch keeps the paged memory terms by now: set it before the first run)
       h->disp_on = value < 0 ? -1 : (value != 0);

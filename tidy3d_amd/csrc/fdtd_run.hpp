@@ -1057,7 +1057,7 @@ struct Run {
   // joins the streams, reads the timers
   int finish() {
     flush_seams(h, st);          // (a run never returns with stale seam columns)
-    flux_reduce(h, st);          // (nor with flux-time records waiting in their rings)
+    ring_drain(h, st);           // (nor with records waiting in their rings)
     if (multi) {
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));

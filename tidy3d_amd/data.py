@@ -489,10 +489,17 @@ def expand_symmetry(arr: np.ndarray, half: Sequence[np.ndarray], full: Sequence[
 def _field_container(cls, mon, spec: SolverSpec, fp: FieldPlan, raw: np.ndarray, lead: str,
                      lead_coords: np.ndarray, sim_center, dtype, full=None):
     """``full`` = (FieldPlan on the full grid, full-grid spec, symmetry) when the solver ran on the
-    symmetry-reduced domain."""
+    symmetry-reduced domain.  A two-dimensional ``raw`` [lead, kept nodes of all fields] is what the device has gathered onto the
+    target coordinates already (MonitorSpec kind "time_sparse"): nothing is interpolated here."""
     kw = {}
+    off = 0
     for ic, fname in enumerate(fp.fields):
-        arr = _colocate_box(raw, spec, fp, ic, fname)           # [lead, z, y, x]
+        if raw.ndim == 2:
+            nx, ny, nz = (len(t) for t in fp.target[fname])
+            arr = raw[:, off:off + nx * ny * nz].reshape(raw.shape[0], nz, ny, nx)
+            off += nx * ny * nz
+        else:
+            arr = _colocate_box(raw, spec, fp, ic, fname)       # [lead, z, y, x]
         arr = np.transpose(arr, (3, 2, 1, 0)).astype(dtype)      # (x, y, z, lead)
         tx, ty, tz = fp.target[fname]
         if full is not None:
@@ -500,6 +507,8 @@ def _field_container(cls, mon, spec: SolverSpec, fp: FieldPlan, raw: np.ndarray,
             arr = expand_symmetry(arr, (tx, ty, tz), fp_full.target[fname], fname, symmetry, sim_center)
             tx, ty, tz = fp_full.target[fname]
         kw[fname] = DataArray(arr, {"x": tx, "y": ty, "z": tz, lead: lead_coords})
+    if raw.ndim == 2 and off != raw.shape[1]:
+        raise DataError(f"monitor '{fp.spec_name}': {raw.shape[1]} gathered nodes per record, the target coordinates hold {off}")
     gexp = _grid_expanded(spec, fp) if full is None else _grid_expanded(full[1], full[0])
     return cls(monitor=mon, symmetry=(0, 0, 0), symmetry_center=tuple(sim_center),
                grid_expanded=gexp, **kw)

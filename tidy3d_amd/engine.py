@@ -221,6 +221,8 @@ def permute_spec(spec: SolverSpec, s: int) -> SolverSpec:
     # flux-time surfaces: the normal and the per-axis tables are renamed with the axes (their components stay in cyclic order)
     monitors = [m if m.kind != "flux_time" else dataclasses.replace(m, axis=inv[m.axis], taps=pick(m.taps), weights=pick(m.weights))
                 for m in monitors]
+    # sparse field-time monitors: every component's per-axis tables (hence its kept-node counts) are renamed with the axes
+    monitors = [m if m.kind != "time_sparse" else dataclasses.replace(m, taps=tuple(pick(t) for t in m.taps)) for m in monitors]
     return dataclasses.replace(
         spec, shape=pick(spec.shape), boundaries=pick(spec.boundaries), bc=pick(spec.bc), pml=pick(spec.pml),
         mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors,
@@ -379,6 +381,8 @@ class HipEngine:
         if st < 0:
             raise SolverLibraryError(f"fdtd_create failed: {self.lib.error(None)}")
         try:
+            if self.axis_shift:             # (what is formed axis after axis — a sparse field-time monitor's gather — keeps the user's order)
+                self.set_option(L.OPT_AXIS_SHIFT, self.axis_shift)
             self._setup(spec)
             if spec.bloch is not None and _bloch_twin is None:
                 import dataclasses
@@ -613,8 +617,8 @@ class HipEngine:
     def add_monitors(self, monitors):
         """Add ``monitors`` (MonitorSpecs on the device's axes and index layout, as ``self.spec.monitors`` are) to the handle — at
         set-up, or between runs.  Between runs a time or DFT monitor's first record step must lie behind the steps done (the
-        library waits for its first step for ever otherwise); a flux-time monitor skips the steps already done — their entries
-        of the series stay zero — and records the rest: the tail of the series of a monitor present from the start."""
+        library waits for its first step for ever otherwise); a flux-time or sparse field-time monitor skips the steps already
+        done — their entries of the result stay zero — and records the rest: the tail of the series of a monitor present from the start."""
         d, h, spec = self.lib.dll, self.handle, self.spec
         z0, z1, nz = self.z0, self.z1, spec.shape[2]
         uz = (2 - self.axis_shift) % 3            # the device axis that holds the user's z
@@ -640,6 +644,18 @@ class HipEngine:
                 mid = d.fdtd_add_flux_time_monitor(h, int(m.axis), float(m.sign), _ptr(lo), _ptr(hi), len(steps), _ptr(steps),
                                                    _ptr(n_nodes), _ptr(tidx), _ptr(tw), _ptr(wu), _ptr(wv), int(m.staging_bytes))
                 self._chk(mid, "fdtd_add_flux_time_monitor")
+                self.mon_ids.append((m, mid, (lo2, hi2)))
+                continue
+            if m.kind == "time_sparse":
+                if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz) or spec.bloch is not None:
+                    raise SolverLibraryError(f"monitor '{m.name}': a FieldTimeMonitor gathered on the device is not available on z-slabs "
+                                             "(more than one GPU, force_comm) or with Bloch boundaries")
+                n_t = np.asarray(m.targets, dtype=np.int32)
+                tidx = np.ascontiguousarray(np.concatenate([np.asarray(t[a][0], dtype=np.int32).ravel() for t in m.taps for a in range(3)]))
+                tw = _f32(np.concatenate([np.asarray(t[a][1], dtype=np.float64).ravel() for t in m.taps for a in range(3)]))
+                mid = d.fdtd_add_field_time_monitor(h, len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t),
+                                                    _ptr(tidx), _ptr(tw), int(m.staging_bytes))
+                self._chk(mid, "fdtd_add_field_time_monitor")
                 self.mon_ids.append((m, mid, (lo2, hi2)))
                 continue
             if m.kind == "dft":
@@ -760,7 +776,8 @@ class HipEngine:
 
     def monitor_data(self) -> Dict[str, Tuple[np.ndarray, Tuple[int, int]]]:
         """name -> (array over the slab-local part of the box, (z_lo, z_hi) global plane range).
-        time: float32 [n_rec, n_comps, bz, by, bx]; dft: complex64 [nf, n_comps, bz, by, bx]."""
+        time: float32 [n_rec, n_comps, bz, by, bx]; dft: complex64 [nf, n_comps, bz, by, bx]; flux_time: float32 [n_rec];
+        time_sparse: float32 [n_rec, kept nodes of all components] (each component [nz_t, ny_t, nx_t], on the user's axes)."""
         out = {}
         for m, mid, (lo2, hi2) in self.mon_ids:
             if mid < 0:
@@ -768,12 +785,21 @@ class HipEngine:
             bz, by, bx = hi2 - lo2, m.hi[1] - m.lo[1], m.hi[0] - m.lo[0]
             if m.kind == "flux_time":
                 arr = np.empty(len(m.steps), dtype=np.float32)
+            elif m.kind == "time_sparse":
+                arr = np.empty((len(m.steps), sum(int(np.prod(t)) for t in m.targets)), dtype=np.float32)
             elif m.kind == "dft":
                 arr = np.empty((len(m.freqs), len(m.comps), bz, by, bx), dtype=np.complex64)
             else:
                 arr = np.empty((len(m.steps), len(m.comps), bz, by, bx), dtype=np.float32)
             self._chk(self.lib.dll.fdtd_get_monitor(self.handle, mid, _ptr(arr), arr.nbytes),
                       "fdtd_get_monitor")
+            if m.kind == "time_sparse" and self.axis_shift:        # every component back to the user's axes
+                parts, off = [], 0
+                for nx, ny, nz_t in m.targets:
+                    blk = arr[:, off:off + nx * ny * nz_t].reshape(len(arr), nz_t, ny, nx)
+                    parts.append(unpermute_array(blk, self.axis_shift).reshape(len(arr), -1))
+                    off += nx * ny * nz_t
+                arr = np.ascontiguousarray(np.concatenate(parts, axis=1))
             out[m.name] = (arr, (lo2, hi2))
         if self.twin is not None:       # complex fields (ref simulation.py:4396 complex_fields): value = re + i im
             im = self.twin.monitor_data()

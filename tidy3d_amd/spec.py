@@ -147,7 +147,12 @@ class MonitorSpec:
     kind "flux_time": the flux through one planar surface at every recorded step, reduced on the device (float32 [n_rec];
                  csrc/fdtd_flux_time.hpp): flux = sign * sum over the primal nodes of the surface of (E x H) . n_axis times the
                  node's integration weight, each component colocated to the node from the raw box [lo, hi) by ``taps``.
-                 ``comps`` = (E_t1, E_t2, H_t1, H_t2) with t1, t2 = axis + 1, axis + 2 (cyclic)."""
+                 ``comps`` = (E_t1, E_t2, H_t1, H_t2) with t1, t2 = axis + 1, axis + 2 (cyclic).
+    kind "time_sparse": a time monitor whose result holds only the nodes the user keeps, gathered on the device
+                 (csrc/fdtd_field_time.hpp): float32 [n_rec, sum over ``comps`` of the component's kept nodes], inside a record the
+                 components one after the other, each [nz_t][ny_t][nx_t].  Every value is the separable linear interpolation ``taps``
+                 describe from the raw box [lo, hi): the colocated, downsampled primal nodes (colocate=True) or the downsampled Yee
+                 nodes of the component (colocate=False; the node counts then differ between components)."""
 
     kind: str
     comps: Tuple[int, ...]
@@ -166,8 +171,14 @@ class MonitorSpec:
     axis: Optional[int] = None                          # normal of the surface
     sign: float = 1.0                                   # its orientation
     taps: Optional[Tuple] = None                        # per axis (index int32 [4, n_t, 2], weight float64 [4, n_t, 2]) into the box, components as ``comps``
+    #                                                     kind "time_sparse": per component of ``comps``, per axis (index int32 [n_t, 2], weight float64 [n_t, 2])
     weights: Optional[Tuple] = None                     # per axis float64 [n_t] integration weights ([1.] along the normal)
     staging_bytes: int = 0                              # device staging budget (0: the library's default)
+
+    @property
+    def targets(self) -> Tuple[Tuple[int, int, int], ...]:
+        """kind "time_sparse": (nx_t, ny_t, nz_t) kept nodes of every component."""
+        return tuple(tuple(int(len(t[a][0])) for a in range(3)) for t in self.taps)
 
     @property
     def shape(self) -> Tuple[int, int, int]:

@@ -94,7 +94,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         simulation_type: str = "tidy3d", parent_tasks=None, local_gradient: bool = False,
         *, device: int = 0, n_steps: Optional[int] = None, lib=None,
         return_tidy3d: Optional[bool] = None, devices=None, _dist_options: Optional[dict] = None,
-        mode_grid_dispersion: Optional[bool] = None, flux_time_device: Optional[bool] = None) -> SimulationData:
+        mode_grid_dispersion: Optional[bool] = None, flux_time_device: Optional[bool] = None,
+        field_time_device: Optional[bool] = None) -> SimulationData:
     """Solve ``simulation`` on the local MI355X and return its ``SimulationData``.
 
     Cloud-only arguments (``folder_name``, ``callback_url``, ``progress_callback_*``,
@@ -107,14 +108,18 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     one call.  ``mode_grid_dispersion``: False launches mode sources with the continuum mode instead of the one the Yee
     grid propagates (``discretize.MODE_SOURCE_GRID_DISPERSION``, default True; one-GPU runs).  ``flux_time_device``: reduce
     ``FluxTimeMonitor`` surfaces on the device (True), on the host from plane records (False), or per monitor by the memory the
-    records would take (None, ``discretize.FLUX_TIME_HOST_BYTES``; one-GPU runs without symmetry or Bloch boundaries)."""
+    records would take (None, ``discretize.FLUX_TIME_HOST_BYTES``; one-GPU runs without symmetry or Bloch boundaries).
+    ``field_time_device``: colocate and downsample (``interval_space``) ``FieldTimeMonitor`` records on the device (True), on the host
+    from records of the whole box (False), or per monitor (None: on the device where those records would exceed the same
+    threshold and fewer nodes are kept than the box holds; the same kinds of run)."""
     from .engine import HipEngine
 
     sim, was_tidy3d = _as_mirror(simulation)
     sim.validate_pre_upload(source_required=True)
     if devices is not None and len(devices) > 1:
-        from .discretize import _flux_time_refusal
+        from .discretize import _field_time_refusal, _flux_time_refusal
         _flux_time_refusal(sim, flux_time_device, "devices= with more than one GPU")
+        _field_time_refusal(sim, field_time_device, "devices= with more than one GPU")
         sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose, _dist_options or {})
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
         if want_td:
@@ -129,7 +134,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
     t_setup = time.perf_counter()
-    disc = discretize(sim, n_steps=n_steps, mode_grid_dispersion=mode_grid_dispersion, flux_time_device=flux_time_device)
+    disc = discretize(sim, n_steps=n_steps, mode_grid_dispersion=mode_grid_dispersion, flux_time_device=flux_time_device,
+                      field_time_device=field_time_device)
     spec = disc.spec
     lines = [f"Simulation domain Nx, Ny, Nz: {list(spec.shape)}",
              f"Applied symmetries: {tuple(sim.symmetry)}",
@@ -160,8 +166,10 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         if diverged:
             lines.append("WARNING: field divergence detected, exiting solver.")
         on_device = sorted({m.name.split("::")[0] for m in spec.monitors if m.kind == "flux_time"})
+        gathered = sorted(m.name for m in spec.monitors if m.kind == "time_sparse")
         lines.append(schedule_line(stats, spec.n_cells, solve_s)
-                     + (f" FluxTimeMonitor reduced on the device: {', '.join(on_device)}." if on_device else ""))
+                     + (f" FluxTimeMonitor reduced on the device: {', '.join(on_device)}." if on_device else "")
+                     + (f" FieldTimeMonitor gathered on the device: {', '.join(gathered)}." if gathered else ""))
     lines += ["", f"Setup time (s):  {setup_s:.4f}", f"Solver time (s): {solve_s:.4f}",
               f"Time-stepping speed (cells/s): {spec.n_cells * steps_done / max(solve_s, 1e-9):.2e}"]
     sim_data = assemble(disc, raw, log="\n".join(lines), diverged=diverged, n_steps_run=steps_done, device_lib=used_lib, device=device)
