@@ -37,7 +37,8 @@ typedef struct FdtdSolver FdtdSolver;
 
 enum { FDTD_BC_PEC = 0, FDTD_BC_PMC = 1, FDTD_BC_PERIODIC = 2, FDTD_BC_NEIGHBOR = 3 };
 enum { FDTD_MON_TIME = 0, FDTD_MON_DFT = 1, FDTD_MON_FLUX_TIME = 2 /* added by fdtd_add_flux_time_monitor only */,
-       FDTD_MON_TIME_SPARSE = 3 /* added by fdtd_add_field_time_monitor only */ };
+       FDTD_MON_TIME_SPARSE = 3 /* added by fdtd_add_field_time_monitor only */,
+       FDTD_MON_DFT_SPARSE = 4 /* added by fdtd_add_field_dft_monitor only */ };
 /* kernel variants of the two main update kernels (A/B-tested by bench.py --variant) */
 /* AUTO = FUSED on one GPU (single-sweep E+H update, 48 B/cell-step), two-pass ZMARCH otherwise */
 enum { FDTD_VARIANT_AUTO = 0, FDTD_VARIANT_SIMPLE = 1, FDTD_VARIANT_ZMARCH = 2, FDTD_VARIANT_FUSED = 3 };
@@ -284,11 +285,28 @@ int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_
 int fdtd_add_field_time_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
                                 int64_t n_rec, const int64_t* steps, const int32_t* n_targets,
                                 const int32_t* tap_index, const float* tap_weight, int64_t staging_bytes);
+/* FDTD_MON_DFT_SPARSE (ref monitor.py FieldMonitor with interval_space / colocate): the running DFT of the components `comps` on the
+ * nodes the monitor keeps — the result is complex64 [nf][component][n_z][n_y][n_x], the node counts of each component its own
+ * (n_targets[3 * c + a], a = x, y, z; the components follow one another inside a frequency), and the device holds these accumulators
+ * and nothing of the box [lo, hi).  The monitor records like the FDTD_MON_DFT monitor of that box in every schedule (E at step n with
+ * phase_e, H at n + 1/2 with phase_h, both [n_rec][nf] complex64; inside step pairs from the sweep's copy of the middle step); at
+ * every record each sample is colocated onto the kept nodes first,
+ *     v = sum over the 2 x 2 x 2 taps of wx wy wz F[jz][jy][jx]           (separable: x, then y, then z; fp32)
+ *     acc[f][node] += v * phase[rec][f]
+ * with the tap tables of fdtd_add_field_time_monitor (same layout, same checks: a tap of weight 0 is not read, every other index
+ * must lie inside the box).  Added between runs, the steps already done are skipped: it accumulates from then on (fdtd_reset: from
+ * step 0).  Refused on z-slab handles (FDTD_BC_NEIGHBOR faces, fdtd_comm_init); fdtd_run_bloch refuses handles that carry one.
+ * Returns the monitor id (>= 0) or <0. */
+int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
+                               int64_t n_rec, const int64_t* steps, const int32_t* n_targets,
+                               const int32_t* tap_index, const float* tap_weight, int nf, const float* phase_e, const float* phase_h);
 /* time: float [n_rec][n_comps][bz][by][bx];  dft: complex64 [nf][n_comps][bz][by][bx];  flux-time: float [n_rec];
- * sparse field-time: float [n_rec][sum over the components of their kept nodes] */
+ * sparse field-time: float [n_rec][sum over the components of their kept nodes];
+ * sparse DFT: complex64 [nf][sum over the components of their kept nodes] */
 int fdtd_get_monitor(FdtdSolver* h, int monitor_id, void* host, size_t bytes);
 /* device memory a monitor holds, as allocated: out[0] = all of it, out[1] = its record buffer (flux-time, sparse field-time: the staging ring),
- * out[2] = the reduced series of a flux-time monitor / the gathered array of a sparse field-time monitor (else 0),
+ * out[2] = the reduced series of a flux-time monitor / the gathered array of a sparse field-time monitor / the accumulators of a
+ * sparse DFT monitor, nf x kept nodes x 8 B (which holds no records: out[1] = 0) (else 0),
  * out[3] = tables (phase tables; taps, weights, per-tile partial sums) */
 int fdtd_get_monitor_bytes(FdtdSolver* h, int monitor_id, int64_t out[4]);
 
@@ -408,8 +426,8 @@ enum { FDTD_OPT_FLAGS = 0 /* Not switched between runs by any test. */, FDTD_OPT
                                     another launch bound than their own, not a setting for production runs).  May be switched between runs of one engine (A/B inside one placement of the arrays). (tests/test_emu_seam_defer.py switches it.) */
        FDTD_OPT_AXIS_SHIFT = 28, /* 0 (default), 1, 2: the caller laid the problem out with its axes cyclically renamed — device axis a holds the
                                     caller's axis (a + s) % 3.  The solve does not depend on it; what is formed axis after axis in a fixed order
-                                    does: the passes of a sparse field-time monitor's gather (fdtd_add_field_time_monitor) then run along the
-                                    caller's x, y, z, so that the renamed problem gives the bits of the plain one. (tests/test_emu_field_time.py runs all three.) */
+                                    does: the passes of a sparse field-time monitor's gather (fdtd_add_field_time_monitor) and of a sparse DFT
+                                    monitor's colocation (fdtd_add_field_dft_monitor) then run along the caller's x, y, z, so that the renamed problem gives the bits of the plain one. (tests/test_emu_field_time.py runs all three.) */
        FDTD_OPT_LDS_PAD = 10 /* measuring aid: extra dynamic LDS per workgroup of the sweep in bytes (lowers its occupancy). Not switched between runs by any test. */ };
 int fdtd_set_option(FdtdSolver* h, int key, int value);
 int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out);

@@ -24,6 +24,7 @@
 #include "fdtd_aniso.hpp"
 #include "fdtd_flux_time.hpp"
 #include "fdtd_field_time.hpp"
+#include "fdtd_field_dft.hpp"
 
 using namespace fdtd;
 
@@ -148,7 +149,14 @@ struct Monitor {
   size_t result_bytes = 0;         // what fdtd_get_monitor returns of a ring monitor: the series / the gathered array
   float* result() const { return flux ? fp.result : gp.out; }
   long long slot(size_t rec) const { return (long long)(ring ? rec % ring : rec); }
+  // FDTD_MON_DFT_SPARSE: kind stays FDTD_MON_DFT — every schedule treats the monitor as the DFT monitor of its padded box — but
+  // `data` holds float2 [nf][kept nodes]: field_dft_record_kernel colocates each sample onto the kept nodes (fdtd_field_dft.hpp)
+  bool dsparse = false;
+  FieldDftP dp{};
 };
+// what the schedules ask of a monitor: does it record like a running DFT over its box (E^n at the pre point, H^{n+1/2} at the post
+// point, the middle step of a pair from the sweep's dump)?  The whole-box DFT monitor and the sparse one alike.
+inline bool records_as_dft(const Monitor& m) { return m.kind == FDTD_MON_DFT; }
 
 // node table of one kind of step pair of the two-step sweep: the E-side source nodes and the nodes small time monitors
 // sample of the middle step (InjP), for one set of recording monitors
@@ -1020,10 +1028,10 @@ bool fused2_plan(const FdtdSolver* h, long long n, F2Plan* plan, const int* box_
     const bool inside = b.lo0 >= 0 && b.lo1 >= 0 && b.lo2 >= 0 && b.lo0 + b.nx <= h->g.nx && b.lo1 + b.ny <= h->g.ny && b.lo2 + b.nz <= h->g.nz;
     // (shell2 pairs: the shell's boxes copy the middle step out too — a DFT monitor may reach into the layers, as flux planes and mode
     //  monitors normally do; time monitors' samples come from the bulk sweep's node table only)
-    if (box_lo && !(dft_anywhere && m.kind == FDTD_MON_DFT) &&
+    if (box_lo && !(dft_anywhere && records_as_dft(m)) &&
         (b.lo0 < box_lo[0] || b.lo1 < box_lo[1] || b.lo2 < box_lo[2] || b.lo0 + b.nx > box_hi[0] ||
          b.lo1 + b.ny > box_hi[1] || b.lo2 + b.nz > box_hi[2])) return false;
-    if (m.kind == FDTD_MON_DFT) {
+    if (records_as_dft(m)) {
       // A DFT record at the FIRST step: E^n is taken in front of the sweep as always; its H terms need H^{n+1/2}.  A record at
       // the MIDDLE step: its E terms need E^{n+1}; its H terms, H^{n+3/2}, are in the write set afterwards.  The sweep copies
       // what is needed of the middle step out over the box (any size).
@@ -1840,6 +1848,22 @@ void ring_drain(FdtdSolver* h, hipStream_t st) {
   }
 }
 
+// One record launch of a sparse DFT monitor (fdtd_field_dft.hpp): the entries of `r` — component slots and the boxes they are read
+// from, the live fields or the sweep's dump — colocated onto the kept nodes and accumulated with the nf phases at `phase`.
+void launch_field_dft(FdtdSolver* h, const Monitor& m, const FieldDftSrc& r, const float2* phase, hipStream_t st) {
+  int nx = 1;
+  long long rows = 1;
+  for (int e = 0; e < r.n; ++e) {
+    nx = std::max(nx, m.dp.nt[r.slot[e]][0]);
+    rows = std::max(rows, (long long)m.dp.nt[r.slot[e]][1] * m.dp.nt[r.slot[e]][2]);
+  }
+  const unsigned gy = (unsigned)std::min<long long>((rows + kFieldTimeRows - 1) / kFieldTimeRows, kFieldTimeMaxRowBlocks);
+  const dim3 grid((unsigned)((nx + 63) / 64), gy, (unsigned)r.n), block(64, kFieldTimeRows);
+  if (h->axis_shift == 1) hipLaunchKernelGGL(field_dft_record_kernel<1>, grid, block, 0, st, m.dp, r, phase);
+  else if (h->axis_shift == 2) hipLaunchKernelGGL(field_dft_record_kernel<2>, grid, block, 0, st, m.dp, r, phase);
+  else hipLaunchKernelGGL(field_dft_record_kernel<0>, grid, block, 0, st, m.dp, r, phase);
+}
+
 // H-side source terms of step n act on H^{n-1/2} in place in FRONT of a pair's sweep: then the small time monitors of the pair take
 // E^n and their first H half-sample in front of those (record_monitors at the top of the step) and pair_record adds the rest.
 // Round 6: the H-side corrections of a TFSF box count too — since such boxes inject inside pairs (paged source terms) a probe on
@@ -1860,12 +1884,20 @@ void pair_record(FdtdSolver* h, const F2Table* tb, long long n, hipStream_t st) 
     Monitor& m = h->mons[(size_t)tb->dfts[q]];
     for (int pass = 0; pass < 2; ++pass) {
       if (m.next >= m.steps.size() || m.steps[m.next] != n + pass) continue;
-      DftDumpP r{};
-      for (size_t ic = 0; ic < m.comps.size(); ++ic)
-        if ((m.comps[ic] >= 3) == (pass == 0)) { r.slot[r.n] = (int)ic; r.off[r.n] = tb->dft_off[q][(size_t)m.comps[ic]]; r.n++; }
-      if (r.n > 0)
-        launch_dft_record_dump(st, r, h->dump_buf, reinterpret_cast<float2*>(m.data), m.cells, (long long)m.comps.size() * m.cells,
-                               (const float2*)((pass == 0 ? m.phase_h : m.phase_e) + (long long)m.next * m.nf), m.nf);
+      const float2* phase = (const float2*)((pass == 0 ? m.phase_h : m.phase_e) + (long long)m.next * m.nf);
+      if (m.dsparse) {                 // the dump holds the whole box of each component, contiguous
+        FieldDftSrc s{};
+        s.sy = m.box.nx; s.sz = (long long)m.box.nx * m.box.ny;
+        for (size_t ic = 0; ic < m.comps.size(); ++ic)
+          if ((m.comps[ic] >= 3) == (pass == 0)) { s.slot[s.n] = (int)ic; s.f[s.n] = h->dump_buf + tb->dft_off[q][(size_t)m.comps[ic]]; s.n++; }
+        if (s.n > 0) launch_field_dft(h, m, s, phase, st);
+      } else {
+        DftDumpP r{};
+        for (size_t ic = 0; ic < m.comps.size(); ++ic)
+          if ((m.comps[ic] >= 3) == (pass == 0)) { r.slot[r.n] = (int)ic; r.off[r.n] = tb->dft_off[q][(size_t)m.comps[ic]]; r.n++; }
+        if (r.n > 0)
+          launch_dft_record_dump(st, r, h->dump_buf, reinterpret_cast<float2*>(m.data), m.cells, (long long)m.comps.size() * m.cells, phase, m.nf);
+      }
       if (pass == 0) m.next++;
     }
   }
@@ -2884,6 +2916,14 @@ void record_monitors(FdtdSolver* h, long long n, bool post, hipStream_t st, cons
         if (m.ring && (size_t)rec - m.reduced >= m.ring) ring_drain(h, st);      // (a full ring: its complete records first)
         float* out = reinterpret_cast<float*>(m.data) + m.slot((size_t)rec) * nc * m.cells;
         hipLaunchKernelGGL(time_record_multi_kernel, grid, dim3(256), 0, st, r, h->g, m.box, out, (long long)m.cells);
+      } else if (m.dsparse) {          // the live fields at the box origin
+        FieldDftSrc s{};
+        s.n = r.n; s.sy = h->g.nx; s.sz = h->g.sxy;
+        for (int q = 0; q < r.n; ++q) {
+          s.slot[q] = r.slot[q];
+          s.f[q] = r.f[q] + (long long)m.box.lo2 * h->g.sxy + (long long)m.box.lo1 * h->g.nx + m.box.lo0;
+        }
+        launch_field_dft(h, m, s, (const float2*)((post ? m.phase_h : m.phase_e) + rec * m.nf), st);
       } else {
         const long long fstride = (long long)nc * m.cells;
         hipLaunchKernelGGL(dft_record_multi_kernel, grid, dim3(256), 0, st, r, h->g, m.box,
@@ -3417,6 +3457,7 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
   if (!h) return -1;
   if (kind == FDTD_MON_FLUX_TIME) return fail(h, "fdtd_add_monitor: FDTD_MON_FLUX_TIME monitors are added by fdtd_add_flux_time_monitor");
   if (kind == FDTD_MON_TIME_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_TIME_SPARSE monitors are added by fdtd_add_field_time_monitor");
+  if (kind == FDTD_MON_DFT_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_DFT_SPARSE monitors are added by fdtd_add_field_dft_monitor");
   if (kind != FDTD_MON_TIME && kind != FDTD_MON_DFT) return fail(h, "fdtd_add_monitor: bad kind %d", kind);
   const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
   for (int a = 0; a < 3; ++a)
@@ -3470,6 +3511,35 @@ int ring_setup(FdtdSolver* h, Monitor& m, int64_t staging_bytes) {
   float* stage = nullptr;
   if (dev_alloc(h, &stage, m.ring * rec_floats)) return -1;
   m.data = stage;
+  return 0;
+}
+// The tap tables of a sparse monitor (`who` = the entry point, for messages): component after component and inside a component
+// axis after axis [n_targets][2] taps into a box of `ext` cells.  Every tap that is read (weight != 0) must lie inside the box; no
+// weight may be NaN.  Fills where each component's tables start, its node counts, where it starts inside a record and the totals.
+int tap_tables(FdtdSolver* h, const char* who, int n_comps, const int32_t* comps, const int ext[3], const int32_t* n_targets,
+               const int32_t* tap_index, const float* tap_weight, int off[6][3], int nt_out[6][3], long long out_off[6],
+               long long* rec_nodes, size_t* n_taps_out) {
+  size_t n_taps = 0;
+  *rec_nodes = 0;
+  for (int c = 0; c < n_comps; ++c) {
+    long long nodes = 1;
+    for (int a = 0; a < 3; ++a) {
+      const int nt = n_targets[3 * c + a];
+      if (nt < 1 || nt > (1 << 24)) return fail(h, "%s: %d nodes of component %d along axis %d", who, nt, comps[c], a);
+      off[c][a] = (int)n_taps; nt_out[c][a] = nt;
+      for (size_t t = 0; t < (size_t)2 * nt; ++t) {
+        const float w = tap_weight[n_taps + t];
+        if (!(w == w) || (w != 0.0f && (tap_index[n_taps + t] < 0 || tap_index[n_taps + t] >= ext[a])))
+          return fail(h, "%s: tap %zu of component %d, axis %d (index %d, weight %g) outside the box of %d cells", who, t, comps[c], a,
+                      tap_index[n_taps + t], (double)w, ext[a]);
+      }
+      n_taps += (size_t)2 * nt;
+      nodes *= nt;
+    }
+    out_off[c] = *rec_nodes;
+    *rec_nodes += nodes;
+  }
+  *n_taps_out = n_taps;
   return 0;
 }
 }  // namespace
@@ -3559,24 +3629,8 @@ int fdtd_add_field_time_monitor(FdtdSolver* h, int n_comps, const int32_t* comps
   const int ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
   FieldTimeP p{};
   size_t n_taps = 0;
-  for (int c = 0; c < n_comps; ++c) {
-    long long nodes = 1;
-    for (int a = 0; a < 3; ++a) {
-      const int nt = n_targets[3 * c + a];
-      if (nt < 1 || nt > (1 << 24)) return fail(h, "fdtd_add_field_time_monitor: %d nodes of component %d along axis %d", nt, comps[c], a);
-      p.off[c][a] = (int)n_taps; p.nt[c][a] = nt;
-      for (size_t t = 0; t < (size_t)2 * nt; ++t) {
-        const float w = tap_weight[n_taps + t];
-        if (!(w == w) || (w != 0.0f && (tap_index[n_taps + t] < 0 || tap_index[n_taps + t] >= ext[a])))
-          return fail(h, "fdtd_add_field_time_monitor: tap %zu of component %d, axis %d (index %d, weight %g) outside the box of %d cells", t, comps[c], a,
-                      tap_index[n_taps + t], (double)w, ext[a]);
-      }
-      n_taps += (size_t)2 * nt;
-      nodes *= nt;
-    }
-    p.out_off[c] = p.rec_nodes;
-    p.rec_nodes += nodes;
-  }
+  if (tap_tables(h, "fdtd_add_field_time_monitor", n_comps, comps, ext, n_targets, tap_index, tap_weight, p.off, p.nt, p.out_off, &p.rec_nodes, &n_taps))
+    return -1;
   HIPCHK(h, hipSetDevice(h->cfg.device));
   const int64_t bytes_before = h->stats.device_bytes;
   Monitor m;
@@ -3606,13 +3660,64 @@ int fdtd_add_field_time_monitor(FdtdSolver* h, int n_comps, const int32_t* comps
   return (int)h->mons.size() - 1;
 }
 
+int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
+                               int64_t n_rec, const int64_t* steps, const int32_t* n_targets, const int32_t* tap_index,
+                               const float* tap_weight, int nf, const float* phase_e, const float* phase_h) {
+  if (!h) return -1;
+  if (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR)
+    return fail(h, "fdtd_add_field_dft_monitor: not available on z-slab handles (the box would be cut between ranks)");
+  if (n_comps < 1 || n_comps > 6) return fail(h, "fdtd_add_field_dft_monitor: n_comps must be 1..6");
+  if (!comps || !lo || !hi || !n_targets || !tap_index || !tap_weight || n_rec < 0 || (n_rec && (!steps || !phase_e || !phase_h)))
+    return fail(h, "fdtd_add_field_dft_monitor: bad argument");
+  if (nf < 1) return fail(h, "fdtd_add_field_dft_monitor: a DFT monitor needs frequencies");
+  for (int c = 0; c < n_comps; ++c) if (comps[c] < 0 || comps[c] > 5) return fail(h, "fdtd_add_field_dft_monitor: bad component %d", comps[c]);
+  const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
+  for (int a = 0; a < 3; ++a)
+    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "fdtd_add_field_dft_monitor: box [%d,%d) outside axis %d of %d cells", lo[a], hi[a], a, N[a]);
+  const int ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+  FieldDftP p{};
+  size_t n_taps = 0;
+  if (tap_tables(h, "fdtd_add_field_dft_monitor", n_comps, comps, ext, n_targets, tap_index, tap_weight, p.off, p.nt, p.out_off, &p.nodes, &n_taps))
+    return -1;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  const int64_t bytes_before = h->stats.device_bytes;
+  Monitor m;
+  m.kind = FDTD_MON_DFT;
+  m.dsparse = true;
+  m.comps.assign(comps, comps + n_comps);
+  m.box.lo0 = lo[0]; m.box.lo1 = lo[1]; m.box.lo2 = lo[2];
+  m.box.nx = ext[0]; m.box.ny = ext[1]; m.box.nz = ext[2];
+  m.cells = (long long)ext[0] * ext[1] * ext[2];
+  m.steps.assign(steps, steps + n_rec);
+  for (size_t i = 1; i < m.steps.size(); ++i)
+    if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_field_dft_monitor: steps must be strictly increasing");
+  // added between runs: the steps already done are skipped — the monitor accumulates from now on — until fdtd_reset
+  while (m.next < m.steps.size() && m.steps[m.next] < h->step) ++m.next;
+  m.nf = nf;
+  // (like fdtd_add_monitor: what a failure below has allocated stays with the handle until fdtd_destroy)
+  m.data_bytes = (size_t)nf * (size_t)p.nodes * sizeof(float2);
+  float2* acc = nullptr;
+  if (dev_alloc(h, &acc, (size_t)nf * (size_t)p.nodes)) return -1;
+  m.data = acc;
+  int* di = nullptr; float* dw = nullptr;
+  if (dev_upload(h, &di, (const int*)tap_index, n_taps) || dev_upload(h, &dw, tap_weight, n_taps)) return -1;
+  if (dev_upload(h, &m.phase_e, reinterpret_cast<const float2*>(phase_e), (size_t)n_rec * nf) ||
+      dev_upload(h, &m.phase_h, reinterpret_cast<const float2*>(phase_h), (size_t)n_rec * nf))
+    return -1;
+  p.acc = acc; p.idx = di; p.w = dw; p.nf = nf;
+  m.dp = p;
+  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
+  h->mons.push_back(m);
+  return (int)h->mons.size() - 1;
+}
+
 int fdtd_get_monitor_bytes(FdtdSolver* h, int id, int64_t out[4]) {
   if (!h) return -1;
   if (id < 0 || id >= (int)h->mons.size() || !out) return fail(h, "fdtd_get_monitor_bytes: bad id %d", id);
   const Monitor& m = h->mons[id];
   out[0] = (int64_t)m.dev_bytes;
-  out[1] = (int64_t)m.data_bytes;
-  out[2] = m.ring ? (int64_t)(m.dev_bytes - m.data_bytes - m.aux_bytes) : 0;
+  out[1] = m.dsparse ? 0 : (int64_t)m.data_bytes;          // (a sparse DFT monitor holds no records: its accumulators are its result)
+  out[2] = m.ring ? (int64_t)(m.dev_bytes - m.data_bytes - m.aux_bytes) : (m.dsparse ? (int64_t)m.data_bytes : 0);
   out[3] = m.ring ? (int64_t)m.aux_bytes : (int64_t)(m.dev_bytes - m.data_bytes);
   return 0;
 }
@@ -3691,7 +3796,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   HIPCHK(h, hipSetDevice(h->cfg.device));
   ncclUniqueId u;
   std::memcpy(&u, id, 128);
-  for (const Monitor& m : h->mons) if (m.ring) return fail(h, "fdtd_comm_init: flux-time and sparse field-time monitors are not available on z-slab handles");
+  for (const Monitor& m : h->mons) if (m.ring || m.dsparse) return fail(h, "fdtd_comm_init: flux-time, sparse field-time and sparse DFT monitors are not available on z-slab handles");
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)
@@ -3753,7 +3858,7 @@ extern "C" {
 int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user) {
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  if (h->comm) for (const Monitor& m : h->mons) if (m.ring) return fail(h, "fdtd_run: flux-time and sparse field-time monitors are not available on z-slab handles");
+  if (h->comm) for (const Monitor& m : h->mons) if (m.ring || m.dsparse) return fail(h, "fdtd_run: flux-time, sparse field-time and sparse DFT monitors are not available on z-slab handles");
   Run r{h, n_steps, progress, user};
   if (r.setup() || r.setup_schedules() || r.setup_pairs()) return -1;
   if (r.loop()) { flush_seams(h, h->stream); return -1; }      // (an error leaves no stale seam columns either)
@@ -3770,7 +3875,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
                    FdtdProgressFn progress, void* user) {
   if (!hr || !hi) return -1;
   for (const FdtdSolver* hh : {hr, hi})
-    for (const Monitor& m : hh->mons) if (m.ring) return fail(hr, "fdtd_run_bloch: flux-time and sparse field-time monitors (fdtd_add_flux_time_monitor, fdtd_add_field_time_monitor) are not available with Bloch boundaries (complex fields)");
+    for (const Monitor& m : hh->mons) if (m.ring || m.dsparse) return fail(hr, "fdtd_run_bloch: flux-time, sparse field-time and sparse DFT monitors (fdtd_add_flux_time_monitor, fdtd_add_field_time_monitor, fdtd_add_field_dft_monitor) are not available with Bloch boundaries (complex fields)");
   if (hi->comm) return fail(hr, "fdtd_run_bloch: the communicator of a z-slab belongs to the first (real-part) handle");
   // fully anisotropic bodies: the Re handle's lists (wrap codes included) drive both parts; the Im handle's carry the same rows
   const bool aniso = !hr->aniso.empty();

@@ -35,13 +35,53 @@ struct FieldTimeP {
   int cnt;
 };
 
+// The value on one kept node: sum over the 2 x 2 x 2 taps of wx wy wz f[jz * sz + jy * sy + jx] — `f` a box of one component with
+// unit stride along x — formed separably along the caller's x, then y, then z (S as below), fp32; what lies under a zero weight is
+// not read.  Shared with field_dft_record_kernel (fdtd_field_dft.hpp): one set of operations for both.
+template <int S>
+__device__ __forceinline__ float colocate_taps(const float* f, long long sy, long long sz, const int (&j)[3][2], const float (&w)[3][2]) {
+  constexpr int A0 = (3 - S) % 3, A1 = (4 - S) % 3, A2 = (5 - S) % 3;
+  float v[2][2][2];                                            // [z tap][y tap][x tap]
+#pragma unroll
+  for (int cz = 0; cz < 2; ++cz)
+#pragma unroll
+    for (int cy = 0; cy < 2; ++cy)
+#pragma unroll
+      for (int cx = 0; cx < 2; ++cx)
+        v[cz][cy][cx] = (w[2][cz] != 0.0f && w[1][cy] != 0.0f && w[0][cx] != 0.0f) ? f[(long long)j[2][cz] * sz + (long long)j[1][cy] * sy + j[0][cx]] : 0.0f;
+  float t1[2][2], t2[2];                                       // after the first pass [tap along A2][tap along A1], after the second [tap along A2]
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2) {
+#pragma unroll
+    for (int c1 = 0; c1 < 2; ++c1) {
+      float s = 0.0f;
+#pragma unroll
+      for (int c0 = 0; c0 < 2; ++c0) {
+        int t[3];
+        t[A0] = c0; t[A1] = c1; t[A2] = c2;
+        if (w[A0][c0] != 0.0f) s = s + w[A0][c0] * v[t[2]][t[1]][t[0]];
+      }
+      t1[c2][c1] = s;
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int c1 = 0; c1 < 2; ++c1)
+      if (w[A1][c1] != 0.0f) s = s + w[A1][c1] * t1[c2][c1];
+    t2[c2] = s;
+  }
+  float s = 0.0f;
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2)
+    if (w[A2][c2] != 0.0f) s = s + w[A2][c2] * t2[c2];
+  return s;
+}
+
 // blockIdx.x = piece of 64 nodes along x, blockIdx.y (strided) = group of kFieldTimeRows rows, blockIdx.z = record of the launch x component.
 // S = the cyclic renaming the caller laid the problem out with (FDTD_OPT_AXIS_SHIFT: device axis a holds the caller's axis (a + S) % 3):
 // the three passes run along the caller's x, y, z — device axes (3 - S) % 3, (4 - S) % 3, (5 - S) % 3 — so that a renamed problem
 // gives the bits of the plain one.
 template <int S>
 __global__ __launch_bounds__(64 * kFieldTimeRows) void field_time_gather_kernel(FieldTimeP p) {
-  constexpr int A0 = (3 - S) % 3, A1 = (4 - S) % 3, A2 = (5 - S) % 3;
   const int c = (int)(blockIdx.z % (unsigned)p.n_comps), q = (int)(blockIdx.z / (unsigned)p.n_comps);
   if (q >= p.cnt) return;
   const int n0 = p.nt[c][0], n1 = p.nt[c][1], n2 = p.nt[c][2];
@@ -65,39 +105,7 @@ __global__ __launch_bounds__(64 * kFieldTimeRows) void field_time_gather_kernel(
       j[1][t] = p.idx[p.off[c][1] + 2 * q1 + t]; w[1][t] = p.w[p.off[c][1] + 2 * q1 + t];
       j[2][t] = p.idx[p.off[c][2] + 2 * q2 + t]; w[2][t] = p.w[p.off[c][2] + 2 * q2 + t];
     }
-    float v[2][2][2];                                          // [z tap][y tap][x tap]; what lies under a zero weight is not read
-#pragma unroll
-    for (int cz = 0; cz < 2; ++cz)
-#pragma unroll
-      for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-        for (int cx = 0; cx < 2; ++cx)
-          v[cz][cy][cx] = (w[2][cz] != 0.0f && w[1][cy] != 0.0f && w[0][cx] != 0.0f) ? f[((long long)j[2][cz] * by + j[1][cy]) * bx + j[0][cx]] : 0.0f;
-    float t1[2][2], t2[2];                                     // after the first pass [tap along A2][tap along A1], after the second [tap along A2]
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
-#pragma unroll
-      for (int c1 = 0; c1 < 2; ++c1) {
-        float s = 0.0f;
-#pragma unroll
-        for (int c0 = 0; c0 < 2; ++c0) {
-          int t[3];
-          t[A0] = c0; t[A1] = c1; t[A2] = c2;
-          if (w[A0][c0] != 0.0f) s = s + w[A0][c0] * v[t[2]][t[1]][t[0]];
-        }
-        t1[c2][c1] = s;
-      }
-      float s = 0.0f;
-#pragma unroll
-      for (int c1 = 0; c1 < 2; ++c1)
-        if (w[A1][c1] != 0.0f) s = s + w[A1][c1] * t1[c2][c1];
-      t2[c2] = s;
-    }
-    float s = 0.0f;
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2)
-      if (w[A2][c2] != 0.0f) s = s + w[A2][c2] * t2[c2];
-    o[row * n0 + x] = s;
+    o[row * n0 + x] = colocate_taps<S>(f, (long long)bx, (long long)bx * by, j, w);
   }
 }
 

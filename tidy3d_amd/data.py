@@ -490,7 +490,7 @@ def _field_container(cls, mon, spec: SolverSpec, fp: FieldPlan, raw: np.ndarray,
                      lead_coords: np.ndarray, sim_center, dtype, full=None):
     """``full`` = (FieldPlan on the full grid, full-grid spec, symmetry) when the solver ran on the
     symmetry-reduced domain.  A two-dimensional ``raw`` [lead, kept nodes of all fields] is what the device has gathered onto the
-    target coordinates already (MonitorSpec kind "time_sparse"): nothing is interpolated here."""
+    target coordinates already (MonitorSpec kinds "time_sparse", "dft_sparse"): nothing is interpolated here."""
     kw = {}
     off = 0
     for ic, fname in enumerate(fp.fields):

@@ -15,7 +15,7 @@ import numpy as np
 from . import lib as L
 from .coeffs import damping_tables, h_coeff, inv_steps, material_table, pml_axis
 from .exceptions import SetupError, SolverLibraryError
-from .spec import BC_PERIODIC, MonitorSpec, SolverSpec
+from .spec import BC_PERIODIC, SPARSE_KINDS, MonitorSpec, SolverSpec
 
 
 def _f32(a) -> np.ndarray:
@@ -221,8 +221,8 @@ def permute_spec(spec: SolverSpec, s: int) -> SolverSpec:
     # flux-time surfaces: the normal and the per-axis tables are renamed with the axes (their components stay in cyclic order)
     monitors = [m if m.kind != "flux_time" else dataclasses.replace(m, axis=inv[m.axis], taps=pick(m.taps), weights=pick(m.weights))
                 for m in monitors]
-    # sparse field-time monitors: every component's per-axis tables (hence its kept-node counts) are renamed with the axes
-    monitors = [m if m.kind != "time_sparse" else dataclasses.replace(m, taps=tuple(pick(t) for t in m.taps)) for m in monitors]
+    # sparse field-time and sparse DFT monitors: every component's per-axis tables (hence its kept-node counts) are renamed with the axes
+    monitors = [m if m.kind not in SPARSE_KINDS else dataclasses.replace(m, taps=tuple(pick(t) for t in m.taps)) for m in monitors]
     return dataclasses.replace(
         spec, shape=pick(spec.shape), boundaries=pick(spec.boundaries), bc=pick(spec.bc), pml=pick(spec.pml),
         mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors,
@@ -618,7 +618,8 @@ class HipEngine:
         """Add ``monitors`` (MonitorSpecs on the device's axes and index layout, as ``self.spec.monitors`` are) to the handle — at
         set-up, or between runs.  Between runs a time or DFT monitor's first record step must lie behind the steps done (the
         library waits for its first step for ever otherwise); a flux-time or sparse field-time monitor skips the steps already
-        done — their entries of the result stay zero — and records the rest: the tail of the series of a monitor present from the start."""
+        done — their entries of the result stay zero — and records the rest: the tail of the series of a monitor present from the
+        start; a sparse DFT monitor skips them too and accumulates from then on."""
         d, h, spec = self.lib.dll, self.handle, self.spec
         z0, z1, nz = self.z0, self.z1, spec.shape[2]
         uz = (2 - self.axis_shift) % 3            # the device axis that holds the user's z
@@ -646,16 +647,23 @@ class HipEngine:
                 self._chk(mid, "fdtd_add_flux_time_monitor")
                 self.mon_ids.append((m, mid, (lo2, hi2)))
                 continue
-            if m.kind == "time_sparse":
+            if m.kind in SPARSE_KINDS:
                 if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz) or spec.bloch is not None:
-                    raise SolverLibraryError(f"monitor '{m.name}': a FieldTimeMonitor gathered on the device is not available on z-slabs "
+                    what = "FieldTimeMonitor gathered" if m.kind == "time_sparse" else "FieldMonitor accumulated"
+                    raise SolverLibraryError(f"monitor '{m.name}': a {what} on the device is not available on z-slabs "
                                              "(more than one GPU, force_comm) or with Bloch boundaries")
                 n_t = np.asarray(m.targets, dtype=np.int32)
                 tidx = np.ascontiguousarray(np.concatenate([np.asarray(t[a][0], dtype=np.int32).ravel() for t in m.taps for a in range(3)]))
                 tw = _f32(np.concatenate([np.asarray(t[a][1], dtype=np.float64).ravel() for t in m.taps for a in range(3)]))
-                mid = d.fdtd_add_field_time_monitor(h, len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t),
-                                                    _ptr(tidx), _ptr(tw), int(m.staging_bytes))
-                self._chk(mid, "fdtd_add_field_time_monitor")
+                if m.kind == "time_sparse":
+                    mid = d.fdtd_add_field_time_monitor(h, len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t),
+                                                        _ptr(tidx), _ptr(tw), int(m.staging_bytes))
+                    self._chk(mid, "fdtd_add_field_time_monitor")
+                else:
+                    pe, ph = _cplx_f32(m.phase_e), _cplx_f32(m.phase_h)
+                    mid = d.fdtd_add_field_dft_monitor(h, len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t),
+                                                       _ptr(tidx), _ptr(tw), len(m.freqs), _ptr(pe), _ptr(ph))
+                    self._chk(mid, "fdtd_add_field_dft_monitor")
                 self.mon_ids.append((m, mid, (lo2, hi2)))
                 continue
             if m.kind == "dft":
@@ -777,7 +785,8 @@ class HipEngine:
     def monitor_data(self) -> Dict[str, Tuple[np.ndarray, Tuple[int, int]]]:
         """name -> (array over the slab-local part of the box, (z_lo, z_hi) global plane range).
         time: float32 [n_rec, n_comps, bz, by, bx]; dft: complex64 [nf, n_comps, bz, by, bx]; flux_time: float32 [n_rec];
-        time_sparse: float32 [n_rec, kept nodes of all components] (each component [nz_t, ny_t, nx_t], on the user's axes)."""
+        time_sparse: float32 [n_rec, kept nodes of all components] (each component [nz_t, ny_t, nx_t], on the user's axes);
+        dft_sparse: complex64 [nf, kept nodes of all components], laid out likewise."""
         out = {}
         for m, mid, (lo2, hi2) in self.mon_ids:
             if mid < 0:
@@ -787,13 +796,15 @@ class HipEngine:
                 arr = np.empty(len(m.steps), dtype=np.float32)
             elif m.kind == "time_sparse":
                 arr = np.empty((len(m.steps), sum(int(np.prod(t)) for t in m.targets)), dtype=np.float32)
+            elif m.kind == "dft_sparse":
+                arr = np.empty((len(m.freqs), sum(int(np.prod(t)) for t in m.targets)), dtype=np.complex64)
             elif m.kind == "dft":
                 arr = np.empty((len(m.freqs), len(m.comps), bz, by, bx), dtype=np.complex64)
             else:
                 arr = np.empty((len(m.steps), len(m.comps), bz, by, bx), dtype=np.float32)
             self._chk(self.lib.dll.fdtd_get_monitor(self.handle, mid, _ptr(arr), arr.nbytes),
                       "fdtd_get_monitor")
-            if m.kind == "time_sparse" and self.axis_shift:        # every component back to the user's axes
+            if m.kind in SPARSE_KINDS and self.axis_shift:          # every component back to the user's axes
                 parts, off = [], 0
                 for nx, ny, nz_t in m.targets:
                     blk = arr[:, off:off + nx * ny * nz_t].reshape(len(arr), nz_t, ny, nx)
@@ -812,7 +823,8 @@ class HipEngine:
 
     def monitor_bytes(self, name: str, detail: bool = False):
         """Device memory, as allocated, of the monitor ``name`` (all surfaces ``name::*`` of a flux monitor): bytes, or with ``detail``
-        a dict total / records (time and DFT buffers, the staging ring of a flux-time surface) / series (reduced flux) / tables."""
+        a dict total / records (time and DFT buffers, the staging ring of a flux-time surface) / series (reduced flux, gathered
+        field-time nodes, the accumulators of a sparse DFT monitor) / tables."""
         tot = np.zeros(4, dtype=np.int64)
         hit = False
         for m, mid, _ in self.mon_ids:

@@ -136,6 +136,10 @@ class TfsfSpec:
     name: str = ""
 
 
+# MonitorSpec kinds whose result holds the kept nodes only, interpolated on the device by per-component ``taps``
+SPARSE_KINDS = ("time_sparse", "dft_sparse")
+
+
 @dataclass
 class MonitorSpec:
     """A recorder over a raw Yee index box [lo, hi) (same box for every component).
@@ -152,7 +156,11 @@ class MonitorSpec:
                  (csrc/fdtd_field_time.hpp): float32 [n_rec, sum over ``comps`` of the component's kept nodes], inside a record the
                  components one after the other, each [nz_t][ny_t][nx_t].  Every value is the separable linear interpolation ``taps``
                  describe from the raw box [lo, hi): the colocated, downsampled primal nodes (colocate=True) or the downsampled Yee
-                 nodes of the component (colocate=False; the node counts then differ between components)."""
+                 nodes of the component (colocate=False; the node counts then differ between components).
+    kind "dft_sparse": a running DFT accumulated on the nodes the user keeps only (csrc/fdtd_field_dft.hpp): complex64 [nf, sum over
+                 ``comps`` of the component's kept nodes], inside a frequency the components one after the other, each
+                 [nz_t][ny_t][nx_t].  Recorded like kind "dft" (``freqs``, ``phase_e``, ``phase_h``); every sample is interpolated onto
+                 the kept nodes by ``taps`` (as kind "time_sparse") before it is accumulated."""
 
     kind: str
     comps: Tuple[int, ...]
@@ -171,13 +179,13 @@ class MonitorSpec:
     axis: Optional[int] = None                          # normal of the surface
     sign: float = 1.0                                   # its orientation
     taps: Optional[Tuple] = None                        # per axis (index int32 [4, n_t, 2], weight float64 [4, n_t, 2]) into the box, components as ``comps``
-    #                                                     kind "time_sparse": per component of ``comps``, per axis (index int32 [n_t, 2], weight float64 [n_t, 2])
+    #                                                     kinds "time_sparse", "dft_sparse": per component of ``comps``, per axis (index int32 [n_t, 2], weight float64 [n_t, 2])
     weights: Optional[Tuple] = None                     # per axis float64 [n_t] integration weights ([1.] along the normal)
     staging_bytes: int = 0                              # device staging budget (0: the library's default)
 
     @property
     def targets(self) -> Tuple[Tuple[int, int, int], ...]:
-        """kind "time_sparse": (nx_t, ny_t, nz_t) kept nodes of every component."""
+        """kinds "time_sparse", "dft_sparse": (nx_t, ny_t, nz_t) kept nodes of every component."""
         return tuple(tuple(int(len(t[a][0])) for a in range(3)) for t in self.taps)
 
     @property

@@ -95,7 +95,7 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         *, device: int = 0, n_steps: Optional[int] = None, lib=None,
         return_tidy3d: Optional[bool] = None, devices=None, _dist_options: Optional[dict] = None,
         mode_grid_dispersion: Optional[bool] = None, flux_time_device: Optional[bool] = None,
-        field_time_device: Optional[bool] = None) -> SimulationData:
+        field_time_device: Optional[bool] = None, field_dft_device: Optional[bool] = None) -> SimulationData:
     """Solve ``simulation`` on the local MI355X and return its ``SimulationData``.
 
     Cloud-only arguments (``folder_name``, ``callback_url``, ``progress_callback_*``,
@@ -111,15 +111,19 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     records would take (None, ``discretize.FLUX_TIME_HOST_BYTES``; one-GPU runs without symmetry or Bloch boundaries).
     ``field_time_device``: colocate and downsample (``interval_space``) ``FieldTimeMonitor`` records on the device (True), on the host
     from records of the whole box (False), or per monitor (None: on the device where those records would exceed the same
-    threshold and fewer nodes are kept than the box holds; the same kinds of run)."""
+    threshold and fewer nodes are kept than the box holds; the same kinds of run).  ``field_dft_device``: the same three values for
+    ``FieldMonitor`` — accumulate its running DFT on the kept nodes only, on the device (True), over the whole box with colocation
+    and ``interval_space`` on the host (False), or per monitor (None: on the device where the whole box's accumulators would
+    exceed the threshold and fewer nodes are kept)."""
     from .engine import HipEngine
 
     sim, was_tidy3d = _as_mirror(simulation)
     sim.validate_pre_upload(source_required=True)
     if devices is not None and len(devices) > 1:
-        from .discretize import _field_time_refusal, _flux_time_refusal
+        from .discretize import _field_dft_refusal, _field_time_refusal, _flux_time_refusal
         _flux_time_refusal(sim, flux_time_device, "devices= with more than one GPU")
         _field_time_refusal(sim, field_time_device, "devices= with more than one GPU")
+        _field_dft_refusal(sim, field_dft_device, "devices= with more than one GPU")
         sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose, _dist_options or {})
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
         if want_td:
@@ -135,7 +139,7 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         device = int(devices[0])
     t_setup = time.perf_counter()
     disc = discretize(sim, n_steps=n_steps, mode_grid_dispersion=mode_grid_dispersion, flux_time_device=flux_time_device,
-                      field_time_device=field_time_device)
+                      field_time_device=field_time_device, field_dft_device=field_dft_device)
     spec = disc.spec
     lines = [f"Simulation domain Nx, Ny, Nz: {list(spec.shape)}",
              f"Applied symmetries: {tuple(sim.symmetry)}",
@@ -167,9 +171,11 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
             lines.append("WARNING: field divergence detected, exiting solver.")
         on_device = sorted({m.name.split("::")[0] for m in spec.monitors if m.kind == "flux_time"})
         gathered = sorted(m.name for m in spec.monitors if m.kind == "time_sparse")
+        accumulated = sorted(m.name for m in spec.monitors if m.kind == "dft_sparse")
         lines.append(schedule_line(stats, spec.n_cells, solve_s)
                      + (f" FluxTimeMonitor reduced on the device: {', '.join(on_device)}." if on_device else "")
-                     + (f" FieldTimeMonitor gathered on the device: {', '.join(gathered)}." if gathered else ""))
+                     + (f" FieldTimeMonitor gathered on the device: {', '.join(gathered)}." if gathered else "")
+                     + (f" FieldMonitor accumulated on the device: {', '.join(accumulated)}." if accumulated else ""))
     lines += ["", f"Setup time (s):  {setup_s:.4f}", f"Solver time (s): {solve_s:.4f}",
               f"Time-stepping speed (cells/s): {spec.n_cells * steps_done / max(solve_s, 1e-9):.2e}"]
     sim_data = assemble(disc, raw, log="\n".join(lines), diverged=diverged, n_steps_run=steps_done, device_lib=used_lib, device=device)
