@@ -124,36 +124,38 @@ struct Tfsf {
   TfsfList e, h;
 };
 
+// what `data` holds and what becomes of it: records or accumulators of the whole box, read back as they are (fdtd_add_monitor); a
+// ring of records that ring_drain reduces to one flux value each (fdtd_flux_time.hpp) or gathers onto the kept nodes
+// (fdtd_field_time.hpp); DFT accumulators on the kept nodes alone (fdtd_field_dft.hpp)
+enum class MonForm { Whole, FluxRing, SparseRing, SparseDft };
+enum { kBytesTotal, kBytesRecords, kBytesResult, kBytesTables };      // the figures of fdtd_get_monitor_bytes
+
 struct Monitor {
-  int kind = 0;
+  int kind = 0;                    // FDTD_MON_TIME / FDTD_MON_DFT: how every schedule treats the monitor, whatever its form
+  MonForm form = MonForm::Whole;
   std::vector<int> comps;
   BoxP box{};
   std::vector<long long> steps;
   size_t next = 0;                 // next entry of `steps` to record
   int nf = 0;
   float2 *phase_e = nullptr, *phase_h = nullptr;   // [n_rec][nf]
-  void* data = nullptr;
-  size_t data_bytes = 0;
+  void* data = nullptr;            // Whole: [n_rec][comps][box] floats / [nf][comps][box] float2; rings: `ring` records (slot = record
+  size_t data_bytes = 0;           // index mod ring); SparseDft: float2 [nf][kept nodes]
   long long cells = 0;
-  size_t dev_bytes = 0;            // device memory the monitor holds, tables included (fdtd_get_monitor_bytes)
-  // FDTD_MON_FLUX_TIME: kind stays FDTD_MON_TIME — every schedule treats the monitor as the time monitor of its box — and `data` is
-  // a ring of `ring` records (slot = record index mod ring) that ring_drain turns into result[n_rec] (fdtd_flux_time.hpp)
-  bool flux = false;
-  size_t ring = 0;                 // records the staging buffer holds (0: one slot per recorded step)
+  int64_t held[4] = {0, 0, 0, 0};  // device memory the monitor holds, by kBytes*: taken where it is allocated (took)
+  int64_t mark = 0;                // h->stats.device_bytes when the last of them was taken
+  size_t ring = 0;                 // records the staging buffer holds (0: no ring)
   size_t reduced = 0;              // records [0, reduced) are in `result`, their slots zero again
-  FluxMonP fp{};                   // addresses and shapes of its tables
-  size_t aux_bytes = 0;            // tap / weight tables and per-tile partial sums
-  // FDTD_MON_TIME_SPARSE: the same ring, all of `comps`; ring_drain gathers every complete record onto the kept nodes (fdtd_field_time.hpp)
-  bool sparse = false;
-  FieldTimeP gp{};
   size_t result_bytes = 0;         // what fdtd_get_monitor returns of a ring monitor: the series / the gathered array
-  float* result() const { return flux ? fp.result : gp.out; }
+  FluxMonP fp{};                   // FluxRing: addresses and shapes of its tables
+  FieldTimeP gp{};                 // SparseRing
+  FieldDftP dp{};                  // SparseDft
+  float* result() const { return form == MonForm::FluxRing ? fp.result : gp.out; }
   long long slot(size_t rec) const { return (long long)(ring ? rec % ring : rec); }
-  // FDTD_MON_DFT_SPARSE: kind stays FDTD_MON_DFT — every schedule treats the monitor as the DFT monitor of its padded box — but
-  // `data` holds float2 [nf][kept nodes]: field_dft_record_kernel colocates each sample onto the kept nodes (fdtd_field_dft.hpp)
-  bool dsparse = false;
-  FieldDftP dp{};
 };
+inline bool has_ring(const Monitor& m) { return m.form == MonForm::FluxRing || m.form == MonForm::SparseRing; }
+// the forms that read their whole box on one handle: not on z-slab handles, not with Bloch boundaries
+inline bool needs_whole_grid(const Monitor& m) { return m.form != MonForm::Whole; }
 // what the schedules ask of a monitor: does it record like a running DFT over its box (E^n at the pre point, H^{n+1/2} at the post
 // point, the middle step of a pair from the sweep's dump)?  The whole-box DFT monitor and the sparse one alike.
 inline bool records_as_dft(const Monitor& m) { return m.kind == FDTD_MON_DFT; }
@@ -371,6 +373,16 @@ int fail(FdtdSolver* h, const char* fmt, ...) {
   va_end(ap);
   if (h) h->err = buf; else g_create_error = buf;
   return -1;
+}
+
+// z-slab handles and Bloch pairs refuse the monitors of `h` that need their whole box on one handle (the error goes to `err`)
+int refuse_whole_grid_monitors(FdtdSolver* err, const FdtdSolver* h, const char* who, bool bloch = false) {
+  for (const Monitor& m : h->mons)
+    if (needs_whole_grid(m))
+      return fail(err, "%s: flux-time, sparse field-time and sparse DFT monitors%s", who,
+                  bloch ? " (fdtd_add_flux_time_monitor, fdtd_add_field_time_monitor, fdtd_add_field_dft_monitor) are not available with Bloch boundaries (complex fields)"
+                        : " are not available on z-slab handles");
+  return 0;
 }
 
 #define HIPCHK(h, call)                                                                   \
@@ -1798,6 +1810,20 @@ int shell2_why_not(const FdtdSolver* h, ShellGeom* G) {
 // records were written on, behind them: no other edge.
 // Flux-time monitors (fdtd_flux_time.hpp): one value of the series per record, all monitors in one launch (kFluxMaxJobs per launch).
 // Sparse field-time monitors (fdtd_field_time.hpp): the values on the kept nodes, one launch per monitor.
+// grid.x, grid.y of a launch over the kept nodes of the component slots `slot[0 .. n)` (for_each_kept_node), grid.z the caller's
+dim3 tap_grid(const TapTables& T, const int* slot, int n, unsigned gz) {
+  int nx = 1;
+  long long rows = 1;
+  for (int e = 0; e < n; ++e) {
+    nx = std::max(nx, T.nt[slot[e]][0]);
+    rows = std::max(rows, (long long)T.nt[slot[e]][1] * T.nt[slot[e]][2]);
+  }
+  return dim3((unsigned)((nx + 63) / 64), (unsigned)std::min<long long>((rows + kFieldTimeRows - 1) / kFieldTimeRows, kFieldTimeMaxRowBlocks), gz);
+}
+// launch K<S>, S = the handle's FDTD_OPT_AXIS_SHIFT, with the workgroup of for_each_kept_node
+#define LAUNCH_TAP_KERNEL(K, h, grid, st, ...) \
+  hipLaunchKernelGGL(((h)->axis_shift == 1 ? K<1> : (h)->axis_shift == 2 ? K<2> : K<0>), grid, dim3(64, kFieldTimeRows), 0, st, __VA_ARGS__)
+
 void ring_drain(FdtdSolver* h, hipStream_t st) {
   size_t q = 0;
   while (q < h->mons.size()) {
@@ -1805,7 +1831,7 @@ void ring_drain(FdtdSolver* h, hipStream_t st) {
     int tiles = 0, cnt = 0;
     for (; q < h->mons.size() && L.n < kFluxMaxJobs; ++q) {
       Monitor& m = h->mons[q];
-      if (!m.flux || m.reduced >= m.next) continue;
+      if (m.form != MonForm::FluxRing || m.reduced >= m.next) continue;
       FluxMonP& p = L.m[L.n++];
       p = m.fp;
       p.r0 = (long long)m.reduced;
@@ -1818,28 +1844,19 @@ void ring_drain(FdtdSolver* h, hipStream_t st) {
     hipLaunchKernelGGL(flux_time_final_kernel, dim3((cnt + 255) / 256, L.n), dim3(256), 0, st, L);
   }
   for (const Monitor& m : h->mons) {
-    if (!m.sparse || m.reduced >= m.next) continue;
+    if (m.form != MonForm::SparseRing || m.reduced >= m.next) continue;
     dbg_sync(h);
-    int nx = 1;
-    long long rows = 1;
-    for (size_t c = 0; c < m.comps.size(); ++c) {
-      nx = std::max(nx, m.gp.nt[c][0]);
-      rows = std::max(rows, (long long)m.gp.nt[c][1] * m.gp.nt[c][2]);
-    }
-    const unsigned gy = (unsigned)std::min<long long>((rows + kFieldTimeRows - 1) / kFieldTimeRows, kFieldTimeMaxRowBlocks);
+    static const int all_slots[6] = {0, 1, 2, 3, 4, 5};
     const size_t per_launch = (size_t)65535 / m.comps.size();          // (grid z: record x component)
     for (size_t r = m.reduced; r < m.next; r += per_launch) {
       FieldTimeP p = m.gp;
       p.r0 = (long long)r;
       p.cnt = (int)std::min(per_launch, m.next - r);
-      const dim3 grid((unsigned)((nx + 63) / 64), gy, (unsigned)(p.cnt * p.n_comps)), block(64, kFieldTimeRows);
-      if (h->axis_shift == 1) hipLaunchKernelGGL(field_time_gather_kernel<1>, grid, block, 0, st, p);
-      else if (h->axis_shift == 2) hipLaunchKernelGGL(field_time_gather_kernel<2>, grid, block, 0, st, p);
-      else hipLaunchKernelGGL(field_time_gather_kernel<0>, grid, block, 0, st, p);
+      LAUNCH_TAP_KERNEL(field_time_gather_kernel, h, tap_grid(p.t, all_slots, p.n_comps, (unsigned)(p.cnt * p.n_comps)), st, p);
     }
   }
   for (Monitor& m : h->mons) {
-    if (!m.ring || m.reduced >= m.next) continue;
+    if (!has_ring(m) || m.reduced >= m.next) continue;
     const size_t rec_bytes = m.comps.size() * (size_t)m.cells * sizeof(float);
     const size_t s0 = m.reduced % m.ring, cnt = m.next - m.reduced, first = std::min(cnt, m.ring - s0);
     hipMemsetAsync(reinterpret_cast<char*>(m.data) + s0 * rec_bytes, 0, first * rec_bytes, st);
@@ -1851,17 +1868,7 @@ void ring_drain(FdtdSolver* h, hipStream_t st) {
 // One record launch of a sparse DFT monitor (fdtd_field_dft.hpp): the entries of `r` — component slots and the boxes they are read
 // from, the live fields or the sweep's dump — colocated onto the kept nodes and accumulated with the nf phases at `phase`.
 void launch_field_dft(FdtdSolver* h, const Monitor& m, const FieldDftSrc& r, const float2* phase, hipStream_t st) {
-  int nx = 1;
-  long long rows = 1;
-  for (int e = 0; e < r.n; ++e) {
-    nx = std::max(nx, m.dp.nt[r.slot[e]][0]);
-    rows = std::max(rows, (long long)m.dp.nt[r.slot[e]][1] * m.dp.nt[r.slot[e]][2]);
-  }
-  const unsigned gy = (unsigned)std::min<long long>((rows + kFieldTimeRows - 1) / kFieldTimeRows, kFieldTimeMaxRowBlocks);
-  const dim3 grid((unsigned)((nx + 63) / 64), gy, (unsigned)r.n), block(64, kFieldTimeRows);
-  if (h->axis_shift == 1) hipLaunchKernelGGL(field_dft_record_kernel<1>, grid, block, 0, st, m.dp, r, phase);
-  else if (h->axis_shift == 2) hipLaunchKernelGGL(field_dft_record_kernel<2>, grid, block, 0, st, m.dp, r, phase);
-  else hipLaunchKernelGGL(field_dft_record_kernel<0>, grid, block, 0, st, m.dp, r, phase);
+  LAUNCH_TAP_KERNEL(field_dft_record_kernel, h, tap_grid(m.dp.t, r.slot, r.n, (unsigned)r.n), st, m.dp, r, phase);
 }
 
 // H-side source terms of step n act on H^{n-1/2} in place in FRONT of a pair's sweep: then the small time monitors of the pair take
@@ -1885,7 +1892,7 @@ void pair_record(FdtdSolver* h, const F2Table* tb, long long n, hipStream_t st) 
     for (int pass = 0; pass < 2; ++pass) {
       if (m.next >= m.steps.size() || m.steps[m.next] != n + pass) continue;
       const float2* phase = (const float2*)((pass == 0 ? m.phase_h : m.phase_e) + (long long)m.next * m.nf);
-      if (m.dsparse) {                 // the dump holds the whole box of each component, contiguous
+      if (m.form == MonForm::SparseDft) {      // the dump holds the whole box of each component, contiguous
         FieldDftSrc s{};
         s.sy = m.box.nx; s.sz = (long long)m.box.nx * m.box.ny;
         for (size_t ic = 0; ic < m.comps.size(); ++ic)
@@ -1907,7 +1914,7 @@ void pair_record(FdtdSolver* h, const F2Table* tb, long long n, hipStream_t st) 
   long long max_cells = 0;
   for (size_t q = 0; q < tb->mons.size(); ++q) {      // rings: room for the (at most two) records of this pair
     const Monitor& m = h->mons[(size_t)tb->mons[q]];
-    if (!m.ring) continue;
+    if (!has_ring(m)) continue;
     size_t last = m.next;
     if (last < m.steps.size() && m.steps[last] == n) ++last;
     if (last < m.steps.size() && m.steps[last] == n + 1) ++last;
@@ -2913,10 +2920,10 @@ void record_monitors(FdtdSolver* h, long long n, bool post, hipStream_t st, cons
     if (r.n > 0 && m.cells > 0) {
       const dim3 grid(nblk(m.cells), r.n);
       if (m.kind == FDTD_MON_TIME) {
-        if (m.ring && (size_t)rec - m.reduced >= m.ring) ring_drain(h, st);      // (a full ring: its complete records first)
+        if (has_ring(m) && (size_t)rec - m.reduced >= m.ring) ring_drain(h, st);      // (a full ring: its complete records first)
         float* out = reinterpret_cast<float*>(m.data) + m.slot((size_t)rec) * nc * m.cells;
         hipLaunchKernelGGL(time_record_multi_kernel, grid, dim3(256), 0, st, r, h->g, m.box, out, (long long)m.cells);
-      } else if (m.dsparse) {          // the live fields at the box origin
+      } else if (m.form == MonForm::SparseDft) {      // the live fields at the box origin
         FieldDftSrc s{};
         s.n = r.n; s.sy = h->g.nx; s.sz = h->g.sxy;
         for (int q = 0; q < r.n; ++q) {
@@ -3451,58 +3458,54 @@ int fdtd_add_tfsf(FdtdSolver* h, int n_aux, const float* ae, const float* be, co
   return 0;
 }
 
-int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps, const int32_t lo[3],
-                     const int32_t hi[3], int64_t n_rec, const int64_t* steps, int nf, const float* phase_e,
-                     const float* phase_h) {
-  if (!h) return -1;
-  if (kind == FDTD_MON_FLUX_TIME) return fail(h, "fdtd_add_monitor: FDTD_MON_FLUX_TIME monitors are added by fdtd_add_flux_time_monitor");
-  if (kind == FDTD_MON_TIME_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_TIME_SPARSE monitors are added by fdtd_add_field_time_monitor");
-  if (kind == FDTD_MON_DFT_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_DFT_SPARSE monitors are added by fdtd_add_field_dft_monitor");
-  if (kind != FDTD_MON_TIME && kind != FDTD_MON_DFT) return fail(h, "fdtd_add_monitor: bad kind %d", kind);
+}  // extern "C"
+namespace {
+// What every fdtd_add_*monitor starts with (`who` = the entry point, for messages): the checks of the handle (`cut` != nullptr:
+// the form needs its whole box on one handle, and a z-slab would cut that surface / box), of the components, the index box and
+// the steps; then `m`'s comps, box, cells and steps, the extents of the box, and the mark its device memory is counted from.
+int monitor_begin(FdtdSolver* h, const char* who, const char* cut, int n_comps, const int32_t* comps, const int32_t lo[3],
+                  const int32_t hi[3], int64_t n_rec, const int64_t* steps, Monitor* m, int ext[3]) {
+  if (cut && (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR))
+    return fail(h, "%s: not available on z-slab handles (the %s would be cut between ranks)", who, cut);
+  if (n_comps < 1 || n_comps > 6) return fail(h, "%s: n_comps must be 1..6", who);
+  if (!comps || !lo || !hi || n_rec < 0 || (n_rec && !steps)) return fail(h, "%s: bad argument", who);
+  for (int c = 0; c < n_comps; ++c) if (comps[c] < 0 || comps[c] > 5) return fail(h, "%s: bad component %d", who, comps[c]);
   const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
-  for (int a = 0; a < 3; ++a)
-    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "fdtd_add_monitor: box [%d,%d) outside axis %d of %d cells", lo[a], hi[a], a, N[a]);
-  if (n_comps < 1 || n_comps > 6) return fail(h, "fdtd_add_monitor: n_comps must be 1..6");
-  if (kind == FDTD_MON_DFT && nf < 1) return fail(h, "fdtd_add_monitor: a DFT monitor needs frequencies");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  const int64_t bytes_before = h->stats.device_bytes;
-  Monitor m;
-  m.kind = kind;
-  m.comps.assign(comps, comps + n_comps);
-  for (int c : m.comps) if (c < 0 || c > 5) return fail(h, "fdtd_add_monitor: bad component %d", c);
-  m.box.lo0 = lo[0]; m.box.lo1 = lo[1]; m.box.lo2 = lo[2];
-  m.box.nx = hi[0] - lo[0]; m.box.ny = hi[1] - lo[1]; m.box.nz = hi[2] - lo[2];
-  m.cells = (long long)m.box.nx * m.box.ny * m.box.nz;
-  m.steps.assign(steps, steps + n_rec);
-  for (size_t i = 1; i < m.steps.size(); ++i)
-    if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_monitor: steps must be strictly increasing");
-  m.nf = nf;
-  if (kind == FDTD_MON_TIME) {
-    m.data_bytes = (size_t)n_rec * n_comps * m.cells * sizeof(float);
-    float* d = nullptr;
-    if (dev_alloc(h, &d, (size_t)n_rec * n_comps * m.cells)) return -1;
-    m.data = d;
-  } else {
-    m.data_bytes = (size_t)nf * n_comps * m.cells * sizeof(float2);
-    float2* d = nullptr;
-    if (dev_alloc(h, &d, (size_t)nf * n_comps * m.cells)) return -1;
-    m.data = d;
-    if (dev_upload(h, &m.phase_e, reinterpret_cast<const float2*>(phase_e), (size_t)n_rec * nf) ||
-        dev_upload(h, &m.phase_h, reinterpret_cast<const float2*>(phase_h), (size_t)n_rec * nf))
-      return -1;
+  for (int a = 0; a < 3; ++a) {
+    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "%s: box [%d,%d) outside axis %d of %d cells", who, lo[a], hi[a], a, N[a]);
+    ext[a] = hi[a] - lo[a];
   }
-  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
+  m->comps.assign(comps, comps + n_comps);
+  m->box.lo0 = lo[0]; m->box.lo1 = lo[1]; m->box.lo2 = lo[2];
+  m->box.nx = ext[0]; m->box.ny = ext[1]; m->box.nz = ext[2];
+  m->cells = (long long)ext[0] * ext[1] * ext[2];
+  m->steps.assign(steps, steps + n_rec);
+  for (size_t i = 1; i < m->steps.size(); ++i)
+    if (m->steps[i] <= m->steps[i - 1]) return fail(h, "%s: steps must be strictly increasing", who);
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  m->mark = h->stats.device_bytes;
+  return 0;
+}
+// what the handle has allocated since the monitor's mark is `what` (kBytes*) of the monitor
+void took(const FdtdSolver* h, Monitor& m, int what) {
+  m.held[what] += h->stats.device_bytes - m.mark;
+  m.held[kBytesTotal] += h->stats.device_bytes - m.mark;
+  m.mark = h->stats.device_bytes;
+}
+int monitor_end(FdtdSolver* h, const Monitor& m) {
   h->mons.push_back(m);
   return (int)h->mons.size() - 1;
 }
-
-}  // extern "C"
-namespace {
-// The staging ring of a ring monitor (comps, cells and steps set): as many records as the budget holds, at least two (a step pair
-// records two steps), no more than there are.  Added between runs, the steps already done are skipped — their part of the result
-// stays zero — until fdtd_reset.  (Like fdtd_add_monitor: what a failure has allocated stays with the handle until fdtd_destroy.)
-int ring_setup(FdtdSolver* h, Monitor& m, int64_t staging_bytes) {
+// A device-side monitor added between runs skips the steps already done — their part of the result stays zero, a DFT accumulates
+// from now on — until fdtd_reset.  (fdtd_add_monitor's do not.)
+void skip_done_steps(const FdtdSolver* h, Monitor& m) {
   while (m.next < m.steps.size() && m.steps[m.next] < h->step) ++m.next;
+}
+// The staging ring of a ring monitor (comps, cells and steps set): as many records as the budget holds, at least two (a step pair
+// records two steps), no more than there are.  (Like fdtd_add_monitor: what a failure has allocated stays with the handle until
+// fdtd_destroy.)
+int ring_setup(FdtdSolver* h, Monitor& m, int64_t staging_bytes) {
+  skip_done_steps(h, m);
   m.reduced = m.next;
   const size_t rec_floats = m.comps.size() * (size_t)m.cells, rec_bytes = rec_floats * sizeof(float);
   const size_t budget = staging_bytes > 0 ? (size_t)staging_bytes : ((size_t)32 << 20);
@@ -3511,85 +3514,108 @@ int ring_setup(FdtdSolver* h, Monitor& m, int64_t staging_bytes) {
   float* stage = nullptr;
   if (dev_alloc(h, &stage, m.ring * rec_floats)) return -1;
   m.data = stage;
+  took(h, m, kBytesRecords);
   return 0;
 }
-// The tap tables of a sparse monitor (`who` = the entry point, for messages): component after component and inside a component
-// axis after axis [n_targets][2] taps into a box of `ext` cells.  Every tap that is read (weight != 0) must lie inside the box; no
-// weight may be NaN.  Fills where each component's tables start, its node counts, where it starts inside a record and the totals.
-int tap_tables(FdtdSolver* h, const char* who, int n_comps, const int32_t* comps, const int ext[3], const int32_t* n_targets,
-               const int32_t* tap_index, const float* tap_weight, int off[6][3], int nt_out[6][3], long long out_off[6],
-               long long* rec_nodes, size_t* n_taps_out) {
+// `n` taps along axis `a` of a box of `ext` cells (`of`: whose, for the message): every tap that is read (weight != 0) must lie
+// inside the box; no weight may be NaN.
+int check_taps(FdtdSolver* h, const char* who, const char* of, int a, size_t n, const int32_t* idx, const float* w, int ext) {
+  for (size_t t = 0; t < n; ++t)
+    if (!(w[t] == w[t]) || (w[t] != 0.0f && (idx[t] < 0 || idx[t] >= ext)))
+      return fail(h, "%s: tap %zu of %saxis %d (index %d, weight %g) outside the box of %d cells", who, t, of, a, idx[t], (double)w[t], ext);
+  return 0;
+}
+// The tap tables of a sparse monitor: component after component and inside a component axis after axis [n_targets][2] taps into
+// a box of `ext` cells.  Checks them, fills where each component's tables start, its node counts, where it starts inside a record
+// and the total, and uploads them (the monitor's kBytesTables).
+int tap_tables(FdtdSolver* h, const char* who, Monitor& m, const int ext[3], const int32_t* n_targets, const int32_t* tap_index,
+               const float* tap_weight, TapTables* T) {
   size_t n_taps = 0;
-  *rec_nodes = 0;
-  for (int c = 0; c < n_comps; ++c) {
+  T->nodes = 0;
+  for (size_t c = 0; c < m.comps.size(); ++c) {
+    char of[32];
+    snprintf(of, sizeof(of), "component %d, ", m.comps[c]);
     long long nodes = 1;
     for (int a = 0; a < 3; ++a) {
       const int nt = n_targets[3 * c + a];
-      if (nt < 1 || nt > (1 << 24)) return fail(h, "%s: %d nodes of component %d along axis %d", who, nt, comps[c], a);
-      off[c][a] = (int)n_taps; nt_out[c][a] = nt;
-      for (size_t t = 0; t < (size_t)2 * nt; ++t) {
-        const float w = tap_weight[n_taps + t];
-        if (!(w == w) || (w != 0.0f && (tap_index[n_taps + t] < 0 || tap_index[n_taps + t] >= ext[a])))
-          return fail(h, "%s: tap %zu of component %d, axis %d (index %d, weight %g) outside the box of %d cells", who, t, comps[c], a,
-                      tap_index[n_taps + t], (double)w, ext[a]);
-      }
+      if (nt < 1 || nt > (1 << 24)) return fail(h, "%s: %d nodes of component %d along axis %d", who, nt, m.comps[c], a);
+      T->off[c][a] = (int)n_taps; T->nt[c][a] = nt;
+      if (check_taps(h, who, of, a, (size_t)2 * nt, tap_index + n_taps, tap_weight + n_taps, ext[a])) return -1;
       n_taps += (size_t)2 * nt;
       nodes *= nt;
     }
-    out_off[c] = *rec_nodes;
-    *rec_nodes += nodes;
+    T->out_off[c] = T->nodes;
+    T->nodes += nodes;
   }
-  *n_taps_out = n_taps;
+  int* di = nullptr; float* dw = nullptr;
+  if (dev_upload(h, &di, (const int*)tap_index, n_taps) || dev_upload(h, &dw, tap_weight, n_taps)) return -1;
+  T->idx = di; T->w = dw;
+  took(h, m, kBytesTables);
   return 0;
 }
 }  // namespace
 extern "C" {
 
+int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps, const int32_t lo[3],
+                     const int32_t hi[3], int64_t n_rec, const int64_t* steps, int nf, const float* phase_e,
+                     const float* phase_h) {
+  if (!h) return -1;
+  if (kind == FDTD_MON_FLUX_TIME) return fail(h, "fdtd_add_monitor: FDTD_MON_FLUX_TIME monitors are added by fdtd_add_flux_time_monitor");
+  if (kind == FDTD_MON_TIME_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_TIME_SPARSE monitors are added by fdtd_add_field_time_monitor");
+  if (kind == FDTD_MON_DFT_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_DFT_SPARSE monitors are added by fdtd_add_field_dft_monitor");
+  if (kind != FDTD_MON_TIME && kind != FDTD_MON_DFT) return fail(h, "fdtd_add_monitor: bad kind %d", kind);
+  Monitor m;
+  int ext[3];
+  if (monitor_begin(h, "fdtd_add_monitor", nullptr, n_comps, comps, lo, hi, n_rec, steps, &m, ext)) return -1;
+  if (kind == FDTD_MON_DFT && nf < 1) return fail(h, "fdtd_add_monitor: a DFT monitor needs frequencies");
+  m.kind = kind;
+  m.nf = nf;
+  if (kind == FDTD_MON_TIME) {
+    m.data_bytes = (size_t)n_rec * n_comps * m.cells * sizeof(float);
+    float* d = nullptr;
+    if (dev_alloc(h, &d, (size_t)n_rec * n_comps * m.cells)) return -1;
+    m.data = d;
+    took(h, m, kBytesRecords);
+  } else {
+    m.data_bytes = (size_t)nf * n_comps * m.cells * sizeof(float2);
+    float2* d = nullptr;
+    if (dev_alloc(h, &d, (size_t)nf * n_comps * m.cells)) return -1;
+    m.data = d;
+    took(h, m, kBytesRecords);
+    if (dev_upload(h, &m.phase_e, reinterpret_cast<const float2*>(phase_e), (size_t)n_rec * nf) ||
+        dev_upload(h, &m.phase_h, reinterpret_cast<const float2*>(phase_h), (size_t)n_rec * nf))
+      return -1;
+    took(h, m, kBytesTables);
+  }
+  return monitor_end(h, m);
+}
+
 int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_t lo[3], const int32_t hi[3], int64_t n_rec,
                                const int64_t* steps, const int32_t n_nodes[3], const int32_t* tap_index, const float* tap_weight,
                                const float* wu, const float* wv, int64_t staging_bytes) {
   if (!h) return -1;
-  if (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR)
-    return fail(h, "fdtd_add_flux_time_monitor: not available on z-slab handles (the surface would be cut between ranks)");
   if (axis < 0 || axis > 2) return fail(h, "fdtd_add_flux_time_monitor: bad axis %d", axis);
-  if (!lo || !hi || !n_nodes || !tap_index || !tap_weight || !wu || !wv || n_rec < 0 || (n_rec && !steps))
-    return fail(h, "fdtd_add_flux_time_monitor: bad argument");
-  const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
-  for (int a = 0; a < 3; ++a)
-    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "fdtd_add_flux_time_monitor: box [%d,%d) outside axis %d of %d cells", lo[a], hi[a], a, N[a]);
+  const int t1 = (axis + 1) % 3, t2 = (axis + 2) % 3;
+  const int32_t comps[4] = {t1, t2, 3 + t1, 3 + t2};
+  Monitor m;
+  int ext[3];
+  if (monitor_begin(h, "fdtd_add_flux_time_monitor", "surface", 4, comps, lo, hi, n_rec, steps, &m, ext)) return -1;
+  if (!n_nodes || !tap_index || !tap_weight || !wu || !wv) return fail(h, "fdtd_add_flux_time_monitor: bad argument");
   const int u = axis == 0 ? 1 : 0;                             // the lower tangential axis (wu), the other one takes wv
-  for (int a = 0; a < 3; ++a)
-    if (n_nodes[a] < 1 || (a == axis && n_nodes[a] != 1)) return fail(h, "fdtd_add_flux_time_monitor: %d nodes along axis %d", n_nodes[a], a);
-  // every tap that is read (weight != 0) must lie inside the box
-  const int ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
-  size_t tap_off[3], n_taps = 0;
+  size_t tap_off[3], n_taps = 0;                               // per axis [4][nt][2] taps: eight per node
   for (int a = 0; a < 3; ++a) {
+    if (n_nodes[a] < 1 || (a == axis && n_nodes[a] != 1)) return fail(h, "fdtd_add_flux_time_monitor: %d nodes along axis %d", n_nodes[a], a);
+    if (check_taps(h, "fdtd_add_flux_time_monitor", "", a, (size_t)8 * n_nodes[a], tap_index + n_taps, tap_weight + n_taps, ext[a])) return -1;
     tap_off[a] = n_taps;
-    for (size_t t = 0; t < (size_t)8 * n_nodes[a]; ++t) {
-      const float w = tap_weight[n_taps + t];
-      if (!(w == w) || (w != 0.0f && (tap_index[n_taps + t] < 0 || tap_index[n_taps + t] >= ext[a])))
-        return fail(h, "fdtd_add_flux_time_monitor: tap %zu of axis %d (index %d, weight %g) outside the box of %d cells", t, a, tap_index[n_taps + t], (double)w, ext[a]);
-    }
     n_taps += (size_t)8 * n_nodes[a];
   }
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  const int64_t bytes_before = h->stats.device_bytes;
-  Monitor m;
   m.kind = FDTD_MON_TIME;
-  m.flux = true;
-  const int t1 = (axis + 1) % 3, t2 = (axis + 2) % 3;
-  m.comps = {t1, t2, 3 + t1, 3 + t2};
-  m.box.lo0 = lo[0]; m.box.lo1 = lo[1]; m.box.lo2 = lo[2];
-  m.box.nx = ext[0]; m.box.ny = ext[1]; m.box.nz = ext[2];
-  m.cells = (long long)ext[0] * ext[1] * ext[2];
-  m.steps.assign(steps, steps + n_rec);
-  for (size_t i = 1; i < m.steps.size(); ++i)
-    if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_flux_time_monitor: steps must be strictly increasing");
+  m.form = MonForm::FluxRing;
   if (ring_setup(h, m, staging_bytes)) return -1;
   float *stage = reinterpret_cast<float*>(m.data), *result = nullptr, *partial = nullptr;
   if (dev_alloc(h, &result, (size_t)n_rec)) return -1;
   m.result_bytes = (size_t)n_rec * sizeof(float);
-  const int64_t bytes_aux = h->stats.device_bytes;
+  took(h, m, kBytesResult);
   FluxMonP& p = m.fp;
   const long long nodes = (long long)n_nodes[0] * n_nodes[1] * n_nodes[2];
   p.tiles = (int)((nodes + kFluxTile - 1) / kFluxTile);
@@ -3606,119 +3632,65 @@ int fdtd_add_flux_time_monitor(FdtdSolver* h, int axis, float sign, const int32_
   p.stage = stage; p.partial = partial; p.result = result;
   p.ring = (int)m.ring;
   p.sign = sign;
-  m.aux_bytes = (size_t)(h->stats.device_bytes - bytes_aux);
-  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
-  h->mons.push_back(m);
-  return (int)h->mons.size() - 1;
+  took(h, m, kBytesTables);                                    // (the per-tile partial sums count as tables)
+  return monitor_end(h, m);
 }
 
 int fdtd_add_field_time_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
                                 int64_t n_rec, const int64_t* steps, const int32_t* n_targets, const int32_t* tap_index,
                                 const float* tap_weight, int64_t staging_bytes) {
   if (!h) return -1;
-  if (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR)
-    return fail(h, "fdtd_add_field_time_monitor: not available on z-slab handles (the box would be cut between ranks)");
-  if (n_comps < 1 || n_comps > 6) return fail(h, "fdtd_add_field_time_monitor: n_comps must be 1..6");
-  if (!comps || !lo || !hi || !n_targets || !tap_index || !tap_weight || n_rec < 0 || (n_rec && !steps))
-    return fail(h, "fdtd_add_field_time_monitor: bad argument");
-  for (int c = 0; c < n_comps; ++c) if (comps[c] < 0 || comps[c] > 5) return fail(h, "fdtd_add_field_time_monitor: bad component %d", comps[c]);
-  const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
-  for (int a = 0; a < 3; ++a)
-    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "fdtd_add_field_time_monitor: box [%d,%d) outside axis %d of %d cells", lo[a], hi[a], a, N[a]);
-  // every tap that is read (weight != 0) must lie inside the box
-  const int ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
-  FieldTimeP p{};
-  size_t n_taps = 0;
-  if (tap_tables(h, "fdtd_add_field_time_monitor", n_comps, comps, ext, n_targets, tap_index, tap_weight, p.off, p.nt, p.out_off, &p.rec_nodes, &n_taps))
-    return -1;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  const int64_t bytes_before = h->stats.device_bytes;
+  const char* who = "fdtd_add_field_time_monitor";
   Monitor m;
+  int ext[3];
+  if (monitor_begin(h, who, "box", n_comps, comps, lo, hi, n_rec, steps, &m, ext)) return -1;
+  if (!n_targets || !tap_index || !tap_weight) return fail(h, "%s: bad argument", who);
   m.kind = FDTD_MON_TIME;
-  m.sparse = true;
-  m.comps.assign(comps, comps + n_comps);
-  m.box.lo0 = lo[0]; m.box.lo1 = lo[1]; m.box.lo2 = lo[2];
-  m.box.nx = ext[0]; m.box.ny = ext[1]; m.box.nz = ext[2];
-  m.cells = (long long)ext[0] * ext[1] * ext[2];
-  m.steps.assign(steps, steps + n_rec);
-  for (size_t i = 1; i < m.steps.size(); ++i)
-    if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_field_time_monitor: steps must be strictly increasing");
-  if (ring_setup(h, m, staging_bytes)) return -1;
-  float* out = nullptr;
-  if (dev_alloc(h, &out, (size_t)n_rec * (size_t)p.rec_nodes)) return -1;
-  m.result_bytes = (size_t)n_rec * (size_t)p.rec_nodes * sizeof(float);
-  const int64_t bytes_aux = h->stats.device_bytes;
-  int* di = nullptr; float* dw = nullptr;
-  if (dev_upload(h, &di, (const int*)tap_index, n_taps) || dev_upload(h, &dw, tap_weight, n_taps)) return -1;
-  p.stage = reinterpret_cast<const float*>(m.data); p.out = out; p.idx = di; p.w = dw;
+  m.form = MonForm::SparseRing;
+  FieldTimeP& p = m.gp;
+  if (tap_tables(h, who, m, ext, n_targets, tap_index, tap_weight, &p.t) || ring_setup(h, m, staging_bytes)) return -1;
+  if (dev_alloc(h, &p.out, (size_t)n_rec * (size_t)p.t.nodes)) return -1;
+  m.result_bytes = (size_t)n_rec * (size_t)p.t.nodes * sizeof(float);
+  took(h, m, kBytesResult);
+  p.stage = reinterpret_cast<const float*>(m.data);
   for (int a = 0; a < 3; ++a) p.b[a] = ext[a];
   p.n_comps = n_comps; p.ring = (int)m.ring;
-  m.gp = p;
-  m.aux_bytes = (size_t)(h->stats.device_bytes - bytes_aux);
-  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
-  h->mons.push_back(m);
-  return (int)h->mons.size() - 1;
+  return monitor_end(h, m);
 }
 
 int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
                                int64_t n_rec, const int64_t* steps, const int32_t* n_targets, const int32_t* tap_index,
                                const float* tap_weight, int nf, const float* phase_e, const float* phase_h) {
   if (!h) return -1;
-  if (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR)
-    return fail(h, "fdtd_add_field_dft_monitor: not available on z-slab handles (the box would be cut between ranks)");
-  if (n_comps < 1 || n_comps > 6) return fail(h, "fdtd_add_field_dft_monitor: n_comps must be 1..6");
-  if (!comps || !lo || !hi || !n_targets || !tap_index || !tap_weight || n_rec < 0 || (n_rec && (!steps || !phase_e || !phase_h)))
-    return fail(h, "fdtd_add_field_dft_monitor: bad argument");
-  if (nf < 1) return fail(h, "fdtd_add_field_dft_monitor: a DFT monitor needs frequencies");
-  for (int c = 0; c < n_comps; ++c) if (comps[c] < 0 || comps[c] > 5) return fail(h, "fdtd_add_field_dft_monitor: bad component %d", comps[c]);
-  const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
-  for (int a = 0; a < 3; ++a)
-    if (lo[a] < 0 || hi[a] > N[a] || hi[a] <= lo[a]) return fail(h, "fdtd_add_field_dft_monitor: box [%d,%d) outside axis %d of %d cells", lo[a], hi[a], a, N[a]);
-  const int ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
-  FieldDftP p{};
-  size_t n_taps = 0;
-  if (tap_tables(h, "fdtd_add_field_dft_monitor", n_comps, comps, ext, n_targets, tap_index, tap_weight, p.off, p.nt, p.out_off, &p.nodes, &n_taps))
-    return -1;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  const int64_t bytes_before = h->stats.device_bytes;
+  const char* who = "fdtd_add_field_dft_monitor";
   Monitor m;
+  int ext[3];
+  if (monitor_begin(h, who, "box", n_comps, comps, lo, hi, n_rec, steps, &m, ext)) return -1;
+  if (!n_targets || !tap_index || !tap_weight || (n_rec && (!phase_e || !phase_h))) return fail(h, "%s: bad argument", who);
+  if (nf < 1) return fail(h, "%s: a DFT monitor needs frequencies", who);
   m.kind = FDTD_MON_DFT;
-  m.dsparse = true;
-  m.comps.assign(comps, comps + n_comps);
-  m.box.lo0 = lo[0]; m.box.lo1 = lo[1]; m.box.lo2 = lo[2];
-  m.box.nx = ext[0]; m.box.ny = ext[1]; m.box.nz = ext[2];
-  m.cells = (long long)ext[0] * ext[1] * ext[2];
-  m.steps.assign(steps, steps + n_rec);
-  for (size_t i = 1; i < m.steps.size(); ++i)
-    if (m.steps[i] <= m.steps[i - 1]) return fail(h, "fdtd_add_field_dft_monitor: steps must be strictly increasing");
-  // added between runs: the steps already done are skipped — the monitor accumulates from now on — until fdtd_reset
-  while (m.next < m.steps.size() && m.steps[m.next] < h->step) ++m.next;
+  m.form = MonForm::SparseDft;
   m.nf = nf;
+  skip_done_steps(h, m);
   // (like fdtd_add_monitor: what a failure below has allocated stays with the handle until fdtd_destroy)
-  m.data_bytes = (size_t)nf * (size_t)p.nodes * sizeof(float2);
-  float2* acc = nullptr;
-  if (dev_alloc(h, &acc, (size_t)nf * (size_t)p.nodes)) return -1;
-  m.data = acc;
-  int* di = nullptr; float* dw = nullptr;
-  if (dev_upload(h, &di, (const int*)tap_index, n_taps) || dev_upload(h, &dw, tap_weight, n_taps)) return -1;
+  FieldDftP& p = m.dp;
+  if (tap_tables(h, who, m, ext, n_targets, tap_index, tap_weight, &p.t)) return -1;
+  m.data_bytes = (size_t)nf * (size_t)p.t.nodes * sizeof(float2);
+  if (dev_alloc(h, &p.acc, (size_t)nf * (size_t)p.t.nodes)) return -1;
+  m.data = p.acc;
+  took(h, m, kBytesResult);                                    // (no records: the accumulators are the result)
   if (dev_upload(h, &m.phase_e, reinterpret_cast<const float2*>(phase_e), (size_t)n_rec * nf) ||
       dev_upload(h, &m.phase_h, reinterpret_cast<const float2*>(phase_h), (size_t)n_rec * nf))
     return -1;
-  p.acc = acc; p.idx = di; p.w = dw; p.nf = nf;
-  m.dp = p;
-  m.dev_bytes = (size_t)(h->stats.device_bytes - bytes_before);
-  h->mons.push_back(m);
-  return (int)h->mons.size() - 1;
+  took(h, m, kBytesTables);
+  p.nf = nf;
+  return monitor_end(h, m);
 }
 
 int fdtd_get_monitor_bytes(FdtdSolver* h, int id, int64_t out[4]) {
   if (!h) return -1;
   if (id < 0 || id >= (int)h->mons.size() || !out) return fail(h, "fdtd_get_monitor_bytes: bad id %d", id);
-  const Monitor& m = h->mons[id];
-  out[0] = (int64_t)m.dev_bytes;
-  out[1] = m.dsparse ? 0 : (int64_t)m.data_bytes;          // (a sparse DFT monitor holds no records: its accumulators are its result)
-  out[2] = m.ring ? (int64_t)(m.dev_bytes - m.data_bytes - m.aux_bytes) : (m.dsparse ? (int64_t)m.data_bytes : 0);
-  out[3] = m.ring ? (int64_t)m.aux_bytes : (int64_t)(m.dev_bytes - m.data_bytes);
+  std::copy(h->mons[id].held, h->mons[id].held + 4, out);
   return 0;
 }
 
@@ -3726,7 +3698,7 @@ int fdtd_get_monitor(FdtdSolver* h, int id, void* host, size_t bytes) {
   if (!h) return -1;
   if (id < 0 || id >= (int)h->mons.size()) return fail(h, "fdtd_get_monitor: bad id %d", id);
   Monitor& m = h->mons[id];
-  if (m.ring) {                        // the reduced series / the gathered nodes
+  if (has_ring(m)) {                   // the reduced series / the gathered nodes
     if (bytes != m.result_bytes) return fail(h, "fdtd_get_monitor: expected %zu bytes, got %zu", m.result_bytes, bytes);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     ring_drain(h, h->stream);
@@ -3796,7 +3768,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   HIPCHK(h, hipSetDevice(h->cfg.device));
   ncclUniqueId u;
   std::memcpy(&u, id, 128);
-  for (const Monitor& m : h->mons) if (m.ring || m.dsparse) return fail(h, "fdtd_comm_init: flux-time, sparse field-time and sparse DFT monitors are not available on z-slab handles");
+  if (refuse_whole_grid_monitors(h, h, "fdtd_comm_init")) return -1;
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)
@@ -3840,7 +3812,7 @@ int fdtd_reset(FdtdSolver* h) {
   for (Monitor& m : h->mons) {
     HIPCHK(h, hipMemset(m.data, 0, m.data_bytes));
     m.next = 0;
-    if (m.ring) { HIPCHK(h, hipMemset(m.result(), 0, std::max<size_t>(m.result_bytes, sizeof(float)))); m.reduced = 0; }
+    if (has_ring(m)) { HIPCHK(h, hipMemset(m.result(), 0, std::max<size_t>(m.result_bytes, sizeof(float)))); m.reduced = 0; }
   }
   h->step = 0; h->energy_max = 0.0;
   h->stats.steps_done = 0; h->stats.diverged = 0; h->stats.stopped_early = 0; h->stats.field_decay = 0.0;      // (what a fresh handle reports until its first decay check)
@@ -3858,7 +3830,7 @@ extern "C" {
 int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user) {
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  if (h->comm) for (const Monitor& m : h->mons) if (m.ring || m.dsparse) return fail(h, "fdtd_run: flux-time, sparse field-time and sparse DFT monitors are not available on z-slab handles");
+  if (h->comm && refuse_whole_grid_monitors(h, h, "fdtd_run")) return -1;
   Run r{h, n_steps, progress, user};
   if (r.setup() || r.setup_schedules() || r.setup_pairs()) return -1;
   if (r.loop()) { flush_seams(h, h->stream); return -1; }      // (an error leaves no stale seam columns either)
@@ -3874,8 +3846,7 @@ int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user
 int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double phase[3], const int n_real[3],
                    FdtdProgressFn progress, void* user) {
   if (!hr || !hi) return -1;
-  for (const FdtdSolver* hh : {hr, hi})
-    for (const Monitor& m : hh->mons) if (m.ring || m.dsparse) return fail(hr, "fdtd_run_bloch: flux-time, sparse field-time and sparse DFT monitors (fdtd_add_flux_time_monitor, fdtd_add_field_time_monitor, fdtd_add_field_dft_monitor) are not available with Bloch boundaries (complex fields)");
+  for (const FdtdSolver* hh : {hr, hi}) if (refuse_whole_grid_monitors(hr, hh, "fdtd_run_bloch", true)) return -1;
   if (hi->comm) return fail(hr, "fdtd_run_bloch: the communicator of a z-slab belongs to the first (real-part) handle");
   // fully anisotropic bodies: the Re handle's lists (wrap codes included) drive both parts; the Im handle's carry the same rows
   const bool aniso = !hr->aniso.empty();

@@ -23,13 +23,8 @@
 namespace fdtd {
 
 struct FieldDftP {
-  float2* acc;               // [nf][nodes]: per frequency the components one after the other, each [n2][n1][n0]
-  const int* idx;            // taps: for component slot c and axis a, [nt[c][a]][2] indices into the box along a at off[c][a]
-  const float* w;            //       their weights, same layout
-  int off[6][3];
-  int nt[6][3];              // kept nodes per component slot and axis
-  long long out_off[6];      // where component slot c starts inside a frequency of `acc`
-  long long nodes;           // kept nodes of all components
+  float2* acc;               // [nf][t.nodes]: per frequency the components one after the other, each [n2][n1][n0]
+  TapTables t;
   int nf;
 };
 struct FieldDftSrc {         // the entries of one launch: component slots of the monitor and the box each is read from
@@ -39,40 +34,24 @@ struct FieldDftSrc {         // the entries of one launch: component slots of th
   long long sy, sz;          // row and plane stride of the boxes
 };
 
-// blockIdx.x = piece of 64 nodes along x, blockIdx.y (strided) = group of kFieldTimeRows rows, blockIdx.z = entry of the launch.
-// S: as field_time_gather_kernel (FDTD_OPT_AXIS_SHIFT).
+// blockIdx.z = entry of the launch; x, y and S: for_each_kept_node (fdtd_field_time.hpp).
 template <int S>
 __global__ __launch_bounds__(64 * kFieldTimeRows) void field_dft_record_kernel(FieldDftP p, FieldDftSrc r, const float2* phase) {
   const int e = (int)blockIdx.z;
   if (e >= r.n) return;
   const int c = r.slot[e];
-  const int n0 = p.nt[c][0], n1 = p.nt[c][1], n2 = p.nt[c][2];
-  const int x = (int)blockIdx.x * 64 + (int)threadIdx.x;
-  if (x >= n0) return;                                         // (no barrier below)
-  const float* f = r.f[e];
-  float2* a0 = p.acc + p.out_off[c];
-  int j[3][2];
-  float w[3][2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) { j[0][t] = p.idx[p.off[c][0] + 2 * x + t]; w[0][t] = p.w[p.off[c][0] + 2 * x + t]; }
-  const long long rows = (long long)n1 * n2;
-  for (long long row = (long long)blockIdx.y * kFieldTimeRows + threadIdx.y; row < rows; row += (long long)gridDim.y * kFieldTimeRows) {
-    const int q1 = (int)(row % n1), q2 = (int)(row / n1);      // (the same in all 64 lanes of the wave)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      j[1][t] = p.idx[p.off[c][1] + 2 * q1 + t]; w[1][t] = p.w[p.off[c][1] + 2 * q1 + t];
-      j[2][t] = p.idx[p.off[c][2] + 2 * q2 + t]; w[2][t] = p.w[p.off[c][2] + 2 * q2 + t];
-    }
-    const float v = colocate_taps<S>(f, r.sy, r.sz, j, w);
-    const long long t = row * n0 + x;
+  const int x = kept_x();
+  if (x >= p.t.nt[c][0]) return;                               // (no barrier below)
+  float2* a0 = p.acc + p.t.out_off[c];
+  for_each_kept_node<S>(p.t, c, x, r.f[e], r.sy, r.sz, [&](long long node, float v) {
     for (int k = 0; k < p.nf; ++k) {
       const float2 ph = phase[k];
-      float2 a = a0[(long long)k * p.nodes + t];
+      float2 a = a0[(long long)k * p.t.nodes + node];
       a.x += v * ph.x;
       a.y += v * ph.y;
-      a0[(long long)k * p.nodes + t] = a;
+      a0[(long long)k * p.t.nodes + node] = a;
     }
-  }
+  });
 }
 
 }  // namespace fdtd

@@ -20,15 +20,20 @@ namespace fdtd {
 constexpr int kFieldTimeRows = 4;       // rows of nodes (waves) per workgroup
 constexpr int kFieldTimeMaxRowBlocks = 16384;     // grid rows of a launch at most (a workgroup strides the rest)
 
-struct FieldTimeP {
-  const float* stage;        // [ring][n_comps][bz][by][bx]
-  float* out;                // [n_rec][rec_nodes]: per record the components one after the other, each [n2][n1][n0]
-  const int* idx;            // taps: for component c and axis a, [nt[c][a]][2] indices into the box along a at off[c][a]
+// The tap tables of a sparse monitor, shared by FieldTimeP and FieldDftP (fdtd_field_dft.hpp): filled and uploaded by tap_tables
+// (fdtd_capi.hip), walked by for_each_kept_node.
+struct TapTables {
+  const int* idx;            // taps: for component slot c and axis a, [nt[c][a]][2] indices into the box along a at off[c][a]
   const float* w;            //       their weights, same layout
   int off[6][3];
-  int nt[6][3];              // kept nodes per component and axis
-  long long out_off[6];      // where component c starts inside a record of `out`
-  long long rec_nodes;       // kept nodes of a record, all components
+  int nt[6][3];              // kept nodes per component slot and axis
+  long long out_off[6];      // where component slot c starts inside a record / a frequency of the result
+  long long nodes;           // kept nodes of all components
+};
+struct FieldTimeP {
+  const float* stage;        // [ring][n_comps][bz][by][bx]
+  float* out;                // [n_rec][t.nodes]: per record the components one after the other, each [n2][n1][n0]
+  TapTables t;
   int b[3];                  // box extents bx, by, bz
   int n_comps, ring;
   long long r0;              // records [r0, r0 + cnt) of this launch
@@ -76,37 +81,46 @@ __device__ __forceinline__ float colocate_taps(const float* f, long long sy, lon
   return s;
 }
 
-// blockIdx.x = piece of 64 nodes along x, blockIdx.y (strided) = group of kFieldTimeRows rows, blockIdx.z = record of the launch x component.
+// The kept nodes of component slot `c` that belong to this thread — node `x` (< nt[c][0]: a thread beyond has returned, kept_x)
+// of the rows blockIdx.y (strided) = group of kFieldTimeRows rows: sink(index of the node inside the component, its value
+// colocated from the box `f`) for each.
 // S = the cyclic renaming the caller laid the problem out with (FDTD_OPT_AXIS_SHIFT: device axis a holds the caller's axis (a + S) % 3):
 // the three passes run along the caller's x, y, z — device axes (3 - S) % 3, (4 - S) % 3, (5 - S) % 3 — so that a renamed problem
 // gives the bits of the plain one.
-template <int S>
-__global__ __launch_bounds__(64 * kFieldTimeRows) void field_time_gather_kernel(FieldTimeP p) {
-  const int c = (int)(blockIdx.z % (unsigned)p.n_comps), q = (int)(blockIdx.z / (unsigned)p.n_comps);
-  if (q >= p.cnt) return;
-  const int n0 = p.nt[c][0], n1 = p.nt[c][1], n2 = p.nt[c][2];
-  const int x = (int)blockIdx.x * 64 + (int)threadIdx.x;
-  if (x >= n0) return;                                         // (no barrier below)
-  const long long rec = p.r0 + q;
-  const int slot = (int)(rec % p.ring);
-  const int bx = p.b[0], by = p.b[1];
-  const long long cells = (long long)bx * by * p.b[2];
-  const float* f = p.stage + ((long long)slot * p.n_comps + c) * cells;
-  float* o = p.out + rec * p.rec_nodes + p.out_off[c];
+__device__ __forceinline__ int kept_x() { return (int)blockIdx.x * 64 + (int)threadIdx.x; }      // blockIdx.x = piece of 64 nodes along x
+template <int S, class Sink>
+__device__ __forceinline__ void for_each_kept_node(const TapTables& T, int c, int x, const float* f, long long sy, long long sz, Sink&& sink) {
+  const int n0 = T.nt[c][0], n1 = T.nt[c][1], n2 = T.nt[c][2];
   int j[3][2];
   float w[3][2];
 #pragma unroll
-  for (int t = 0; t < 2; ++t) { j[0][t] = p.idx[p.off[c][0] + 2 * x + t]; w[0][t] = p.w[p.off[c][0] + 2 * x + t]; }
+  for (int t = 0; t < 2; ++t) { j[0][t] = T.idx[T.off[c][0] + 2 * x + t]; w[0][t] = T.w[T.off[c][0] + 2 * x + t]; }
   const long long rows = (long long)n1 * n2;
   for (long long row = (long long)blockIdx.y * kFieldTimeRows + threadIdx.y; row < rows; row += (long long)gridDim.y * kFieldTimeRows) {
     const int q1 = (int)(row % n1), q2 = (int)(row / n1);      // (the same in all 64 lanes of the wave)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      j[1][t] = p.idx[p.off[c][1] + 2 * q1 + t]; w[1][t] = p.w[p.off[c][1] + 2 * q1 + t];
-      j[2][t] = p.idx[p.off[c][2] + 2 * q2 + t]; w[2][t] = p.w[p.off[c][2] + 2 * q2 + t];
+      j[1][t] = T.idx[T.off[c][1] + 2 * q1 + t]; w[1][t] = T.w[T.off[c][1] + 2 * q1 + t];
+      j[2][t] = T.idx[T.off[c][2] + 2 * q2 + t]; w[2][t] = T.w[T.off[c][2] + 2 * q2 + t];
     }
-    o[row * n0 + x] = colocate_taps<S>(f, (long long)bx, (long long)bx * by, j, w);
+    sink(row * n0 + x, colocate_taps<S>(f, sy, sz, j, w));
   }
+}
+
+// blockIdx.z = record of the launch x component; x, y and S: for_each_kept_node.
+template <int S>
+__global__ __launch_bounds__(64 * kFieldTimeRows) void field_time_gather_kernel(FieldTimeP p) {
+  const int c = (int)(blockIdx.z % (unsigned)p.n_comps), q = (int)(blockIdx.z / (unsigned)p.n_comps);
+  if (q >= p.cnt) return;
+  const int x = kept_x();
+  if (x >= p.t.nt[c][0]) return;                               // (no barrier below)
+  const long long rec = p.r0 + q;
+  const int slot = (int)(rec % p.ring);
+  const int bx = p.b[0], by = p.b[1];
+  const long long cells = (long long)bx * by * p.b[2];
+  float* o = p.out + rec * p.t.nodes + p.t.out_off[c];
+  for_each_kept_node<S>(p.t, c, x, p.stage + ((long long)slot * p.n_comps + c) * cells, (long long)bx, (long long)bx * by,
+                        [&](long long node, float v) { o[node] = v; });
 }
 
 }  // namespace fdtd

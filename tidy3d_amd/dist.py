@@ -137,8 +137,8 @@ def slab_discretization(sim, n_steps: Optional[int] = None):
     """The discretization of a z-slab run.  FluxTimeMonitors stay on the host path whatever their size: the device reduction
     (MonitorSpec kind "flux_time") needs the whole surface on one GPU, and the engine refuses it on a slab.  FieldTimeMonitors
     likewise: the device gather (kind "time_sparse") needs the whole box on one GPU; and FieldMonitors (kind "dft_sparse")."""
-    from .discretize import discretize
-    return discretize(sim, n_steps=n_steps, flux_time_device=False, field_time_device=False, field_dft_device=False)
+    from .discretize import DevicePaths, discretize
+    return discretize(sim, n_steps=n_steps, device_paths=DevicePaths.all_host())
 
 
 def run(simulation, verbose: bool = True, n_steps: Optional[int] = None, lib=None, **kw):

@@ -295,6 +295,21 @@ def _local_pml_counts(tables: List[np.ndarray]) -> Tuple[int, int]:
     return lead, trail
 
 
+# MonitorSpec kinds with a device-side path of their own: what the refusals call them, dtype and shape of what fdtd_get_monitor returns
+_DEVICE_KINDS = {
+    "flux_time": ("FluxTimeMonitor reduced", np.float32, lambda m: (len(m.steps),)),
+    "time_sparse": ("FieldTimeMonitor gathered", np.float32, lambda m: (len(m.steps), sum(int(np.prod(t)) for t in m.targets))),
+    "dft_sparse": ("FieldMonitor accumulated", np.complex64, lambda m: (len(m.freqs), sum(int(np.prod(t)) for t in m.targets))),
+}
+
+
+def _flat_taps(pairs):
+    """(indices, weights) pairs in table order -> the int32 and float32 arrays the library takes."""
+    pairs = list(pairs)
+    return (np.ascontiguousarray(np.concatenate([np.asarray(i, dtype=np.int32).ravel() for i, _ in pairs])),
+            _f32(np.concatenate([np.asarray(w, dtype=np.float64).ravel() for _, w in pairs])))
+
+
 class HipEngine:
     def __init__(self, spec: SolverSpec, lib: Optional[L.FdtdLib] = None, device: int = 0,
                  variant: int = L.VARIANT_AUTO, flags: int = 0, z_chunk: int = 0,
@@ -633,37 +648,26 @@ class HipEngine:
             lo = np.asarray([m.lo[0], m.lo[1], lo2 - z0], dtype=np.int32)
             hi = np.asarray([m.hi[0], m.hi[1], hi2 - z0], dtype=np.int32)
             steps = np.ascontiguousarray(m.steps, dtype=np.int64)
-            if m.kind == "flux_time":
+            if m.kind in _DEVICE_KINDS:
                 if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz) or spec.bloch is not None:
-                    raise SolverLibraryError(f"monitor '{m.name}': a FluxTimeMonitor reduced on the device is not available on z-slabs "
+                    raise SolverLibraryError(f"monitor '{m.name}': a {_DEVICE_KINDS[m.kind][0]} on the device is not available on z-slabs "
                                              "(more than one GPU, force_comm) or with Bloch boundaries")
-                n_nodes = np.asarray([len(w) for w in m.weights], dtype=np.int32)
-                tidx = np.ascontiguousarray(np.concatenate([np.asarray(t[0], dtype=np.int32).ravel() for t in m.taps]))
-                tw = _f32(np.concatenate([np.asarray(t[1], dtype=np.float64).ravel() for t in m.taps]))
-                u, v = [a for a in range(3) if a != m.axis]
-                wu, wv = _f32(m.weights[u]), _f32(m.weights[v])
-                mid = d.fdtd_add_flux_time_monitor(h, int(m.axis), float(m.sign), _ptr(lo), _ptr(hi), len(steps), _ptr(steps),
-                                                   _ptr(n_nodes), _ptr(tidx), _ptr(tw), _ptr(wu), _ptr(wv), int(m.staging_bytes))
-                self._chk(mid, "fdtd_add_flux_time_monitor")
-                self.mon_ids.append((m, mid, (lo2, hi2)))
-                continue
-            if m.kind in SPARSE_KINDS:
-                if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz) or spec.bloch is not None:
-                    what = "FieldTimeMonitor gathered" if m.kind == "time_sparse" else "FieldMonitor accumulated"
-                    raise SolverLibraryError(f"monitor '{m.name}': a {what} on the device is not available on z-slabs "
-                                             "(more than one GPU, force_comm) or with Bloch boundaries")
-                n_t = np.asarray(m.targets, dtype=np.int32)
-                tidx = np.ascontiguousarray(np.concatenate([np.asarray(t[a][0], dtype=np.int32).ravel() for t in m.taps for a in range(3)]))
-                tw = _f32(np.concatenate([np.asarray(t[a][1], dtype=np.float64).ravel() for t in m.taps for a in range(3)]))
-                if m.kind == "time_sparse":
-                    mid = d.fdtd_add_field_time_monitor(h, len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t),
-                                                        _ptr(tidx), _ptr(tw), int(m.staging_bytes))
-                    self._chk(mid, "fdtd_add_field_time_monitor")
+                if m.kind == "flux_time":
+                    n_nodes, (tidx, tw) = np.asarray([len(w) for w in m.weights], dtype=np.int32), _flat_taps(m.taps)
+                    wu, wv = (_f32(m.weights[a]) for a in range(3) if a != m.axis)
+                    name, args = "fdtd_add_flux_time_monitor", (int(m.axis), float(m.sign), _ptr(lo), _ptr(hi), len(steps), _ptr(steps),
+                                                                 _ptr(n_nodes), _ptr(tidx), _ptr(tw), _ptr(wu), _ptr(wv), int(m.staging_bytes))
                 else:
-                    pe, ph = _cplx_f32(m.phase_e), _cplx_f32(m.phase_h)
-                    mid = d.fdtd_add_field_dft_monitor(h, len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t),
-                                                       _ptr(tidx), _ptr(tw), len(m.freqs), _ptr(pe), _ptr(ph))
-                    self._chk(mid, "fdtd_add_field_dft_monitor")
+                    n_t = np.asarray(m.targets, dtype=np.int32)
+                    tidx, tw = _flat_taps(t[a] for t in m.taps for a in range(3))
+                    args = (len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t), _ptr(tidx), _ptr(tw))
+                    if m.kind == "time_sparse":
+                        name, args = "fdtd_add_field_time_monitor", args + (int(m.staging_bytes),)
+                    else:
+                        pe, ph = _cplx_f32(m.phase_e), _cplx_f32(m.phase_h)
+                        name, args = "fdtd_add_field_dft_monitor", args + (len(m.freqs), _ptr(pe), _ptr(ph))
+                mid = getattr(d, name)(h, *args)
+                self._chk(mid, name)
                 self.mon_ids.append((m, mid, (lo2, hi2)))
                 continue
             if m.kind == "dft":
@@ -792,12 +796,8 @@ class HipEngine:
             if mid < 0:
                 continue
             bz, by, bx = hi2 - lo2, m.hi[1] - m.lo[1], m.hi[0] - m.lo[0]
-            if m.kind == "flux_time":
-                arr = np.empty(len(m.steps), dtype=np.float32)
-            elif m.kind == "time_sparse":
-                arr = np.empty((len(m.steps), sum(int(np.prod(t)) for t in m.targets)), dtype=np.float32)
-            elif m.kind == "dft_sparse":
-                arr = np.empty((len(m.freqs), sum(int(np.prod(t)) for t in m.targets)), dtype=np.complex64)
+            if m.kind in _DEVICE_KINDS:
+                arr = np.empty(_DEVICE_KINDS[m.kind][2](m), dtype=_DEVICE_KINDS[m.kind][1])
             elif m.kind == "dft":
                 arr = np.empty((len(m.freqs), len(m.comps), bz, by, bx), dtype=np.complex64)
             else:

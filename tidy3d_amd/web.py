@@ -22,7 +22,7 @@ import numpy as np
 
 from . import schema as td
 from .data import SimulationData, assemble
-from .discretize import discretize
+from .discretize import DevicePaths, _device_refusals, discretize
 from .exceptions import SetupError, SolverLibraryError
 
 log = logging.getLogger("tidy3d_amd")
@@ -119,11 +119,9 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
 
     sim, was_tidy3d = _as_mirror(simulation)
     sim.validate_pre_upload(source_required=True)
+    paths = DevicePaths(flux_time_device, field_time_device, field_dft_device)
     if devices is not None and len(devices) > 1:
-        from .discretize import _field_dft_refusal, _field_time_refusal, _flux_time_refusal
-        _flux_time_refusal(sim, flux_time_device, "devices= with more than one GPU")
-        _field_time_refusal(sim, field_time_device, "devices= with more than one GPU")
-        _field_dft_refusal(sim, field_dft_device, "devices= with more than one GPU")
+        _device_refusals(sim, paths, "devices= with more than one GPU")
         sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose, _dist_options or {})
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
         if want_td:
@@ -138,8 +136,7 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
     t_setup = time.perf_counter()
-    disc = discretize(sim, n_steps=n_steps, mode_grid_dispersion=mode_grid_dispersion, flux_time_device=flux_time_device,
-                      field_time_device=field_time_device, field_dft_device=field_dft_device)
+    disc = discretize(sim, n_steps=n_steps, mode_grid_dispersion=mode_grid_dispersion, device_paths=paths)
     spec = disc.spec
     lines = [f"Simulation domain Nx, Ny, Nz: {list(spec.shape)}",
              f"Applied symmetries: {tuple(sim.symmetry)}",
