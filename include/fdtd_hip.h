@@ -38,7 +38,8 @@ typedef struct FdtdSolver FdtdSolver;
 enum { FDTD_BC_PEC = 0, FDTD_BC_PMC = 1, FDTD_BC_PERIODIC = 2, FDTD_BC_NEIGHBOR = 3 };
 enum { FDTD_MON_TIME = 0, FDTD_MON_DFT = 1, FDTD_MON_FLUX_TIME = 2 /* added by fdtd_add_flux_time_monitor only */,
        FDTD_MON_TIME_SPARSE = 3 /* added by fdtd_add_field_time_monitor only */,
-       FDTD_MON_DFT_SPARSE = 4 /* added by fdtd_add_field_dft_monitor only */ };
+       FDTD_MON_DFT_SPARSE = 4 /* added by fdtd_add_field_dft_monitor only */,
+       FDTD_MON_DFT_LATTICE = 5 /* added by fdtd_add_lattice_dft_monitor only */ };
 /* kernel variants of the two main update kernels (A/B-tested by bench.py --variant) */
 /* AUTO = FUSED on one GPU (single-sweep E+H update, 48 B/cell-step), two-pass ZMARCH otherwise */
 enum { FDTD_VARIANT_AUTO = 0, FDTD_VARIANT_SIMPLE = 1, FDTD_VARIANT_ZMARCH = 2, FDTD_VARIANT_FUSED = 3 };
@@ -300,13 +301,25 @@ int fdtd_add_field_time_monitor(FdtdSolver* h, int n_comps, const int32_t* comps
 int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
                                int64_t n_rec, const int64_t* steps, const int32_t* n_targets,
                                const int32_t* tap_index, const float* tap_weight, int nf, const float* phase_e, const float* phase_h);
+/* FDTD_MON_DFT_LATTICE (ref monitor.py FieldProjectionAngleMonitor / CartesianMonitor / KSpaceMonitor: one surface of a projection
+ * monitor): the running DFT of the components `comps` on the surface's sampling lattice — everything as FDTD_MON_DFT_SPARSE (the result
+ * complex64 [nf][component][n_z][n_y][n_x], fdtd_get_monitor and fdtd_get_monitor_bytes, the schedules, adding between runs, fdtd_reset,
+ * the refusals), but with n_taps = 4 taps per node and axis, tables [n_targets][n_taps] per component and axis: a lattice point lies
+ * between two colocated nodes with two Yee taps each, in the order node j tap 0, node j tap 1, node j + 1 tap 0, node j + 1 tap 1,
+ *     v = sum over the 4 x 4 x 4 slots of wx wy wz F[jz][jy][jx]          (separable: x, then y, then z; fp32; the slots in table order,
+ *                                                                        duplicates not merged; a slot of weight 0 is neither read nor added)
+ * The lanes of a wave run along the first axis on which a component keeps more than one node (csrc/fdtd_lattice_dft.hpp): the result
+ * layout does not depend on it.  Any other n_taps is refused.  Returns the monitor id (>= 0) or <0. */
+int fdtd_add_lattice_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
+                                 int64_t n_rec, const int64_t* steps, const int32_t* n_targets, int n_taps /* 4 */,
+                                 const int32_t* tap_index, const float* tap_weight, int nf, const float* phase_e, const float* phase_h);
 /* time: float [n_rec][n_comps][bz][by][bx];  dft: complex64 [nf][n_comps][bz][by][bx];  flux-time: float [n_rec];
  * sparse field-time: float [n_rec][sum over the components of their kept nodes];
- * sparse DFT: complex64 [nf][sum over the components of their kept nodes] */
+ * sparse DFT, lattice DFT: complex64 [nf][sum over the components of their kept nodes] */
 int fdtd_get_monitor(FdtdSolver* h, int monitor_id, void* host, size_t bytes);
 /* device memory a monitor holds, as allocated: out[0] = all of it, out[1] = its record buffer (flux-time, sparse field-time: the staging ring),
  * out[2] = the reduced series of a flux-time monitor / the gathered array of a sparse field-time monitor / the accumulators of a
- * sparse DFT monitor, nf x kept nodes x 8 B (which holds no records: out[1] = 0) (else 0),
+ * sparse or lattice DFT monitor, nf x kept nodes x 8 B (which holds no records: out[1] = 0) (else 0),
  * out[3] = tables (phase tables; taps, weights, per-tile partial sums) */
 int fdtd_get_monitor_bytes(FdtdSolver* h, int monitor_id, int64_t out[4]);
 
@@ -426,8 +439,8 @@ enum { FDTD_OPT_FLAGS = 0 /* Not switched between runs by any test. */, FDTD_OPT
                                     another launch bound than their own, not a setting for production runs).  May be switched between runs of one engine (A/B inside one placement of the arrays). (tests/test_emu_seam_defer.py switches it.) */
        FDTD_OPT_AXIS_SHIFT = 28, /* 0 (default), 1, 2: the caller laid the problem out with its axes cyclically renamed — device axis a holds the
                                     caller's axis (a + s) % 3.  The solve does not depend on it; what is formed axis after axis in a fixed order
-                                    does: the passes of a sparse field-time monitor's gather (fdtd_add_field_time_monitor) and of a sparse DFT
-                                    monitor's colocation (fdtd_add_field_dft_monitor) then run along the caller's x, y, z, so that the renamed problem gives the bits of the plain one. (tests/test_emu_field_time.py runs all three.) */
+                                    does: the passes of a sparse field-time monitor's gather (fdtd_add_field_time_monitor), of a sparse DFT
+                                    monitor's colocation (fdtd_add_field_dft_monitor) and of a lattice DFT monitor's sums (fdtd_add_lattice_dft_monitor) then run along the caller's x, y, z, so that the renamed problem gives the bits of the plain one. (tests/test_emu_field_time.py runs all three.) */
        FDTD_OPT_LDS_PAD = 10 /* measuring aid: extra dynamic LDS per workgroup of the sweep in bytes (lowers its occupancy). Not switched between runs by any test. */ };
 int fdtd_set_option(FdtdSolver* h, int key, int value);
 int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out);

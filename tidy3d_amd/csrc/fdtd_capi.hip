@@ -25,6 +25,7 @@
 #include "fdtd_flux_time.hpp"
 #include "fdtd_field_time.hpp"
 #include "fdtd_field_dft.hpp"
+#include "fdtd_lattice_dft.hpp"
 
 using namespace fdtd;
 
@@ -126,8 +127,9 @@ struct Tfsf {
 
 // what `data` holds and what becomes of it: records or accumulators of the whole box, read back as they are (fdtd_add_monitor); a
 // ring of records that ring_drain reduces to one flux value each (fdtd_flux_time.hpp) or gathers onto the kept nodes
-// (fdtd_field_time.hpp); DFT accumulators on the kept nodes alone (fdtd_field_dft.hpp)
-enum class MonForm { Whole, FluxRing, SparseRing, SparseDft };
+// (fdtd_field_time.hpp); DFT accumulators on the kept nodes alone (fdtd_field_dft.hpp), or on the sampling lattice of a projection
+// surface alone (fdtd_lattice_dft.hpp: the tables of `dp` then hold kLatticeTaps taps per node and axis)
+enum class MonForm { Whole, FluxRing, SparseRing, SparseDft, LatticeDft };
 enum { kBytesTotal, kBytesRecords, kBytesResult, kBytesTables };      // the figures of fdtd_get_monitor_bytes
 
 struct Monitor {
@@ -140,7 +142,7 @@ struct Monitor {
   int nf = 0;
   float2 *phase_e = nullptr, *phase_h = nullptr;   // [n_rec][nf]
   void* data = nullptr;            // Whole: [n_rec][comps][box] floats / [nf][comps][box] float2; rings: `ring` records (slot = record
-  size_t data_bytes = 0;           // index mod ring); SparseDft: float2 [nf][kept nodes]
+  size_t data_bytes = 0;           // index mod ring); SparseDft, LatticeDft: float2 [nf][kept nodes]
   long long cells = 0;
   int64_t held[4] = {0, 0, 0, 0};  // device memory the monitor holds, by kBytes*: taken where it is allocated (took)
   int64_t mark = 0;                // h->stats.device_bytes when the last of them was taken
@@ -149,7 +151,7 @@ struct Monitor {
   size_t result_bytes = 0;         // what fdtd_get_monitor returns of a ring monitor: the series / the gathered array
   FluxMonP fp{};                   // FluxRing: addresses and shapes of its tables
   FieldTimeP gp{};                 // SparseRing
-  FieldDftP dp{};                  // SparseDft
+  FieldDftP dp{};                  // SparseDft, LatticeDft
   float* result() const { return form == MonForm::FluxRing ? fp.result : gp.out; }
   long long slot(size_t rec) const { return (long long)(ring ? rec % ring : rec); }
 };
@@ -377,6 +379,10 @@ int fail(FdtdSolver* h, const char* fmt, ...) {
 
 // z-slab handles and Bloch pairs refuse the monitors of `h` that need their whole box on one handle (the error goes to `err`)
 int refuse_whole_grid_monitors(FdtdSolver* err, const FdtdSolver* h, const char* who, bool bloch = false) {
+  for (const Monitor& m : h->mons)
+    if (m.form == MonForm::LatticeDft)
+      return fail(err, "%s: lattice DFT monitors%s", who,
+                  bloch ? " (fdtd_add_lattice_dft_monitor) are not available with Bloch boundaries (complex fields)" : " are not available on z-slab handles");
   for (const Monitor& m : h->mons)
     if (needs_whole_grid(m))
       return fail(err, "%s: flux-time, sparse field-time and sparse DFT monitors%s", who,
@@ -1867,8 +1873,22 @@ void ring_drain(FdtdSolver* h, hipStream_t st) {
 
 // One record launch of a sparse DFT monitor (fdtd_field_dft.hpp): the entries of `r` — component slots and the boxes they are read
 // from, the live fields or the sweep's dump — colocated onto the kept nodes and accumulated with the nf phases at `phase`.
+// A lattice DFT monitor (fdtd_lattice_dft.hpp) likewise, the lanes along each component's lattice_lane_axis.
 void launch_field_dft(FdtdSolver* h, const Monitor& m, const FieldDftSrc& r, const float2* phase, hipStream_t st) {
-  LAUNCH_TAP_KERNEL(field_dft_record_kernel, h, tap_grid(m.dp.t, r.slot, r.n, (unsigned)r.n), st, m.dp, r, phase);
+  if (m.form != MonForm::LatticeDft) {
+    LAUNCH_TAP_KERNEL(field_dft_record_kernel, h, tap_grid(m.dp.t, r.slot, r.n, (unsigned)r.n), st, m.dp, r, phase);
+    return;
+  }
+  const TapTables& T = m.dp.t;
+  int nl = 1;
+  long long rows = 1;
+  for (int e = 0; e < r.n; ++e) {
+    const int L = lattice_lane_axis(T, r.slot[e]);
+    nl = std::max(nl, T.nt[r.slot[e]][L]);
+    rows = std::max(rows, lattice_rows(T, r.slot[e], L));
+  }
+  const dim3 grid((unsigned)((nl + 63) / 64), (unsigned)std::min<long long>((rows + kFieldTimeRows - 1) / kFieldTimeRows, kFieldTimeMaxRowBlocks), (unsigned)r.n);
+  LAUNCH_TAP_KERNEL(lattice_dft_record_kernel, h, grid, st, m.dp, r, phase);
 }
 
 // H-side source terms of step n act on H^{n-1/2} in place in FRONT of a pair's sweep: then the small time monitors of the pair take
@@ -1892,7 +1912,7 @@ void pair_record(FdtdSolver* h, const F2Table* tb, long long n, hipStream_t st) 
     for (int pass = 0; pass < 2; ++pass) {
       if (m.next >= m.steps.size() || m.steps[m.next] != n + pass) continue;
       const float2* phase = (const float2*)((pass == 0 ? m.phase_h : m.phase_e) + (long long)m.next * m.nf);
-      if (m.form == MonForm::SparseDft) {      // the dump holds the whole box of each component, contiguous
+      if (m.form == MonForm::SparseDft || m.form == MonForm::LatticeDft) {      // the dump holds the whole box of each component, contiguous
         FieldDftSrc s{};
         s.sy = m.box.nx; s.sz = (long long)m.box.nx * m.box.ny;
         for (size_t ic = 0; ic < m.comps.size(); ++ic)
@@ -2923,7 +2943,7 @@ void record_monitors(FdtdSolver* h, long long n, bool post, hipStream_t st, cons
         if (has_ring(m) && (size_t)rec - m.reduced >= m.ring) ring_drain(h, st);      // (a full ring: its complete records first)
         float* out = reinterpret_cast<float*>(m.data) + m.slot((size_t)rec) * nc * m.cells;
         hipLaunchKernelGGL(time_record_multi_kernel, grid, dim3(256), 0, st, r, h->g, m.box, out, (long long)m.cells);
-      } else if (m.form == MonForm::SparseDft) {      // the live fields at the box origin
+      } else if (m.form == MonForm::SparseDft || m.form == MonForm::LatticeDft) {      // the live fields at the box origin
         FieldDftSrc s{};
         s.n = r.n; s.sy = h->g.nx; s.sz = h->g.sxy;
         for (int q = 0; q < r.n; ++q) {
@@ -3525,11 +3545,11 @@ int check_taps(FdtdSolver* h, const char* who, const char* of, int a, size_t n, 
       return fail(h, "%s: tap %zu of %saxis %d (index %d, weight %g) outside the box of %d cells", who, t, of, a, idx[t], (double)w[t], ext);
   return 0;
 }
-// The tap tables of a sparse monitor: component after component and inside a component axis after axis [n_targets][2] taps into
-// a box of `ext` cells.  Checks them, fills where each component's tables start, its node counts, where it starts inside a record
+// The tap tables of a sparse monitor: component after component and inside a component axis after axis [n_targets][per] taps into
+// a box of `ext` cells (per = 2: colocation taps; kLatticeTaps: those of a lattice DFT monitor).  Checks them, fills where each component's tables start, its node counts, where it starts inside a record
 // and the total, and uploads them (the monitor's kBytesTables).
 int tap_tables(FdtdSolver* h, const char* who, Monitor& m, const int ext[3], const int32_t* n_targets, const int32_t* tap_index,
-               const float* tap_weight, TapTables* T) {
+               const float* tap_weight, TapTables* T, int per = 2) {
   size_t n_taps = 0;
   T->nodes = 0;
   for (size_t c = 0; c < m.comps.size(); ++c) {
@@ -3540,8 +3560,8 @@ int tap_tables(FdtdSolver* h, const char* who, Monitor& m, const int ext[3], con
       const int nt = n_targets[3 * c + a];
       if (nt < 1 || nt > (1 << 24)) return fail(h, "%s: %d nodes of component %d along axis %d", who, nt, m.comps[c], a);
       T->off[c][a] = (int)n_taps; T->nt[c][a] = nt;
-      if (check_taps(h, who, of, a, (size_t)2 * nt, tap_index + n_taps, tap_weight + n_taps, ext[a])) return -1;
-      n_taps += (size_t)2 * nt;
+      if (check_taps(h, who, of, a, (size_t)per * nt, tap_index + n_taps, tap_weight + n_taps, ext[a])) return -1;
+      n_taps += (size_t)per * nt;
       nodes *= nt;
     }
     T->out_off[c] = T->nodes;
@@ -3563,6 +3583,7 @@ int fdtd_add_monitor(FdtdSolver* h, int kind, int n_comps, const int32_t* comps,
   if (kind == FDTD_MON_FLUX_TIME) return fail(h, "fdtd_add_monitor: FDTD_MON_FLUX_TIME monitors are added by fdtd_add_flux_time_monitor");
   if (kind == FDTD_MON_TIME_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_TIME_SPARSE monitors are added by fdtd_add_field_time_monitor");
   if (kind == FDTD_MON_DFT_SPARSE) return fail(h, "fdtd_add_monitor: FDTD_MON_DFT_SPARSE monitors are added by fdtd_add_field_dft_monitor");
+  if (kind == FDTD_MON_DFT_LATTICE) return fail(h, "fdtd_add_monitor: FDTD_MON_DFT_LATTICE monitors are added by fdtd_add_lattice_dft_monitor");
   if (kind != FDTD_MON_TIME && kind != FDTD_MON_DFT) return fail(h, "fdtd_add_monitor: bad kind %d", kind);
   Monitor m;
   int ext[3];
@@ -3658,23 +3679,24 @@ int fdtd_add_field_time_monitor(FdtdSolver* h, int n_comps, const int32_t* comps
   return monitor_end(h, m);
 }
 
-int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
-                               int64_t n_rec, const int64_t* steps, const int32_t* n_targets, const int32_t* tap_index,
-                               const float* tap_weight, int nf, const float* phase_e, const float* phase_h) {
-  if (!h) return -1;
-  const char* who = "fdtd_add_field_dft_monitor";
+}  // extern "C"
+namespace {
+// fdtd_add_field_dft_monitor and fdtd_add_lattice_dft_monitor: accumulators on the kept nodes alone, `per` taps per node and axis
+int add_sparse_dft(FdtdSolver* h, const char* who, MonForm form, int per, int n_comps, const int32_t* comps, const int32_t lo[3],
+                   const int32_t hi[3], int64_t n_rec, const int64_t* steps, const int32_t* n_targets, const int32_t* tap_index,
+                   const float* tap_weight, int nf, const float* phase_e, const float* phase_h) {
   Monitor m;
   int ext[3];
   if (monitor_begin(h, who, "box", n_comps, comps, lo, hi, n_rec, steps, &m, ext)) return -1;
   if (!n_targets || !tap_index || !tap_weight || (n_rec && (!phase_e || !phase_h))) return fail(h, "%s: bad argument", who);
   if (nf < 1) return fail(h, "%s: a DFT monitor needs frequencies", who);
   m.kind = FDTD_MON_DFT;
-  m.form = MonForm::SparseDft;
+  m.form = form;
   m.nf = nf;
   skip_done_steps(h, m);
   // (like fdtd_add_monitor: what a failure below has allocated stays with the handle until fdtd_destroy)
   FieldDftP& p = m.dp;
-  if (tap_tables(h, who, m, ext, n_targets, tap_index, tap_weight, &p.t)) return -1;
+  if (tap_tables(h, who, m, ext, n_targets, tap_index, tap_weight, &p.t, per)) return -1;
   m.data_bytes = (size_t)nf * (size_t)p.t.nodes * sizeof(float2);
   if (dev_alloc(h, &p.acc, (size_t)nf * (size_t)p.t.nodes)) return -1;
   m.data = p.acc;
@@ -3685,6 +3707,25 @@ int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps,
   took(h, m, kBytesTables);
   p.nf = nf;
   return monitor_end(h, m);
+}
+}  // namespace
+extern "C" {
+
+int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
+                               int64_t n_rec, const int64_t* steps, const int32_t* n_targets, const int32_t* tap_index,
+                               const float* tap_weight, int nf, const float* phase_e, const float* phase_h) {
+  if (!h) return -1;
+  return add_sparse_dft(h, "fdtd_add_field_dft_monitor", MonForm::SparseDft, 2, n_comps, comps, lo, hi, n_rec, steps, n_targets, tap_index,
+                        tap_weight, nf, phase_e, phase_h);
+}
+
+int fdtd_add_lattice_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
+                                 int64_t n_rec, const int64_t* steps, const int32_t* n_targets, int n_taps, const int32_t* tap_index,
+                                 const float* tap_weight, int nf, const float* phase_e, const float* phase_h) {
+  if (!h) return -1;
+  if (n_taps != kLatticeTaps) return fail(h, "fdtd_add_lattice_dft_monitor: n_taps must be %d, got %d", kLatticeTaps, n_taps);
+  return add_sparse_dft(h, "fdtd_add_lattice_dft_monitor", MonForm::LatticeDft, kLatticeTaps, n_comps, comps, lo, hi, n_rec, steps, n_targets,
+                        tap_index, tap_weight, nf, phase_e, phase_h);
 }
 
 int fdtd_get_monitor_bytes(FdtdSolver* h, int id, int64_t out[4]) {

@@ -356,6 +356,24 @@ def colocation_taps(spec: SolverSpec, fp: FieldPlan, fname: str, extents):
     return out
 
 
+def lattice_taps(spec: SolverSpec, fp: FieldPlan, fname: str, extents, pts):
+    """Colocation of ``fname`` to the primal nodes (``colocation_taps``) followed by the resampling of those nodes to the lattice
+    ``pts`` = [x, y, z] (``interp_axis``: held constant beyond the ends), as one table: per axis (index int32 [n, 4], weight
+    float64 [n, 4]) into the raw box.  For a lattice point between the colocated nodes j and j + 1 the slots are, in this order,
+    node j tap 0, node j tap 1, node j + 1 tap 0, node j + 1 tap 1, each weight (1 - w) or w times the colocation weight (the
+    product formed in float64).  Equal indices are not merged: the order of the sum is part of the result.  Along the normal
+    axis — one node, the plane position — the last two slots carry weight 0.  A slot of weight 0 carries an index inside the
+    box; the closings ``colocation_taps`` folds in carry over.  What csrc/fdtd_lattice_dft.hpp accumulates with."""
+    out = []
+    for a, (jc, wc) in enumerate(colocation_taps(spec, fp, fname, extents)):
+        jl, wl = interp_taps(fp.target[fname][a], pts[a])
+        jl = np.asarray(jl, dtype=np.int64)
+        idx = np.stack([jc[jl[:, 0], 0], jc[jl[:, 0], 1], jc[jl[:, 1], 0], jc[jl[:, 1], 1]], axis=1)
+        w = np.stack([wl[:, 0] * wc[jl[:, 0], 0], wl[:, 0] * wc[jl[:, 0], 1], wl[:, 1] * wc[jl[:, 1], 0], wl[:, 1] * wc[jl[:, 1], 1]], axis=1)
+        out.append((idx.astype(np.int32), np.asarray(w, np.float64)))
+    return out
+
+
 def _extended_subspace(coords: np.ndarray, ind_beg: int, ind_end: int, periodic: bool) -> np.ndarray:
     """Boundaries [ind_beg, ind_end) with out-of-range indices padded by the periodic image or the
     mirror image about the end planes (ref grid.py:546-603)."""
@@ -490,7 +508,8 @@ def _field_container(cls, mon, spec: SolverSpec, fp: FieldPlan, raw: np.ndarray,
                      lead_coords: np.ndarray, sim_center, dtype, full=None):
     """``full`` = (FieldPlan on the full grid, full-grid spec, symmetry) when the solver ran on the
     symmetry-reduced domain.  A two-dimensional ``raw`` [lead, kept nodes of all fields] is what the device has gathered onto the
-    target coordinates already (MonitorSpec kinds "time_sparse", "dft_sparse"): nothing is interpolated here."""
+    target coordinates already (MonitorSpec kinds "time_sparse", "dft_sparse"; "dft_lattice" with the lattice as ``fp.target``): nothing
+    is interpolated here."""
     kw = {}
     off = 0
     for ic, fname in enumerate(fp.fields):

@@ -136,7 +136,7 @@ def gather_results(eng: HipEngine) -> Optional[Dict[str, np.ndarray]]:
 def slab_discretization(sim, n_steps: Optional[int] = None):
     """The discretization of a z-slab run.  FluxTimeMonitors stay on the host path whatever their size: the device reduction
     (MonitorSpec kind "flux_time") needs the whole surface on one GPU, and the engine refuses it on a slab.  FieldTimeMonitors
-    likewise: the device gather (kind "time_sparse") needs the whole box on one GPU; and FieldMonitors (kind "dft_sparse")."""
+    likewise: the device gather (kind "time_sparse") needs the whole box on one GPU; and FieldMonitors (kind "dft_sparse") and projection monitors (kind "dft_lattice")."""
     from .discretize import DevicePaths, discretize
     return discretize(sim, n_steps=n_steps, device_paths=DevicePaths.all_host())
 

@@ -300,6 +300,7 @@ _DEVICE_KINDS = {
     "flux_time": ("FluxTimeMonitor reduced", np.float32, lambda m: (len(m.steps),)),
     "time_sparse": ("FieldTimeMonitor gathered", np.float32, lambda m: (len(m.steps), sum(int(np.prod(t)) for t in m.targets))),
     "dft_sparse": ("FieldMonitor accumulated", np.complex64, lambda m: (len(m.freqs), sum(int(np.prod(t)) for t in m.targets))),
+    "dft_lattice": ("projection monitor accumulated on its lattice", np.complex64, lambda m: (len(m.freqs), sum(int(np.prod(t)) for t in m.targets))),
 }
 
 
@@ -634,7 +635,7 @@ class HipEngine:
         set-up, or between runs.  Between runs a time or DFT monitor's first record step must lie behind the steps done (the
         library waits for its first step for ever otherwise); a flux-time or sparse field-time monitor skips the steps already
         done — their entries of the result stay zero — and records the rest: the tail of the series of a monitor present from the
-        start; a sparse DFT monitor skips them too and accumulates from then on."""
+        start; a sparse or lattice DFT monitor skips them too and accumulates from then on."""
         d, h, spec = self.lib.dll, self.handle, self.spec
         z0, z1, nz = self.z0, self.z1, spec.shape[2]
         uz = (2 - self.axis_shift) % 3            # the device axis that holds the user's z
@@ -660,12 +661,14 @@ class HipEngine:
                 else:
                     n_t = np.asarray(m.targets, dtype=np.int32)
                     tidx, tw = _flat_taps(t[a] for t in m.taps for a in range(3))
-                    args = (len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t), _ptr(tidx), _ptr(tw))
+                    args = (len(comps), _ptr(comps), _ptr(lo), _ptr(hi), len(steps), _ptr(steps), _ptr(n_t))
                     if m.kind == "time_sparse":
-                        name, args = "fdtd_add_field_time_monitor", args + (int(m.staging_bytes),)
+                        name, args = "fdtd_add_field_time_monitor", args + (_ptr(tidx), _ptr(tw), int(m.staging_bytes))
                     else:
                         pe, ph = _cplx_f32(m.phase_e), _cplx_f32(m.phase_h)
-                        name, args = "fdtd_add_field_dft_monitor", args + (len(m.freqs), _ptr(pe), _ptr(ph))
+                        name, taps = {"dft_sparse": ("fdtd_add_field_dft_monitor", ()),
+                                      "dft_lattice": ("fdtd_add_lattice_dft_monitor", (int(np.shape(m.taps[0][0][0])[1]),))}[m.kind]
+                        args = args + taps + (_ptr(tidx), _ptr(tw), len(m.freqs), _ptr(pe), _ptr(ph))
                 mid = getattr(d, name)(h, *args)
                 self._chk(mid, name)
                 self.mon_ids.append((m, mid, (lo2, hi2)))
@@ -790,7 +793,7 @@ class HipEngine:
         """name -> (array over the slab-local part of the box, (z_lo, z_hi) global plane range).
         time: float32 [n_rec, n_comps, bz, by, bx]; dft: complex64 [nf, n_comps, bz, by, bx]; flux_time: float32 [n_rec];
         time_sparse: float32 [n_rec, kept nodes of all components] (each component [nz_t, ny_t, nx_t], on the user's axes);
-        dft_sparse: complex64 [nf, kept nodes of all components], laid out likewise."""
+        dft_sparse, dft_lattice: complex64 [nf, kept nodes of all components], laid out likewise."""
         out = {}
         for m, mid, (lo2, hi2) in self.mon_ids:
             if mid < 0:
@@ -824,7 +827,7 @@ class HipEngine:
     def monitor_bytes(self, name: str, detail: bool = False):
         """Device memory, as allocated, of the monitor ``name`` (all surfaces ``name::*`` of a flux monitor): bytes, or with ``detail``
         a dict total / records (time and DFT buffers, the staging ring of a flux-time surface) / series (reduced flux, gathered
-        field-time nodes, the accumulators of a sparse DFT monitor) / tables."""
+        field-time nodes, the accumulators of a sparse or lattice DFT monitor) / tables."""
         tot = np.zeros(4, dtype=np.int64)
         hit = False
         for m, mid, _ in self.mon_ids:

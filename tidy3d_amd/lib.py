@@ -40,11 +40,11 @@ SYMBOLS = (
     "fdtd_comm_init", "fdtd_run", "fdtd_run_bloch", "fdtd_get_stats", "fdtd_reset", "fdtd_set_option",
     "fdtd_far_field", "fdtd_set_mirror_plus", "fdtd_add_aniso", "fdtd_add_aniso_bloch", "fdtd_get_seam_stats",
     "fdtd_get_sweep_words", "fdtd_sweep_table", "fdtd_add_flux_time_monitor", "fdtd_get_monitor_bytes",
-    "fdtd_add_field_time_monitor", "fdtd_add_field_dft_monitor",
+    "fdtd_add_field_time_monitor", "fdtd_add_field_dft_monitor", "fdtd_add_lattice_dft_monitor",
 )
 
 BC_PEC, BC_PMC, BC_PERIODIC, BC_NEIGHBOR = 0, 1, 2, 3
-MON_TIME, MON_DFT, MON_FLUX_TIME, MON_TIME_SPARSE, MON_DFT_SPARSE = 0, 1, 2, 3, 4
+MON_TIME, MON_DFT, MON_FLUX_TIME, MON_TIME_SPARSE, MON_DFT_SPARSE, MON_DFT_LATTICE = 0, 1, 2, 3, 4, 5
 VARIANT_AUTO, VARIANT_SIMPLE, VARIANT_ZMARCH, VARIANT_FUSED = 0, 1, 2, 3
 FLAG_TIME_KERNELS = 1
 OPT_FLAGS, OPT_VARIANT, OPT_ZCHUNK, OPT_ROWS, OPT_XCD_REMAP, OPT_FUSED_LB, OPT_PML_FUSED, OPT_BND_PLANES, OPT_AUTOTUNE, OPT_PML_SPLIT, OPT_LDS_PAD, OPT_MEM_HINTS, OPT_PLACEMENT_TRIES, OPT_TBLOCK, OPT_EDGE_ZCHUNK, OPT_GRAPH, OPT_TWOSTEP, OPT_SHELL_PAIRS, OPT_STRIP, OPT_SHELL2, OPT_SHELL2_SHAPE, OPT_DEBUG_SYNC, OPT_TILE_SPLIT, OPT_DISP, OPT_WHATIF, OPT_SRC_PAGED, OPT_SLAB_BOXES_FIRST, OPT_SEAM_DEFER, OPT_AXIS_SHIFT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28
@@ -135,6 +135,7 @@ class FdtdLib:
         d.fdtd_add_flux_time_monitor.argtypes = [vp, C.c_int, C.c_float, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64]
         d.fdtd_add_field_time_monitor.argtypes = [vp, C.c_int, vp, vp, vp, i64, vp, vp, vp, vp, i64]
         d.fdtd_add_field_dft_monitor.argtypes = [vp, C.c_int, vp, vp, vp, i64, vp, vp, vp, vp, C.c_int, vp, vp]
+        d.fdtd_add_lattice_dft_monitor.argtypes = [vp, C.c_int, vp, vp, vp, i64, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
         d.fdtd_get_monitor_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
         d.fdtd_set_field.argtypes = [vp, C.c_int, vp, C.c_size_t]
         d.fdtd_get_field.argtypes = [vp, C.c_int, vp, C.c_size_t]

@@ -58,11 +58,38 @@ def _trapz2(f: np.ndarray, u: np.ndarray, v: np.ndarray) -> complex:
     return _trap(g, v, axis=0) if len(v) > 1 else g[0]
 
 
+def surface_lattice(sim, mon, box, axis: int, medium=None):
+    """The sample points [x, y, z] of one surface ``box`` (normal ``axis``) of the projection monitor ``mon``: a regular lattice of
+    ``PTS_PER_WVL`` points per wavelength — the wavelength at the monitor's highest frequency in the projection ``medium`` (None:
+    the monitor's, or the simulation's where it has none) — over the surface clipped to the simulation domain, at least 2 points
+    per direction; the plane position along the normal (ref field_projection.py:280-349).  Serves planning (discretize.plan_monitors:
+    the lattice the device accumulates on) and assembly (``_surface_currents``) alike."""
+    if medium is None:
+        medium = mon.medium if mon.medium is not None else sim.medium
+    freqs = np.asarray(mon.freqs, float)
+    n_idx = float(np.real(np.sqrt(complex(np.asarray(medium.eps_model(float(freqs.max()))).ravel()[0]))))
+    wavelength = C_0 / float(freqs.max()) / n_idx
+    pts = [None, None, None]
+    pts[axis] = np.array([box.center[axis]])
+    for a in range(3):
+        if a == axis:
+            continue
+        start = max(box.center[a] - box.size[a] / 2.0, sim.center[a] - sim.size[a] / 2.0)
+        stop = min(box.center[a] + box.size[a] / 2.0, sim.center[a] + sim.size[a] / 2.0)
+        n_pts = int(np.ceil(PTS_PER_WVL * (stop - start) / wavelength))
+        pts[a] = np.linspace(start, stop, max(n_pts, 2)) if stop > start else np.array([start])
+    return pts
+
+
 def _surface_currents(disc, plan, raw, norm, medium):
     """Per surface of the monitor: (axis, u, v, sample points [3 arrays], J {axis: (u, v, f)}, M {...}):
     equivalent currents J = n x H, M = -n x E (ref field_projection.py:231-278) on a regular lattice of
-    10 points per wavelength clipped to the simulation domain (ref :280-349)."""
+    10 points per wavelength clipped to the simulation domain (ref :280-349).  A surface accumulated on the device (MonitorSpec
+    kind "dft_lattice": a two-dimensional raw array) holds the values on the lattice of the plan already: nothing is colocated or
+    resampled here, and a ``medium`` whose lattice differs from the recorded one is an error."""
+    import dataclasses
     from .data import FieldData, _field_container, interp_axis
+    from .exceptions import DataError
     mon, sim, spec = plan.monitor, disc.sim, disc.spec
     freqs = np.asarray(mon.freqs, float)
     names = "xyz"
@@ -77,18 +104,19 @@ def _surface_currents(disc, plan, raw, norm, medium):
         m = _M()
         m.size, m.center, m.geometry, m.name = box.size, box.center, box, fp.spec_name
         full = None if pfull is None else (pfull.fields[isurf], disc.spec_full, sym)
+        u, v = [a for a in range(3) if a != axis]
+        pts = surface_lattice(sim, mon, box, axis, medium)
+        on_lattice = np.ndim(raw[fp.spec_name]) == 2
+        if on_lattice:
+            rec = plan.lattices[isurf] if plan.lattices is not None else None
+            if rec is None or any(len(p) != len(q) or not np.array_equal(p, q) for p, q in zip(rec, pts)):
+                raise DataError(f"monitor '{fp.spec_name}' was accumulated on the device on the sampling lattice of its recorded "
+                                f"projection medium ({[len(p) for p in rec] if rec is not None else None} points); the medium asked "
+                                f"for gives another lattice ({[len(p) for p in pts]} points), and the data are not re-sampled: "
+                                "run with projection_device=False to re-project in another medium")
+            fp = dataclasses.replace(fp, target={f: list(rec) for f in fp.fields})      # the values lie on the lattice
         fd = _field_container(FieldData, m, spec, fp, raw[fp.spec_name], "f", freqs, sim.center,
                               np.complex128, full).normalize(norm)
-        u, v = [a for a in range(3) if a != axis]
-        n_idx = float(np.real(np.sqrt(complex(np.asarray(medium.eps_model(float(freqs.max()))).ravel()[0]))))
-        wavelength = C_0 / float(freqs.max()) / n_idx
-        pts = [None, None, None]
-        pts[axis] = np.array([box.center[axis]])
-        for a in (u, v):
-            start = max(box.center[a] - box.size[a] / 2.0, sim.center[a] - sim.size[a] / 2.0)
-            stop = min(box.center[a] + box.size[a] / 2.0, sim.center[a] + sim.size[a] / 2.0)
-            n_pts = int(np.ceil(PTS_PER_WVL * (stop - start) / wavelength))
-            pts[a] = np.linspace(start, stop, max(n_pts, 2)) if stop > start else np.array([start])
         # J = n x H, M = -n x E with the reference's sign table (ref :247-265)
         signs = np.array([-1.0, 1.0])
         if axis % 2 != 0:
@@ -99,6 +127,8 @@ def _surface_currents(disc, plan, raw, norm, medium):
 
         def sampled(comp):
             arr = np.asarray(fd[comp].values)                         # (x, y, z, f) on the colocated nodes
+            if on_lattice:                                            # ... on the lattice: what the host path interpolates to, complex128
+                return np.take(arr, 0, axis=axis).astype(np.complex128)
             for a in (u, v):
                 arr = interp_axis(arr, np.asarray(fd[comp].coords[names[a]]), pts[a], axis=a)
             return np.take(arr, 0, axis=axis)                         # (u, v, f) in x, y, z order

@@ -137,7 +137,7 @@ class TfsfSpec:
 
 
 # MonitorSpec kinds whose result holds the kept nodes only, interpolated on the device by per-component ``taps``
-SPARSE_KINDS = ("time_sparse", "dft_sparse")
+SPARSE_KINDS = ("time_sparse", "dft_sparse", "dft_lattice")
 
 
 @dataclass
@@ -160,7 +160,10 @@ class MonitorSpec:
     kind "dft_sparse": a running DFT accumulated on the nodes the user keeps only (csrc/fdtd_field_dft.hpp): complex64 [nf, sum over
                  ``comps`` of the component's kept nodes], inside a frequency the components one after the other, each
                  [nz_t][ny_t][nx_t].  Recorded like kind "dft" (``freqs``, ``phase_e``, ``phase_h``); every sample is interpolated onto
-                 the kept nodes by ``taps`` (as kind "time_sparse") before it is accumulated."""
+                 the kept nodes by ``taps`` (as kind "time_sparse") before it is accumulated.
+    kind "dft_lattice": one surface of a projection monitor accumulated on its sampling lattice only (csrc/fdtd_lattice_dft.hpp):
+                 everything as kind "dft_sparse", but ``taps`` carry four taps per node and axis (``data.lattice_taps``: colocation to
+                 the primal nodes followed by the resampling to the lattice) and the kept nodes are the lattice points."""
 
     kind: str
     comps: Tuple[int, ...]
@@ -180,12 +183,13 @@ class MonitorSpec:
     sign: float = 1.0                                   # its orientation
     taps: Optional[Tuple] = None                        # per axis (index int32 [4, n_t, 2], weight float64 [4, n_t, 2]) into the box, components as ``comps``
     #                                                     kinds "time_sparse", "dft_sparse": per component of ``comps``, per axis (index int32 [n_t, 2], weight float64 [n_t, 2])
+    #                                                     kind "dft_lattice": likewise, [n_t, 4]
     weights: Optional[Tuple] = None                     # per axis float64 [n_t] integration weights ([1.] along the normal)
     staging_bytes: int = 0                              # device staging budget (0: the library's default)
 
     @property
     def targets(self) -> Tuple[Tuple[int, int, int], ...]:
-        """kinds "time_sparse", "dft_sparse": (nx_t, ny_t, nz_t) kept nodes of every component."""
+        """kinds "time_sparse", "dft_sparse", "dft_lattice": (nx_t, ny_t, nz_t) kept nodes of every component."""
         return tuple(tuple(int(len(t[a][0])) for a in range(3)) for t in self.taps)
 
     @property
