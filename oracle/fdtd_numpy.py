@@ -194,8 +194,8 @@ class OracleFdtd:
         # HIP engine carries them as a (Re, Im) pair of real solvers (fdtd_run_bloch)
         self.bloch = getattr(spec, "bloch", None)
         self.rdtype = dtype
-        if self.bloch is not None:
-            dtype = np.complex128
+        if self.bloch is not None:          # (an fp32 oracle stores complex fields in fp32 parts as it stores real ones)
+            dtype = np.complex64 if np.dtype(dtype) == np.float32 else np.complex128
         self.dtype = dtype
         nx, ny, nz = spec.shape
         shp = (nz, ny, nx)
