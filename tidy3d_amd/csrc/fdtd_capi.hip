@@ -836,9 +836,14 @@ int launch_fused_range(FdtdSolver* h, hipStream_t st, const FusedRange& r) {
   const PmlP* pm = pml_inside ? ((sh && sh->pm) ? sh->pm : h->pml_blk[pml_inside][sh ? sh->parity : h->pml_parity][h->pml_e_parity]) : nullptr;
   const FieldP fa = sh ? sh->src : h->f, fb = sh ? sh->dst : h->f2;
   const int ex_j0 = sh ? sh->ex_j0 : 0, ex_j1 = sh ? sh->ex_j1 : 0;
+  // MATV: 0 = uniform medium, 1 = packed words + LDS table, 2 = the wide table (WIDE: the same (LB, PML, HINT) forms)
+#define FDTD_LAUNCH_FUSED_ARGS grid, block, shmem, st, g, fa, fb, s, m, kbeg, \
+                     kend, zc, pmc, nbx, nby, nbz, remap, pm, nbz1, k2beg, k2end, ty_a, ty_gap, ex_j0, ex_j1
 #define FDTD_LAUNCH_FUSED_H(MATV, LBV, PMLV, HV)                                                       \
-  hipLaunchKernelGGL((fused_step_kernel<MATV, LBV, PMLV, HV>), grid, block, shmem, st, g, fa, fb, s, m, kbeg, \
-                     kend, zc, pmc, nbx, nby, nbz, remap, pm, nbz1, k2beg, k2end, ty_a, ty_gap, ex_j0, ex_j1)
+  do {                                                                                                \
+    if (MATV == 2) hipLaunchKernelGGL((fused_step_kernel<true, LBV, PMLV, HV, true>), FDTD_LAUNCH_FUSED_ARGS); \
+    else hipLaunchKernelGGL((fused_step_kernel<(MATV != 0), LBV, PMLV, HV>), FDTD_LAUNCH_FUSED_ARGS);   \
+  } while (0)
   // Non-temporal field stores (FDTD_OPT_MEM_HINTS) in the instantiations WITHOUT CPML only: measured inside one engine
   // (profiles/r02z_probe_same_engine_cache_hints.jsonl) they take 2.1 % off the plain sweep and 3.1 % off the one with
   // materials, and ADD 13 % to the CPML-carrying ones (2-3 waves per SIMD: the slower store completion is not hidden).
@@ -857,18 +862,25 @@ int launch_fused_range(FdtdSolver* h, hipStream_t st, const FusedRange& r) {
     else if (PMLV != 0 && h->mem_hints) FDTD_LAUNCH_FUSED_H(MATV, LBV, PMLV, 128);                    \
     else FDTD_LAUNCH_FUSED_H(MATV, LBV, PMLV, 0);                                                     \
   } while (0)
+  const bool wide = h->mat4 && h->mat4b;
   if (pml_inside == 1) {        // x recursions only: every tile of a grid with x layers
-    if (h->mat4) { if (lb == 256) FDTD_LAUNCH_FUSED(true, 256, 1); else FDTD_LAUNCH_FUSED(true, 512, 1); }
-    else { if (lb == 256) FDTD_LAUNCH_FUSED(false, 256, 1); else FDTD_LAUNCH_FUSED(false, 512, 1); }
+    if (wide) { if (lb == 256) FDTD_LAUNCH_FUSED(2, 256, 1); else FDTD_LAUNCH_FUSED(2, 512, 1); }
+    else if (h->mat4) { if (lb == 256) FDTD_LAUNCH_FUSED(1, 256, 1); else FDTD_LAUNCH_FUSED(1, 512, 1); }
+    else { if (lb == 256) FDTD_LAUNCH_FUSED(0, 256, 1); else FDTD_LAUNCH_FUSED(0, 512, 1); }
   } else if (pml_inside) {      // all axes (axes outside `pml_inside` have no members in the block)
-    if (h->mat4) { if (lb == 256) FDTD_LAUNCH_FUSED(true, 256, 7); else FDTD_LAUNCH_FUSED(true, 512, 7); }
-    else { if (lb == 256) FDTD_LAUNCH_FUSED(false, 256, 7); else FDTD_LAUNCH_FUSED(false, 512, 7); }
+    if (wide) { if (lb == 256) FDTD_LAUNCH_FUSED(2, 256, 7); else FDTD_LAUNCH_FUSED(2, 512, 7); }
+    else if (h->mat4) { if (lb == 256) FDTD_LAUNCH_FUSED(1, 256, 7); else FDTD_LAUNCH_FUSED(1, 512, 7); }
+    else { if (lb == 256) FDTD_LAUNCH_FUSED(0, 256, 7); else FDTD_LAUNCH_FUSED(0, 512, 7); }
+  } else if (wide) {
+    if (lb == 256) FDTD_LAUNCH_FUSED(2, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(2, 512, 0); else FDTD_LAUNCH_FUSED(2, 1024, 0);
   } else if (h->mat4) {
-    if (lb == 256) FDTD_LAUNCH_FUSED(true, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(true, 512, 0); else FDTD_LAUNCH_FUSED(true, 1024, 0);
+    if (lb == 256) FDTD_LAUNCH_FUSED(1, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(1, 512, 0); else FDTD_LAUNCH_FUSED(1, 1024, 0);
   } else {
-    if (lb == 256) FDTD_LAUNCH_FUSED(false, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(false, 512, 0); else FDTD_LAUNCH_FUSED(false, 1024, 0);
+    if (lb == 256) FDTD_LAUNCH_FUSED(0, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(0, 512, 0); else FDTD_LAUNCH_FUSED(0, 1024, 0);
   }
 #undef FDTD_LAUNCH_FUSED
+#undef FDTD_LAUNCH_FUSED_H
+#undef FDTD_LAUNCH_FUSED_ARGS
   time_end(h, st);
   return 0;
 }
@@ -980,6 +992,9 @@ bool fused2_shape(const FdtdSolver* h, int* W, int* zc, const ClipP* box = nullp
 // from it.  CPML is not a reason here: the caller then asks shell_eligible.
 int fused2_why_not(const FdtdSolver* h, bool slab_rank = false, bool shell = false) {
   if (h->twostep_w == 0) return FDTD_F2_OFF_DISABLED;
+  // (first of the problem's own reasons: no two-step sweep, strip or shell box reads the second word per cell, and every pair
+  //  form asks here — shell_why_not, shell2_why_not, the z-slab pairs — before it launches anything)
+  if (h->mat4b) return FDTD_F2_OFF_WIDE_TABLE;
   { int W, zc; if (!fused2_shape(h, &W, &zc)) return FDTD_F2_OFF_TOO_SMALL; }
   if (h->comm && !slab_rank) return FDTD_F2_OFF_COMM;
   // (a shell pair: the planes that hold dispersive cells are a z hole of the bulk; round 6: the pair advances them itself once
@@ -3187,13 +3202,22 @@ int upload_material(FdtdSolver* h, const T* mat, size_t count) {
     h->mat4b = base_b + g.sxy;
   }
   const int nbx = (g.nx + 255) / 256;
+  // (wide layout: a segment's word is the 10-bit packed word of the triple all its cells share — BOTH words of every cell agree — when
+  //  its three indices are <= 1023, as those of the background and of ordinary structures are; anything else is kMixedWord.  A packed
+  //  word never has its top two bits set.  the WIDE form of fused_step_kernel reads these; the two-pass kernels read none.)
   std::vector<uint32_t> roww((size_t)g.nz * g.ny * nbx);
   for (size_t r = 0; r < (size_t)g.nz * g.ny; ++r)
     for (int bx = 0; bx < nbx; ++bx) {
       const uint32_t* row = dst + r * g.nx;
-      const int i1 = std::min(g.nx, (bx + 1) * 256);
-      uint32_t w = row[bx * 256];
-      for (int i = bx * 256 + 1; i < i1; ++i) if (row[i] != w) { w = kMixedWord; break; }
+      const int i0 = bx * 256, i1 = std::min(g.nx, (bx + 1) * 256);
+      uint32_t w = row[i0];
+      for (int i = i0 + 1; i < i1; ++i) if (row[i] != w) { w = kMixedWord; break; }
+      if (wide && w != kMixedWord) {
+        const uint32_t* row_b = dst_b + r * g.nx;
+        const uint32_t m0 = w & 0xFFFFu, m1 = w >> 16, m2 = row_b[i0];
+        for (int i = i0 + 1; i < i1; ++i) if (row_b[i] != m2) { w = kMixedWord; break; }
+        if (w != kMixedWord) w = (m0 < (uint32_t)kMaxMedia && m1 < (uint32_t)kMaxMedia && m2 < (uint32_t)kMaxMedia) ? (m0 | (m1 << 10) | (m2 << 20)) : kMixedWord;
+      }
       roww[r * nbx + bx] = w;
     }
   uint32_t* base = nullptr;

@@ -50,8 +50,10 @@ constexpr uint32_t kBgWord = 1u | (1u << 10) | (1u << 20);
 constexpr uint32_t kMixedWord = 0xFFFFFFFFu;
 // More than 1022 media (ref scene.py:52 allows 65530; a CustomMedium with thousands of distinct (permittivity, conductivity)
 // levels): the WIDE layout — 16-bit indices, two words per cell (m4: E_x | E_y << 16, m4b: E_z), coefficients read from the table in
-// global memory (it does not fit LDS).  Two-pass kernels only (e_update_kernel, the slab-form CPML): the sweeps keep the packed
-// 10-bit words and their LDS table; a run with a wide table takes FDTD_VARIANT_ZMARCH.
+// global memory (it does not fit LDS).  The two-pass kernels read it (e_update_kernel, the slab-form CPML), and so does the
+// single-step sweep (fused_step_kernel<true, ., ., ., WIDE>); the two-step and shell sweeps keep the packed 10-bit words and their LDS table.  In
+// the wide layout a row-segment word is still a 10-bit packed word — set where all cells of the segment share one triple of
+// indices <= 1023 (the background and ordinary structures come first in the table) — or kMixedWord.
 constexpr int kMaxMediaWide = 65531;
 struct MatP {
   const uint32_t* m4;             // packed material indices
@@ -511,7 +513,9 @@ __device__ __forceinline__ void pml_h_apply(float& h1, float& h2, float d1, floa
 //     first plane of a chunk recomputes H^{n+1/2}[k0-1] in a prologue).
 // Everything that depends on the row only (threadIdx.y is wave-uniform) is kept in SGPRs.
 // =============================================================================================
-template <bool MAT, int LB, int PML, int HINT = 0>   // PML: bit a set = CPML of axis a runs inside the sweep; HINT: bit 0 = non-temporal field stores, bit 1 = non-temporal loads of E_y, H_y (measured: +0.7 %, not instantiated), bit 3 = H stores ahead of the row exchange
+// WIDE (with MAT): the wide material layout — 16-bit indices, two words per cell, up to 65530 media (MatP) — with the (Ca, Cb) table
+// read from global memory instead of the LDS copy; the same (LB, PML, HINT) forms and register budgets as the packed-word form.
+template <bool MAT, int LB, int PML, int HINT = 0, bool WIDE = false>   // PML: bit a set = CPML of axis a runs inside the sweep; HINT: bit 0 = non-temporal field stores, bit 1 = non-temporal loads of E_y, H_y (measured: +0.7 %, not instantiated), bit 3 = H stores ahead of the row exchange
 __global__ __launch_bounds__(LB, (LB == 256 ? (PML == 0 ? 4 : (PML == 1 ? 3 : 2)) : (LB == 512 ? (PML ? 2 : 4) : 4))) void fused_step_kernel(GridP g, FieldP a, FieldP b, StepP s, MatP m,
                                                           int kbeg, int kend, int zchunk, int pmc_z0,
                                                           int nbx, int nby, int nbz, int xcd_remap,
@@ -519,6 +523,7 @@ __global__ __launch_bounds__(LB, (LB == 256 ? (PML == 0 ? 4 : (PML == 1 ? 3 : 2)
                                                           int nbz1, int k2beg, int k2end, int ty_a, int ty_gap,
                                                           int ex_j0, int ex_j1) {
   constexpr int V = 4;
+  static_assert(MAT || !WIDE, "the wide layout is a form of the materials sweep");
   // 1-D launch; logical tile (bx, by, bz) with by fastest.  Hardware block L runs on XCD L % 8 (observed dispatch
   // order, used for speed only); y-neighbouring tiles share their halo row, and meet in an XCD's L2 when they are
   // resident there at about the same time.  xcd_remap = 0: plain order (neighbours on different XCDs);
@@ -546,9 +551,9 @@ __global__ __launch_bounds__(LB, (LB == 256 ? (PML == 0 ? 4 : (PML == 1 ? 3 : 2)
   if (tile_y >= ty_a) tile_y += ty_gap;
   const int tile_x = (t / nby) % nbx;
   const int tile_z = t / (nby * nbx);
-  __shared__ float2 lut_s[MAT ? kMaxMedia : 1];
+  __shared__ float2 lut_s[MAT && !WIDE ? kMaxMedia : 1];
   HIP_DYNAMIC_SHARED(float4, xch)      // [2 buffers][2 comps][blockDim.y][64] (+ [6][64] x-CPML coefficients)
-  if constexpr (MAT) {
+  if constexpr (MAT && !WIDE) {
     for (int q = threadIdx.y * blockDim.x + threadIdx.x; q < m.n_media; q += blockDim.x * blockDim.y)
       lut_s[q] = m.lut[q];
   }
@@ -566,7 +571,7 @@ __global__ __launch_bounds__(LB, (LB == 256 ? (PML == 0 ? 4 : (PML == 1 ? 3 : 2)
       xco[q * 64 + threadIdx.x] = t4;
     }
   }
-  if constexpr (MAT || (PML & 1) != 0) __syncthreads();
+  if constexpr ((MAT && !WIDE) || (PML & 1) != 0) __syncthreads();
   const int tx = threadIdx.x;
   const int ty = __builtin_amdgcn_readfirstlane((int)threadIdx.y);     // one row per wave
   const int R = blockDim.y - 1;
@@ -794,10 +799,23 @@ __global__ __launch_bounds__(LB, (LB == 256 ? (PML == 0 ? 4 : (PML == 1 ? 3 : 2)
     // material row-segment word of this plane (scalar load) and, where the segment is mixed, the packed words
     [[maybe_unused]] uint32_t rw = kBgWord;
     [[maybe_unused]] uint32_t mw[V] = {kBgWord, kBgWord, kBgWord, kBgWord};
+    // wide layout: the second word per cell where the segment is mixed; else the segment's three table entries (its word names
+    // indices <= 1023 in 10-bit fields as ever), scalar loads that go out here with the plane's field loads
+    [[maybe_unused]] uint32_t mz[V] = {1u, 1u, 1u, 1u};
+    [[maybe_unused]] float2 cu0 = make_float2(m.ca1, m.cb1), cu1 = cu0, cu2 = cu0;
     if constexpr (MAT) {
       if (!halo && row_ok) {
         rw = m.roww[((long long)k * g.ny + j) * nbx + tile_x];
-        if (rw == kMixedWord && act) ldm<V>(mw, at(uni(m.m4 + pb), ub));
+        if constexpr (WIDE) {
+          if (rw != kMixedWord) {
+            cu0 = m.lut[rw & 1023u]; cu1 = m.lut[(rw >> 10) & 1023u]; cu2 = m.lut[(rw >> 20) & 1023u];
+          } else if (act) {
+            ldm<V>(mw, at(uni(m.m4 + pb), ub));
+            ldm<V>(mz, at(uni(m.m4b + pb), ub));
+          }
+        } else {
+          if (rw == kMixedWord && act) ldm<V>(mw, at(uni(m.m4 + pb), ub));
+        }
       }
     }
     float eyx = __shfl_down(eyk[0], 1);
@@ -899,6 +917,20 @@ __global__ __launch_bounds__(LB, (LB == 256 ? (PML == 0 ? 4 : (PML == 1 ? 3 : 2)
         stv_h<V, (HINT & 1) != 0>(b.hx + pb + i0, hxn);
         stv_h<V, (HINT & 1) != 0>(b.hy + pb + i0, hyn);
         stv_h<V, (HINT & 1) != 0>(b.hz + pb + i0, hzn);
+      }
+    }
+    // wide layout, mixed segment: (Ca, Cb) of the lane's twelve components, gathered from the table in global memory (vector
+    // caches: a 5000-entry table is 40 KiB).  Issued HERE, in front of the row exchange, so that the gather's round trip passes
+    // while the wave waits at the barrier; the H phase's temporaries are dead by now.
+    [[maybe_unused]] float2 cw[3][V];
+    if constexpr (WIDE) {
+      if (act && !halo && rw == kMixedWord) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          cw[0][e] = m.lut[mw[e] & 0xFFFFu];
+          cw[1][e] = m.lut[mw[e] >> 16];
+          cw[2][e] = m.lut[mz[e] & 0xFFFFu];
+        }
       }
     }
     // publish H^{n+1/2}_{x,z} of this row for the row above
@@ -1056,7 +1088,11 @@ __global__ __launch_bounds__(LB, (LB == 256 ? (PML == 0 ? 4 : (PML == 1 ? 3 : 2)
       }
     };
     if (act && !halo) {
-      if constexpr (MAT) {
+      if constexpr (WIDE) {
+        // the same shortcut with the wide layout: a segment's word, or kMixedWord and the coefficients gathered above
+        if (rw != kMixedWord) e_phase([&](int c, int) { return c == 0 ? cu0 : (c == 1 ? cu1 : cu2); });
+        else e_phase([&](int c, int e) { return cw[c][e]; });
+      } else if constexpr (MAT) {
         // one word per row segment (256 cells of one row): the medium word of all its cells when they
         // agree — then the packed words are not read at all — or kMixedWord (both fetched at the top of the plane)
         if (rw != kMixedWord) {

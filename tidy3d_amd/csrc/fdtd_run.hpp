@@ -138,11 +138,12 @@ struct Run {
     HIPCHK(h, hipEventRecord(h->ev0, st));
     if (multi && (nb_lo || nb_hi) && nz < 2) return fail(h, "fdtd_run: a z-slab needs at least 2 planes");
     // the fused sweep is the default single-GPU path whenever rows are float4-aligned
-    // (a wide material table — more than 1023 media — has no LDS copy and no packed 10-bit words: the two-pass kernels take it)
-    if (h->mat4b && h->cfg.variant == FDTD_VARIANT_FUSED)
-      return fail(h, "fdtd_run: more than %d media need the two-pass kernels (FDTD_VARIANT_ZMARCH / AUTO), not FDTD_VARIANT_FUSED", kMaxMedia - 1);
-    fused_ok = !h->mat4b && (h->g.nx % 4 == 0) && h->rows_f <= 15 &&
-                            (h->cfg.variant == FDTD_VARIANT_FUSED || h->cfg.variant == FDTD_VARIANT_AUTO);
+    // (a wide material table — more than 1023 media, 16-bit indices, no LDS copy: on one GPU the single-step sweep reads it on
+    //  request, fused_step_kernel<., WIDE>; AUTO here is the two-pass kernels — the caller decides, tidy3d_amd/engine.py — and so is a z-slab rank)
+    if (h->mat4b && multi && h->cfg.variant == FDTD_VARIANT_FUSED)
+      return fail(h, "fdtd_run: more than %d media on a z-slab need the two-pass kernels (FDTD_VARIANT_ZMARCH / AUTO), not FDTD_VARIANT_FUSED", kMaxMedia - 1);
+    fused_ok = (h->g.nx % 4 == 0) && h->rows_f <= 15 &&
+               (h->cfg.variant == FDTD_VARIANT_FUSED || (h->cfg.variant == FDTD_VARIANT_AUTO && !h->mat4b));
     fused = !multi && fused_ok;
     // with a communicator every rank must take the same path: the fused z-slab schedule runs only on
     // explicit request (the host decides for all ranks, tidy3d_amd/engine.py), AUTO = two-pass
@@ -447,7 +448,7 @@ struct Run {
     // paged source terms (round 6): a TFSF box, a mode plane, a current sheet, any list of more than kMaxInj nodes
     spg_ok = false;
     h->spg.pairs = 0;
-    if (fused && !tb_ok && !multi && (!h->tfsf.empty() || !h->psrc.empty())) {
+    if (fused && !tb_ok && !multi && !h->mat4b && (!h->tfsf.empty() || !h->psrc.empty())) {      // (a wide table: no pairs, nothing to page)
       if (fused2_sources(h)) return -1;            // (src_nodes, the seam flags)
       bool needs = !h->tfsf.empty() || h->src_nodes > kMaxInj || h->src_h_on_seam || (h->src_h_nodes > 0 && !h->src_tab);
       if (!needs) {                                // lists of different lengths: mixed alive / spent pairs

@@ -123,6 +123,17 @@ def balanced_slabs(spec: SolverSpec, n_ranks: int, min_planes: int = 4, pairs: b
     return [(edges[i], edges[i + 1]) for i in range(n_ranks)]
 
 
+# VARIANT_AUTO with a wide material table (more than 1023 media) on one GPU: the single-step fused sweep instead of the two-pass
+# kernels?  Set from the 320^3 measurement in docs/history/WIDE_SWEEP.md; below 2^20 cells a grid is bound by launches (the library's
+# FDTD_F2_OFF_TOO_SMALL line) and stays where it was.
+WIDE_SWEEP_AUTO = False
+WIDE_SWEEP_MIN_CELLS = 1 << 20
+
+
+def wide_sweep_pays(n_cells: int) -> bool:
+    return WIDE_SWEEP_AUTO and n_cells >= WIDE_SWEEP_MIN_CELLS
+
+
 def lane_efficiency(n: int) -> float:
     """Busy fraction of the 256-cell row segments (64 lanes x float4) the main kernels give a wavefront."""
     return n / (256.0 * -(-n // 256))
@@ -377,10 +388,21 @@ class HipEngine:
             cfg.bc[i] = int(b)
         if len(spec.media) > 1023:
             # a WIDE material table (more than 1022 media, ref scene.py:52 allows 65530): 16-bit indices, coefficients from global memory —
-            # the two-pass kernels take it; the sweeps keep their 10-bit words and LDS table (fdtd_kernels.hpp MatP)
-            if variant == L.VARIANT_FUSED:
-                raise ValueError("more than 1022 media need the two-pass kernels (VARIANT_AUTO / VARIANT_ZMARCH)")
-            variant = L.VARIANT_ZMARCH
+            # the two-pass kernels take it, or — one GPU, real fields, float4 rows — the single-step fused sweep (fused_step_kernel<., WIDE>:
+            # VARIANT_FUSED, and VARIANT_AUTO where wide_sweep_pays says so); step pairs keep their 10-bit words and LDS table
+            # (fdtd_kernels.hpp MatP), z-slab ranks and Bloch runs keep the two-pass kernels
+            one_gpu = not (n_ranks > 1 or force_comm) and spec.bloch is None and self.nxp % 4 == 0
+            if not one_gpu or variant != L.VARIANT_FUSED and variant != L.VARIANT_AUTO:
+                if variant == L.VARIANT_FUSED:      # asked for and not available: say so (the caller otherwise sees it in .variant only)
+                    import logging
+                    why = ("z-slab ranks" if (n_ranks > 1 or force_comm) else
+                           "Bloch boundaries" if spec.bloch is not None else "rows that are not a multiple of 4 cells (periodic x)")
+                    logging.getLogger("tidy3d_amd").warning(
+                        "VARIANT_FUSED was asked for with %d media: the wide-table fused sweep does not cover %s — the run takes "
+                        "the two-pass kernels (VARIANT_ZMARCH)." % (len(spec.media), why))
+                variant = L.VARIANT_ZMARCH
+            elif variant == L.VARIANT_AUTO:
+                variant = L.VARIANT_FUSED if wide_sweep_pays(self.nxp * ny * nz) else L.VARIANT_ZMARCH
         elif (n_ranks > 1 or force_comm) and spec.bloch is not None:
             variant = L.VARIANT_ZMARCH          # complex fields on z-slabs: two-pass kernels (fdtd_run_bloch)
         elif (n_ranks > 1 or force_comm) and variant in (L.VARIANT_AUTO, L.VARIANT_FUSED):
