@@ -135,7 +135,8 @@ enum { FDTD_F2_OFF_NONE = 0,
        FDTD_F2_OFF_VARIANT = 11,          /* the run is not on the fused sweep at all (two-pass kernels) */
        FDTD_F2_OFF_SHELL = 12,            /* CPML shell too large a part of the grid for shell pairs to pay (cost model, fdtd_capi.hip shell_why_not) */
        FDTD_F2_OFF_MEMORY = 13,           /* no room for the third field set that shell pairs / slab pairs keep the middle step in (+ 50 % field memory) */
-       FDTD_F2_OFF_WIDE_TABLE = 14 };     /* more than 1023 media (16-bit indices, two words per cell): the single-step sweep reads them, the two-step and shell sweeps do not */
+       FDTD_F2_OFF_WIDE_TABLE = 14,       /* more than 1023 media (16-bit indices, two words per cell): the single-step sweep reads them, the two-step and shell sweeps do not */
+       FDTD_F2_OFF_MODULATION = 15 };     /* time-modulated media (fdtd_add_modulation): their list kernels run in front of and behind every single step */
 
 /* progress callback: (step, time [s], field_decay) -> non-zero aborts the run (Ctrl-C path).
  * Mirrors the (perc_done, field_decay) pair the cloud reports (ref web/core/task_core.py:537). */
@@ -226,6 +227,25 @@ int fdtd_add_aniso(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t* cel
  * the two parts; fdtd_run ignores the codes (phase 0). */
 int fdtd_add_aniso_bloch(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t* cell_index, const uint32_t* nbr_index,
                          const float* w_new, const float* w_old, const uint8_t* wrap);
+
+/* time-modulated media (ref tidy3d components/time_modulation.py ModulationSpec on a Medium): n nodes of E component `comp` whose
+ * permittivity and / or conductivity follow
+ *     eps(t) = eps_bar + Re[d_eps exp(-i w_eps t)],    sigma(t) dt / (2 eps0) = s_bar + Re[d_s exp(-i w_sig t)]
+ * (d_eps, d_s: n complex values, re / im interleaved, the time modulation's amplitude and phase folded in; d_s = d_sigma dt / (2 eps0)).
+ * The sweep advances these nodes with their static table medium, E_lin = Ca E^n + Cb K; at the end of the E phase of step n the
+ * library replaces that by
+ *     E^{n+1} = alpha E^n + beta (E_lin - ca E^n),   alpha = (eps^n - s) / (eps^{n+1} + s),   beta = (eps_bar + s_bar) / (eps^{n+1} + s),
+ *     eps^n = eps(n dt),  eps^{n+1} = eps((n + 1) dt),  s = sigma((n + 1/2) dt) dt / (2 eps0)
+ * which is (D^{n+1} - D^n) / dt + sigma^{n+1/2} (E^{n+1} + E^n) / 2 = K with D = eps0 eps(t) E.  ca, eps_bar, s_bar: the node's own
+ * table coefficient Ca and the host's eps_bar = dt / (eps0 Cb) * 2 / (1 + Ca), s_bar = eps_bar (1 - Ca) / (1 + Ca).
+ * omega_eps, omega_sigma: the PHASE ADVANCE PER TIME STEP in radians, 2 pi f dt, of the two modulations (the library forms the phase
+ * of step n in double from the step count).  Cell indexing as in fdtd_add_aniso; a node is listed at most once per component; eps_bar +
+ * s_bar must exceed |d_eps| + |d_s|.  A handle with such a list takes single steps only (FDTD_F2_OFF_MODULATION), no captured graphs,
+ * no slab-interleaved schedule, and is refused on z-slabs (FDTD_BC_NEIGHBOR faces, fdtd_comm_init).  fdtd_run_bloch: give both handles
+ * the same lists — the update is linear with real coefficients, each part is patched on its own. */
+int fdtd_add_modulation(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t* cell_index, const float* ca, const float* eps_bar,
+                        const float* s_bar, const float* d_eps /* [2 n] */, const float* d_s /* [2 n] */, double omega_eps,
+                        double omega_sigma);
 
 /* current source: F[comp[p]][index[p]] += w_re[p]*Re(wave[n]) - w_im[p]*Im(wave[n]);
  * E components use wave_e (sampled at t_n + dt/2), H components wave_h (t_n);

@@ -22,6 +22,7 @@
 #include "fdtd_strip.hpp"
 #include "fdtd_shell2_host.hpp"
 #include "fdtd_aniso.hpp"
+#include "fdtd_modulation.hpp"
 #include "fdtd_flux_time.hpp"
 #include "fdtd_field_time.hpp"
 #include "fdtd_field_dft.hpp"
@@ -90,6 +91,15 @@ struct AnisoGroup {                 // fdtd_aniso.hpp: the off-diagonal coupling
   uint32_t *cell, *nbr;
   float *w_new, *w_old, *old, *delta;
   uint8_t* wrap;                    // [8n] wrap codes of the slots (fdtd_add_aniso_bloch), nullptr = none: read by fdtd_run_bloch only
+};
+
+struct ModGroup {                   // fdtd_modulation.hpp: the nodes of E component `comp` inside time-modulated media, structure of arrays
+  int comp;
+  long long n;
+  uint32_t* cell;
+  float *ca, *eps_bar, *s_bar, *old;
+  float2 *d_eps, *d_s;
+  double w_eps, w_sig;              // phase advance per time step (rad) of the permittivity / conductivity modulation
 };
 
 struct PointSrc {
@@ -241,6 +251,7 @@ struct FdtdSolver {
   int whatif = 0;                    // FDTD_OPT_WHATIF: a what-if instantiation of the vacuum two-step sweep (fdtd_kernels2.hpp; wrong results, meaningful times)
   int disp_on = -1;                  // FDTD_OPT_DISP: dispersive cells inside the two-step sweeps: -1 = default (on), 0 = off (their planes as z holes, round 5)
   std::vector<AnisoGroup> aniso;
+  std::vector<ModGroup> modulation;
   std::vector<PointSrc> psrc;
   std::vector<Tfsf> tfsf;
   std::vector<Monitor> mons;
@@ -1001,6 +1012,7 @@ int fused2_why_not(const FdtdSolver* h, bool slab_rank = false, bool shell = fal
   //  their memory terms are paged, disp_setup)
   if (!h->ade.empty() && !shell && h->disp.state != 1) return FDTD_F2_OFF_ADE;
   if (!h->aniso.empty()) return FDTD_F2_OFF_ADE;               // fully anisotropic bodies: their coupling follows every single step
+  if (!h->modulation.empty()) return FDTD_F2_OFF_MODULATION;   // time-modulated media: their list kernels follow every single step
   // (sources are judged step by step, fused2_sources_why_not: a TFSF box or a mode plane keeps single steps only while it injects)
   // PEC walls; the min faces may be PMC (the symmetry planes of a half / quarter / eighth domain)
   // (a z-slab rank: a neighbour face is no wall — the sweep stays two planes clear of it, fdtd_run)
@@ -2504,6 +2516,29 @@ void aniso_apply_bloch(FdtdSolver* hr, FdtdSolver* hi, const AnisoPhaseTab& tab,
                          (const float*)a.delta, a.n);
 }
 
+// time-modulated media: E^n of the listed nodes, saved in front of the E update ...
+void modulation_save(FdtdSolver* h, hipStream_t st) {
+  if (h->modulation.empty()) return;
+  dbg_sync(h);
+  for (ModGroup& m : h->modulation)
+    hipLaunchKernelGGL(modulation_save_kernel, dim3(nblk(m.n)), dim3(256), 0, st, (const float*)field_ptr(h, m.comp),
+                       (const uint32_t*)m.cell, m.old, m.n);
+}
+// ... and the update with eps(t), sigma(t) in place of the table update, at the END of the E phase of step n (behind CPML, sources,
+// damping and ADE; in front of the ghost fills).  The phases are formed in double from the step count: no drift over long runs.
+void modulation_apply(FdtdSolver* h, long long n, hipStream_t st) {
+  if (h->modulation.empty()) return;
+  dbg_sync(h);
+  for (ModGroup& m : h->modulation) {
+    const double t0 = m.w_eps * (double)n, t1 = m.w_eps * (double)(n + 1), th = m.w_sig * ((double)n + 0.5);
+    const ModPhase p{(float)std::cos(t0), (float)std::sin(t0), (float)std::cos(t1), (float)std::sin(t1), (float)std::cos(th),
+                     (float)std::sin(th)};
+    hipLaunchKernelGGL(modulation_apply_kernel, dim3(nblk(m.n)), dim3(256), 0, st, field_ptr(h, m.comp), (const uint32_t*)m.cell,
+                       (const float*)m.ca, (const float*)m.eps_bar, (const float*)m.s_bar, (const float2*)m.d_eps,
+                       (const float2*)m.d_s, (const float*)m.old, p, m.n);
+  }
+}
+
 void launch_ade(FdtdSolver* h, int kbeg, int kend, hipStream_t st, const FieldP* fs = nullptr) {
   dbg_sync(h);
   if (kend <= kbeg) return;
@@ -2544,7 +2579,7 @@ int disp_setup(FdtdSolver* h) {
   if (D.state != 0) return 0;
   D.state = -1;
   const GridP& g = h->g;
-  if (h->ade.empty() || h->disp_on == 0 || !h->mat4 || h->mat4b || h->comm || !h->aniso.empty() || g.nx % 4 != 0) return 0;
+  if (h->ade.empty() || h->disp_on == 0 || !h->mat4 || h->mat4b || h->comm || !h->aniso.empty() || !h->modulation.empty() || g.nx % 4 != 0) return 0;
   for (const AdeGroup& a : h->ade) if (!a.strict) return 0;
   const int nbx = (g.nx + 255) / 256;
   const size_t nseg = (size_t)g.nz * g.ny * nbx;
@@ -3397,6 +3432,37 @@ int fdtd_add_aniso_bloch(FdtdSolver* h, int comp, int64_t n, const uint32_t* cel
   return add_aniso(h, "fdtd_add_aniso_bloch", comp, n, cell_index, nbr_index, w_new, w_old, wrap);
 }
 
+int fdtd_add_modulation(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index, const float* ca, const float* eps_bar,
+                        const float* s_bar, const float* d_eps, const float* d_s, double omega_eps, double omega_sigma) {
+  if (!h) return -1;
+  if (comp < 0 || comp > 2) return fail(h, "fdtd_add_modulation: comp must be 0..2");
+  if (n <= 0) return 0;
+  if (h->comm) return fail(h, "fdtd_add_modulation: time-modulated media are not available on z-slabs");
+  for (int f = 4; f < 6; ++f)
+    if (h->cfg.bc[f] == FDTD_BC_NEIGHBOR) return fail(h, "fdtd_add_modulation: time-modulated media are not available on z-slabs");
+  if (!std::isfinite(omega_eps) || !std::isfinite(omega_sigma)) return fail(h, "fdtd_add_modulation: omega must be finite");
+  const uint64_t ncell = (uint64_t)n_cells(h);
+  for (int64_t i = 0; i < n; ++i) {
+    if (cell_index[i] >= ncell) return fail(h, "fdtd_add_modulation: cell index out of range");
+    // (the kernel divides by eps^{n+1} + s: the largest swing of both must leave it positive)
+    const double swing = std::hypot((double)d_eps[2 * i], (double)d_eps[2 * i + 1]) + std::hypot((double)d_s[2 * i], (double)d_s[2 * i + 1]);
+    if (!((double)eps_bar[i] + (double)s_bar[i] - swing > 0.0))
+      return fail(h, "fdtd_add_modulation: node %lld: eps_bar + s_bar = %g does not exceed the modulation's swing %g", (long long)i,
+                  (double)eps_bar[i] + (double)s_bar[i], swing);
+  }
+  // (a node listed twice in one component would be patched twice; the lists of one component come from disjoint media)
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  ModGroup m{};
+  m.comp = comp; m.n = n; m.w_eps = omega_eps; m.w_sig = omega_sigma;
+  if (dev_upload(h, &m.cell, cell_index, (size_t)n) || dev_upload(h, &m.ca, ca, (size_t)n) ||
+      dev_upload(h, &m.eps_bar, eps_bar, (size_t)n) || dev_upload(h, &m.s_bar, s_bar, (size_t)n) ||
+      dev_upload(h, &m.d_eps, reinterpret_cast<const float2*>(d_eps), (size_t)n) ||
+      dev_upload(h, &m.d_s, reinterpret_cast<const float2*>(d_s), (size_t)n) || dev_alloc(h, &m.old, (size_t)n))
+    return -1;
+  h->modulation.push_back(m);
+  return 0;
+}
+
 int fdtd_add_point_source(FdtdSolver* h, int64_t n, const int32_t* comp, const uint32_t* cell, const float* w_re,
                           const float* w_im, int64_t n_steps, const float* wave_e, const float* wave_h) {
   if (!h) return -1;
@@ -3834,6 +3900,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   ncclUniqueId u;
   std::memcpy(&u, id, 128);
   if (refuse_whole_grid_monitors(h, h, "fdtd_comm_init")) return -1;
+  if (!h->modulation.empty()) return fail(h, "fdtd_comm_init: time-modulated media are not available on z-slabs");
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)
@@ -3929,6 +3996,14 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
   const bool nb_lo = hr->cfg.bc[4] == FDTD_BC_NEIGHBOR, nb_hi = hr->cfg.bc[5] == FDTD_BC_NEIGHBOR;
   if ((nb_lo || nb_hi) && !multi) return fail(hr, "fdtd_run_bloch: neighbour faces need fdtd_comm_init on the first handle");
   if (multi && aniso) return fail(hr, "fdtd_run_bloch: fully anisotropic media are not available on z-slabs");
+  // time-modulated media: the update is linear with real coefficients — each part is patched by its own handle's lists, the same rows
+  const bool modulated = !hr->modulation.empty();
+  if (hi->modulation.size() != hr->modulation.size())
+    return fail(hr, "fdtd_run_bloch: the two solvers must carry the same time-modulation lists");
+  for (size_t k = 0; k < hr->modulation.size(); ++k)
+    if (hi->modulation[k].comp != hr->modulation[k].comp || hi->modulation[k].n != hr->modulation[k].n)
+      return fail(hr, "fdtd_run_bloch: the two solvers must carry the same time-modulation lists");
+  if (multi && modulated) return fail(hr, "fdtd_run_bloch: time-modulated media are not available on z-slabs");
   if (hi->cfg.bc[4] != hr->cfg.bc[4] || hi->cfg.bc[5] != hr->cfg.bc[5])
     return fail(hr, "fdtd_run_bloch: the two solvers must have the same z faces");
   if (hr->g.nx != hi->g.nx || hr->g.ny != hi->g.ny || hr->g.nz != hi->g.nz || hr->cfg.device != hi->cfg.device ||
@@ -3987,6 +4062,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
         launch_sources(h, true, n, 0, nz, st);
         launch_damp(h, true, 0, nz, st);
         launch_ade(h, 0, nz, st);
+        modulation_apply(h, n, st);
       }
       return;
     }
@@ -3998,6 +4074,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
     for (FdtdSolver* h : both) {
       launch_damp(h, true, 0, nz, st);
       launch_ade(h, 0, nz, st);
+      modulation_apply(h, n, st);
     }
   };
   const long long pc = plane_cells(hr);
@@ -4046,6 +4123,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
     for (Monitor& m : hr->mons) if (m.next < m.steps.size() && m.steps[m.next] == n) rec = true;
     if (rec) for (FdtdSolver* h : both) record_monitors(h, n, false, st);
     if (aniso) aniso_save_bloch(hr, hi, st);     // (E^n of the nodes around fully anisotropic cells, in front of either sweep)
+    for (FdtdSolver* h : both) modulation_save(h, st);      // (E^n of the nodes inside time-modulated media, likewise)
     // H-side corrections of both parts, then the ghost cells (they must carry the corrections too)
     for (FdtdSolver* h : both) {
       launch_damp(h, false, 0, nz, st);
@@ -4080,6 +4158,7 @@ int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double
           launch_sources(h, true, n, 0, nz, st);
           launch_damp(h, true, 0, nz, st);
           launch_ade(h, 0, nz, st);
+          modulation_apply(h, n, st);
         }
       }
       if (!per_z && !nb_hi) for (FdtdSolver* h : both) fill_ghost_e(h, st);

@@ -123,6 +123,7 @@ struct Run {
     nb_lo = h->cfg.bc[4] == FDTD_BC_NEIGHBOR, nb_hi = h->cfg.bc[5] == FDTD_BC_NEIGHBOR;
     if ((nb_lo || nb_hi) && !multi) return fail(h, "fdtd_run: neighbour faces need fdtd_comm_init");
     if (multi && !h->aniso.empty()) return fail(h, "fdtd_run: fully anisotropic media are not available on z-slabs");
+    if (multi && !h->modulation.empty()) return fail(h, "fdtd_run: time-modulated media are not available on z-slabs");
     // (PMC on a plus face of a z-slab rank: x / y walls are local to every plane; a z wall belongs to the rank without an upper
     //  neighbour, whose interior launch must hold the wall's two image planes and the two they mirror)
     // (six planes: the boundary chunk next to the lower neighbour is one plane thick below eight planes, two from there on)
@@ -265,7 +266,7 @@ struct Run {
     tb_two_streams = h->tblock > 4096 && h->stream_overlap == 1;
     tb_ok = fused && tb_req > 0 && !any_pml(h) && h->tfsf.empty() && h->cfg.bc[4] != FDTD_BC_PERIODIC &&
                        h->mirror_wall[0] < 0 && h->mirror_wall[1] < 0 && h->mirror_wall[2] < 0 && h->aniso.empty() &&
-                       nz >= 2 * tb_req;
+                       h->modulation.empty() && nz >= 2 * tb_req;
     h->two_step_pairs = 0;
     h->tblock_used = tb_ok ? tb_req : 0;
     // ---- captured step pairs (hipGraph) ------------------------------------------------------------------------------
@@ -278,6 +279,7 @@ struct Run {
     split_now = (h->pml_split < 0 ? n_cells(h) >= (1LL << 24) : h->pml_split != 0) && any_pml(h) &&
                            (((h->pml_fused < 0 ? 7 : h->pml_fused) & pml_in_sweep_mask(h)) & 6) != 0;
     graph_ok = fused && !tb_ok && !split_now && !(h->cfg.flags & FDTD_FLAG_TIME_KERNELS) && h->aniso.empty() &&
+                    h->modulation.empty() &&      // (a graph bakes its kernel arguments: the modulation's phases change every step)
                     h->use_graph > 0;      // on request only: measured on ROCm 7.2 (profiles/r3i) a replayed pair is ~3 us per step
                                            // SLOWER than launching its kernels (64^3 17.6 -> 20.8, 128^3 28.8 -> 31.4, 200^3 81.5 -> 84.0)
     h->graph_pairs = 0;
@@ -347,6 +349,7 @@ struct Run {
     //  refreshed by their owner)
     fill_mirror(h, st, h->cfg.bc[4] == FDTD_BC_PERIODIC ? -1 : 0, h->cfg.bc[4] == FDTD_BC_PERIODIC ? nz + 1 : nz);
     aniso_save(h, st);                     // (E^n of the nodes around fully anisotropic cells: the sweep's read set is this set)
+    modulation_save(h, st);                // (E^n of the nodes inside time-modulated media)
     launch_damp(h, false, 0, nz, st);
     launch_sources(h, false, n, 0, nz, st);
     launch_pml(h, false, 0, nz, st, 7 & ~pml_in);
@@ -380,6 +383,7 @@ struct Run {
     aniso_apply(h, st);
     launch_damp(h, true, 0, nz, st);
     launch_ade(h, 0, nz, st);
+    modulation_apply(h, n, st);            // (the end of the E phase: E_lin of the listed nodes is complete)
     advance_tfsf_aux(h, true, n, st);
     fill_ghost_fused(h, st);
     return 0;
@@ -1009,12 +1013,14 @@ struct Run {
     }
     if (multi && nb_hi) HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));
     aniso_save(h, st);                     // (these kernels update E in place: E^n of the nodes around fully anisotropic cells first)
+    modulation_save(h, st);
     launch_e_main(h, e_bot, nz, st);
     launch_pml(h, true, e_bot, nz, st);
     launch_sources(h, true, n, e_bot, nz, st);
     aniso_apply(h, st);
     launch_damp(h, true, e_bot, nz, st);
     launch_ade(h, e_bot, nz, st);
+    modulation_apply(h, n, st);
     advance_tfsf_aux(h, true, n, st);
     if (multi) {
       HIPCHK(h, hipEventRecord(h->ev_e_int, st));

@@ -340,8 +340,8 @@ class HipEngine:
         # narrow grids: cyclic renaming of the axes so that the best-filled one runs along x (single GPU)
         self.axis_shift = 0
         self.user_zrange = {m.name: (int(m.lo[2]), int(m.hi[2])) for m in spec.monitors}
-        if getattr(spec, "aniso", None):
-            axis_shift = 0                  # (the coupling lists are laid out for the user's axes)
+        if getattr(spec, "aniso", None) or getattr(spec, "modulation", None):
+            axis_shift = 0                  # (the coupling / modulation lists are laid out for the user's axes)
         if _bloch_twin is None and n_ranks == 1 and slab is None and not force_comm and axis_shift != 0:
             layers = tuple((int(f0.num_layers), int(f1.num_layers)) for f0, f1 in spec.pml)
             # (round 6: lists the node table cannot hold go out as paged source terms inside the pairs — FDTD_OPT_SRC_PAGED — whatever the
@@ -607,6 +607,35 @@ class HipEngine:
                               "fdtd_add_aniso_bloch")
                 else:
                     self._chk(d.fdtd_add_aniso(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32)), "fdtd_add_aniso")
+        # time-modulated media (spec.ModulationSet): per node the table coefficient the sweep applies there and the static medium
+        # recovered from it — eps_bar = dt / (eps0 Cb) * 2 / (1 + Ca), s_bar = sigma_bar dt / (2 eps0) = eps_bar (1 - Ca) / (1 + Ca)
+        modulation = getattr(spec, "modulation", None) or []
+        if modulation:
+            from .exceptions import Tidy3dNotImplementedError
+            if self.n_ranks > 1 or self.force_comm or (z0, z1) != (0, nz):
+                raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media are not available in z-slab (multi-GPU) runs")
+            if aniso:
+                raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media together with FullyAnisotropicMedium are not supported")
+            from .constants import EPSILON_0
+            off = np.asarray(self.ghost, np.int64)          # (Bloch device layout: every node moves by the ghost offset)
+            ca32, cb32 = np.asarray(ca, np.float64), np.asarray(cb, np.float64)     # the float32 table, as the sweep reads it
+            for ms in modulation:
+                n = len(ms.ijk)
+                if n == 0:
+                    continue
+                ijk = np.asarray(ms.ijk, np.int64) + off[None, :]
+                cells = np.ascontiguousarray((ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32))
+                mi = spec.mat_idx[int(ms.comp)][ijk[:, 2], ijk[:, 1], ijk[:, 0]] if spec.mat_idx is not None else np.ones(n, np.int64)
+                ca_n, cb_n = ca32[mi], cb32[mi]
+                if not (cb_n > 0).all():
+                    raise SolverLibraryError("a time-modulated node on a PEC cell")
+                eps_bar = spec.dt / (EPSILON_0 * cb_n) * 2.0 / (1.0 + ca_n)
+                s_bar = eps_bar * (1.0 - ca_n) / (1.0 + ca_n)
+                d_s = np.asarray(ms.d_sigma, np.complex128) * (spec.dt / (2.0 * EPSILON_0))
+                arrs = [_f32(ca_n), _f32(eps_bar), _f32(s_bar), _cplx_f32(np.asarray(ms.d_eps, np.complex128)), _cplx_f32(d_s)]
+                self._chk(d.fdtd_add_modulation(h, int(ms.comp), n, _ptr(cells), *[_ptr(a) for a in arrs],
+                                                2.0 * np.pi * float(ms.freq_eps) * spec.dt, 2.0 * np.pi * float(ms.freq_sigma) * spec.dt),
+                          "fdtd_add_modulation")
         # sources
         from .spec import BC_PEC
         for s in spec.sources:

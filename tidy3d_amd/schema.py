@@ -88,10 +88,13 @@ def parse(obj: Any):
         return Unsupported(type=str(tname), raw=obj)
     # fields that change the physics and that this solver does not model: a medium that carries one becomes a placeholder
     # that raises when the medium is used — never silently the linear / static medium
-    for k in ("nonlinear_spec", "modulation_spec"):
+    for k in ("nonlinear_spec",):
         if obj.get(k) is not None:
             return Unsupported(type=f"{tname} with '{k}'", raw=obj)
     names = {f.name for f in dataclasses.fields(cls)}
+    # time modulation (ModulationSpec) is modelled for ``Medium`` alone: every other medium that carries one stays a placeholder
+    if obj.get("modulation_spec") is not None and "modulation_spec" not in names:
+        return Unsupported(type=f"{tname} with 'modulation_spec'", raw=obj)
     kwargs = {}
     for k, v in obj.items():
         if k in ("type", "attrs") or k not in names:
@@ -753,19 +756,155 @@ class _AbstractMedium(_Model):
         return float(np.real(np.sqrt(complex(eps_inf))))
 
 
+# time modulation (ref components/time_modulation.py).  Convention — PARITY-UNPINNED, the reference package is not at hand: that of
+# this mirror's source-time classes (``ContinuousWave`` below): a(t) = amplitude exp(i phase) exp(-i 2 pi freq0 t), and the modulated
+# quantity is  q(r, t) = q_bar(r) + Re[ amplitude(r) exp(i phase(r)) a(t) ].
+
+@_register
+@dataclass
+class ContinuousWaveTimeModulation(_Model):
+    """ref time_modulation.py ContinuousWaveTimeModulation: a(t) = amplitude exp(i phase) exp(-i 2 pi freq0 t)."""
+
+    freq0: float = 0.0
+    amplitude: float = 1.0
+    phase: float = 0.0
+
+    def __post_init__(self):
+        if not self.freq0 > 0:
+            raise ValidationError("ContinuousWaveTimeModulation.freq0 must be positive.")
+        if self.amplitude < 0:
+            raise ValidationError("ContinuousWaveTimeModulation.amplitude must not be negative.")
+
+    @property
+    def amp_complex(self) -> complex:
+        return complex(self.amplitude * np.exp(1j * self.phase))
+
+    def amp_time(self, time):
+        return self.amp_complex * np.exp(-2j * np.pi * self.freq0 * np.asarray(time, float))
+
+    @property
+    def max_modulation(self) -> float:
+        return float(abs(self.amplitude))
+
+
+@_register
+@dataclass(eq=False)
+class SpaceModulation(_Model):
+    """ref time_modulation.py SpaceModulation: d(r) = amplitude(r) exp(i phase(r)); floats or SpatialDataArrays, evaluated at the
+    Yee nodes with ``interp_method`` (edge values outside the data)."""
+
+    amplitude: Any = 1.0
+    phase: Any = 0.0
+    interp_method: str = "nearest"
+
+    def _check(self):
+        for what in (self.amplitude, self.phase):
+            if isinstance(what, Unsupported):
+                raise Tidy3dNotImplementedError("SpaceModulation on unstructured grids is not supported")
+            if isinstance(what, str):
+                raise SetupError(f"SpaceModulation: the JSON form carries no data (only the placeholder '{what}'); load the "
+                                 "simulation from its .hdf5 file (Simulation.from_file) or pass DataArrays.")
+
+    @staticmethod
+    def _at(v, x, y, z, method):
+        if isinstance(v, (int, float, np.integer, np.floating)):
+            return np.full(np.broadcast(x, y, z).shape, float(v))
+        return np.real(interp_dataset(v, {"x": x, "y": y, "z": z}, method))
+
+    def sel_inside(self, x, y, z) -> np.ndarray:
+        """complex d at the points (equal-shaped coordinate arrays)"""
+        self._check()
+        return self._at(self.amplitude, x, y, z, self.interp_method) * np.exp(1j * self._at(self.phase, x, y, z, self.interp_method))
+
+    @property
+    def max_modulation(self) -> float:
+        self._check()
+        a = self.amplitude
+        return float(abs(a)) if isinstance(a, (int, float, np.integer, np.floating)) else float(np.max(np.abs(np.asarray(a.values))))
+
+
+@_register
+@dataclass(eq=False)
+class SpaceTimeModulation(_Model):
+    """ref time_modulation.py SpaceTimeModulation: Re[ space_modulation(r) time_modulation(t) ]."""
+
+    time_modulation: Any = None
+    space_modulation: Any = field(default_factory=SpaceModulation)
+
+    def __post_init__(self):
+        if not isinstance(self.time_modulation, ContinuousWaveTimeModulation):
+            raise ValidationError("SpaceTimeModulation.time_modulation must be a ContinuousWaveTimeModulation.")
+        if not isinstance(self.space_modulation, SpaceModulation):
+            raise ValidationError("SpaceTimeModulation.space_modulation must be a SpaceModulation.")
+
+    @property
+    def max_modulation(self) -> float:
+        return self.time_modulation.max_modulation * self.space_modulation.max_modulation
+
+
+@_register
+@dataclass(eq=False)
+class ModulationSpec(_Model):
+    """ref time_modulation.py ModulationSpec: the modulation of a medium's relative permittivity and / or conductivity (S/um)."""
+
+    permittivity: Any = None
+    conductivity: Any = None
+
+    def __post_init__(self):
+        for k in ("permittivity", "conductivity"):
+            v = getattr(self, k)
+            if v is not None and not isinstance(v, SpaceTimeModulation):
+                raise ValidationError(f"ModulationSpec.{k} must be a SpaceTimeModulation or None.")
+
+    @property
+    def applied(self) -> bool:
+        """False when every amplitude is zero: the medium is then the static one, bit for bit."""
+        return any(v is not None and v.max_modulation > 0 for v in (self.permittivity, self.conductivity))
+
+
 @_register
 @dataclass
 class Medium(_AbstractMedium):
-    """Dispersionless medium (ref medium.py:1499)."""
+    """Dispersionless medium (ref medium.py:1499), optionally time-modulated (``modulation_spec``)."""
 
     permittivity: float = 1.0
     conductivity: float = 0.0
     name: Optional[str] = None
     frequency_range: Optional[Tuple[float, float]] = None
+    allow_gain: bool = False
+    modulation_spec: Any = None
 
     def __post_init__(self):
         if self.permittivity < 1.0:
             raise ValidationError("Medium.permittivity must be >= 1.")
+        ms = self.modulation_spec
+        if ms is None or isinstance(ms, Unsupported):
+            return
+        if not isinstance(ms, ModulationSpec):
+            raise ValidationError("Medium.modulation_spec must be a ModulationSpec.")
+        # ref medium.py _validate_modulation_spec / _passivity_modulation_validation: the modulated values stay physical
+        if ms.permittivity is not None and self.permittivity - ms.permittivity.max_modulation < 1.0:
+            raise SetupError("The minimum permittivity value with modulation applied was found to be less than 1 "
+                             f"({self.permittivity} - {ms.permittivity.max_modulation}).")
+        if ms.conductivity is not None and not self.allow_gain and self.conductivity - ms.conductivity.max_modulation < 0.0:
+            raise SetupError("For passive medium, the minimum conductivity value with modulation applied must not be negative "
+                             f"({self.conductivity} - {ms.conductivity.max_modulation}); set allow_gain=True for a gain medium.")
+
+    @property
+    def is_time_modulated(self) -> bool:
+        ms = self.modulation_spec
+        if isinstance(ms, Unsupported):
+            ms.fail()
+        return ms is not None and ms.applied
+
+    @property
+    def n_cfl(self) -> float:
+        """ref medium.py:1591: sqrt of the permittivity — of its LOWER bound when it is modulated in time."""
+        eps = float(self.permittivity)
+        ms = self.modulation_spec
+        if isinstance(ms, ModulationSpec) and ms.permittivity is not None:
+            eps -= ms.permittivity.max_modulation
+        return float(np.sqrt(eps))
 
     def pole_residue(self):
         return float(self.permittivity), float(self.conductivity), ()

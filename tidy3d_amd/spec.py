@@ -61,6 +61,25 @@ class AnisoSet:
 
 
 @dataclass
+class ModulationSet:
+    """The nodes of one E component inside one time-modulated medium (ref time_modulation.py ModulationSpec):
+
+        eps(t) = eps_bar + Re[d_eps exp(-2 pi i freq_eps t)],    sigma(t) = sigma_bar + Re[d_sigma exp(-2 pi i freq_sigma t)]
+
+    eps_bar, sigma_bar are the node's own static table medium (``mat_idx``, sub-pixel value included); d_eps, d_sigma carry the
+    space modulation at the node's Yee location times the time modulation's amplitude exp(i phase).  The sweep advances the node
+    with the static medium, E_lin = Ca E^n + Cb K; the solver replaces that by the update of
+    (D^{n+1} - D^n) / dt + sigma^{n+1/2} (E^{n+1} + E^n) / 2 = K, D = eps0 eps(t) E (csrc/fdtd_modulation.hpp)."""
+
+    comp: int                         # E component
+    ijk: np.ndarray                   # [n, 3] nodes (i, j, k), each at most once per component
+    d_eps: np.ndarray                 # complex128 [n]
+    d_sigma: np.ndarray               # complex128 [n], S/um
+    freq_eps: float                   # Hz (0 with d_eps = 0: no permittivity modulation)
+    freq_sigma: float
+
+
+@dataclass
 class PmlFace:
     """CPML profile of one face (ref boundary.py:195-254; units of sigma/alpha: 2 eps0/dt)."""
 
@@ -223,6 +242,7 @@ class SolverSpec:
     # E_norm, H_tan odd — refreshed at the start of every step (discretize._discretize_pmc_plus, kernel mirror_fill_kernel)
     mirror_plus: Optional[Tuple[int, int, int]] = None
     aniso: List[AnisoSet] = field(default_factory=list)   # fully anisotropic bodies: off-diagonal coupling per E component
+    modulation: List[ModulationSet] = field(default_factory=list)   # time-modulated media: their nodes per E component and medium
     shutoff: float = 0.0                                # 0 disables the early stop
     decay_every: int = 0                                # 0 = never evaluate field decay
     decay_ref_step: int = 0                             # steps before this never shut off

@@ -23,7 +23,7 @@ import numpy as np
 from . import schema as td
 from .data import SimulationData, assemble
 from .discretize import DevicePaths, _device_refusals, discretize
-from .exceptions import SetupError, SolverLibraryError
+from .exceptions import SetupError, SolverLibraryError, Tidy3dNotImplementedError
 
 log = logging.getLogger("tidy3d_amd")
 
@@ -127,6 +127,9 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     paths = DevicePaths(flux_time_device, field_time_device, field_dft_device, projection_device)
     if devices is not None and len(devices) > 1:
         _device_refusals(sim, paths, "devices= with more than one GPU")
+        if any(isinstance(m, td.Medium) and m.is_time_modulated for m in sim.mediums):
+            raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media together with devices= with more than one GPU are "
+                                            "not supported")
         sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose, _dist_options or {})
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
         if want_td:
