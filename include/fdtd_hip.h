@@ -157,6 +157,23 @@ int  fdtd_far_field(int device, int n_u, int n_v, const double* u, const double*
                     const double* currents, double w0, double k_re, double k_im, int n_dir, const double* r_u,
                     const double* r_v, const double* r_w, double* out);
 
+/* Exact projection (far_field_approx=False; ref components/field_projection.py:831-1010), the integration step on the
+ * device: the sibling of fdtd_far_field for observation POINTS at a finite distance.  Same surface description (one
+ * surface, one frequency: u, v, wu, wv, currents [4][n_u][n_v], w0, k); n_pts points by their coordinates (p_u, p_v, p_w)
+ * in the same local frame (along u, v and the normal, relative to the monitor's local origin).  With Rv = p - r',
+ * R = |Rv|, Rh = Rv / R, G = exp(i k R) / (4 pi R), G1 = G (i k - 1/R), G2 = G1 (i k - 1/R) + G / R^2 and, per current
+ * type F in {J, M} (F_w = 0), rd = Rh_u F_u + Rh_v F_v:
+ *   I_F[a] = sum wu wv [G F_a + (Rh_a rd G2 + (F_a - Rh_a rd) G1 / R) / k^2],  C_F[a] = sum wu wv G1 (Rh x F)_a,  a in (u, v, w)
+ * (the cross product of a right-handed (u, v, w)).  out[n_pts][12][2] = I_J, I_M, C_J, C_M (re, im), all in fp64; the
+ * caller forms E = i w mu0 I_J - C_M, H = i w eps0 eps I_M + C_J.  A point on a lattice node gives non-finite values.
+ * n_pts == 0 returns 0 without touching out.  Returns 0, or -1 with fdtd_last_error(NULL). */
+int  fdtd_near_field(int device, int n_u, int n_v, const double* u, const double* v, const double* wu, const double* wv,
+                     const double* currents, double w0, double k_re, double k_im, int n_pts, const double* p_u,
+                     const double* p_v, const double* p_w, double* out);
+/* The number of lattice chunks fdtd_near_field cuts an n_u x n_v lattice into for n_pts points (a function of n_pts and
+ * n_u * n_v alone: csrc/fdtd_near_field.hpp); -1 on a bad argument.  Needs no device. */
+int  fdtd_near_field_chunks(int n_pts, int n_u, int n_v);
+
 /* One solve = one handle.  Stands in for SimulationTask.create + upload_simulation of the cloud
  * path (ref web/api/webapi.py:219,237; web/core/task_core.py:121); the grid size is
  * Simulation.grid.num_cells incl. the PML cells (ref simulation.py:4296, grid_spec.py:114-137),

@@ -23,6 +23,7 @@
 #include "fdtd_shell2_host.hpp"
 #include "fdtd_aniso.hpp"
 #include "fdtd_modulation.hpp"
+#include "fdtd_near_field.hpp"
 #include "fdtd_flux_time.hpp"
 #include "fdtd_field_time.hpp"
 #include "fdtd_field_dft.hpp"
@@ -3054,6 +3055,55 @@ int fdtd_far_field(int device, int n_u, int n_v, const double* u, const double* 
     hipLaunchKernelGGL(far_field_kernel, dim3((unsigned)n_dir), dim3(256), 0, 0, p);
     if (hipMemcpy(out, dev[8], sizes[8] * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       rc = fail(nullptr, "fdtd_far_field: %s", hipGetErrorString(hipGetLastError()));
+  }
+  for (double* q : dev) if (q) hipFree(q);
+  return rc;
+}
+
+int fdtd_near_field_chunks(int n_pts, int n_u, int n_v) {
+  if (n_pts < 0 || n_u < 1 || n_v < 1 || (long long)n_u * n_v > 0x7fffffffLL) return fail(nullptr, "fdtd_near_field_chunks: bad argument");
+  return near_field_chunks(n_pts, (long long)n_u * n_v).chunks;
+}
+
+int fdtd_near_field(int device, int n_u, int n_v, const double* u, const double* v, const double* wu, const double* wv,
+                    const double* currents, double w0, double k_re, double k_im, int n_pts, const double* p_u,
+                    const double* p_v, const double* p_w, double* out) {
+  if (n_u < 1 || n_v < 1 || n_pts < 0 || !u || !v || !wu || !wv || !currents || (n_pts && (!p_u || !p_v || !p_w || !out)))
+    return fail(nullptr, "fdtd_near_field: bad argument");
+  if ((long long)n_u * n_v > 0x7fffffffLL) return fail(nullptr, "fdtd_near_field: lattice of %d x %d nodes exceeds the 2^31 node index range", n_u, n_v);
+  if (n_pts == 0) return 0;
+  const size_t n = (size_t)n_u * n_v;
+  const NearChunks ch = near_field_chunks(n_pts, (long long)n);
+  if ((long long)n_pts * ch.chunks > 0x7fffffffLL) return fail(nullptr, "fdtd_near_field: too many points (%d)", n_pts);
+  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, "fdtd_near_field: hipSetDevice(%d) failed", device);
+  // the partial records exist only where the lattice is cut (fdtd_near_field.hpp: at most 8184 of them)
+  const size_t sizes[10] = {(size_t)n_u, (size_t)n_v, (size_t)n_u, (size_t)n_v, 8 * n, (size_t)n_pts, (size_t)n_pts,
+                            (size_t)n_pts, 24 * (size_t)n_pts, ch.chunks > 1 ? 24 * (size_t)n_pts * ch.chunks : 0};
+  const double* host[8] = {u, v, wu, wv, currents, p_u, p_v, p_w};
+  double* dev[10] = {};
+  int rc = 0;
+  for (int i = 0; i < 10 && !rc; ++i) {
+    if (!sizes[i]) continue;
+    if (hipMalloc((void**)&dev[i], sizes[i] * sizeof(double)) != hipSuccess) rc = fail(nullptr, "fdtd_near_field: out of device memory");
+    else if (i < 8 && hipMemcpy(dev[i], host[i], sizes[i] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(nullptr, "fdtd_near_field: upload failed");
+  }
+  if (!rc) {
+    NearP p;
+    p.u = dev[0]; p.v = dev[1]; p.wu = dev[2]; p.wv = dev[3];
+    p.cur = reinterpret_cast<const double2*>(dev[4]);
+    p.n_u = n_u; p.n_v = n_v; p.w0 = w0; p.k_re = k_re; p.k_im = k_im;
+    p.p_u = dev[5]; p.p_v = dev[6]; p.p_w = dev[7];
+    p.chunks = ch.chunks; p.chunk_len = ch.chunk_len;
+    p.dst = ch.chunks > 1 ? dev[9] : dev[8];
+    hipLaunchKernelGGL(near_field_kernel, dim3((unsigned)((long long)n_pts * ch.chunks)), dim3(256), 0, 0, p);
+    if (ch.chunks > 1) {
+      const long long n_vals = 24LL * n_pts;
+      hipLaunchKernelGGL(near_field_sum_kernel, dim3((unsigned)((n_vals + 255) / 256)), dim3(256), 0, 0, (const double*)dev[9], dev[8],
+                         ch.chunks, n_vals);
+    }
+    if (hipMemcpy(out, dev[8], sizes[8] * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(nullptr, "fdtd_near_field: %s", hipGetErrorString(hipGetLastError()));
   }
   for (double* q : dev) if (q) hipFree(q);
   return rc;

@@ -595,14 +595,19 @@ def source_spectrum_fn(disc: Discretization, index: Optional[int]) -> Callable:
 
 
 def assemble(disc: Discretization, raw: Dict[str, np.ndarray], log: str = "", diverged: bool = False,
-             n_steps_run: Optional[int] = None, device_lib=None, device: int = 0) -> SimulationData:
+             n_steps_run: Optional[int] = None, device_lib=None, device: int = 0,
+             exact_projection_device: Optional[bool] = None, exact_lib=None) -> SimulationData:
     """Raw monitor buffers (name -> array as returned by the engine / oracle) -> SimulationData.
     ``n_steps_run``: time steps actually taken (a run that stopped on the shutoff criterion or diverged took
     fewer than ``spec.n_steps``): time-domain monitors then keep only the samples that were recorded — steps
     after the stop never happened and must not come back as zeros on the full ``tmesh`` axis.
     ``device_lib``: the loaded HIP library — projection and diffraction monitors then integrate on the device
-    (``device``: the GPU that ran the solve)."""
+    (``device``: the GPU that ran the solve).  ``exact_projection_device``: where projection monitors with
+    ``far_field_approx=False`` take their surface integrals — on the device (True; an error without a library), on the host
+    (False), or per monitor by its work (None: ``projection.EXACT_HOST_PAIRS``); one line per such monitor in the log says which.
+    ``exact_lib``: a library for these integrals alone (a z-slab run, whose other projections stay on the host)."""
     sim, spec = disc.sim, disc.spec
+    notes = []
 
     def recorded(steps):
         """number of leading entries of ``steps`` that were reached"""
@@ -669,7 +674,11 @@ def assemble(disc: Discretization, raw: Dict[str, np.ndarray], log: str = "", di
             from . import projection
             fn = {"projection_angle": projection.project_angle, "projection_cartesian": projection.project_cartesian,
                   "projection_kspace": projection.project_kspace}[plan.kind]
-            out.append(fn(disc, plan, raw, norm, lib=device_lib, device=device))
+            if plan.kind == "projection_kspace" or mon.far_field_approx:
+                out.append(fn(disc, plan, raw, norm, lib=device_lib, device=device))
+            else:
+                out.append(fn(disc, plan, raw, norm, lib=exact_lib or device_lib, device=device,
+                              exact_device=exact_projection_device, notes=notes))
         elif plan.kind == "mode_solver":
             from .plugins.mode import ModeSolver
             ms = ModeSolver(simulation=sim, plane=mon.geometry, mode_spec=mon.mode_spec, freqs=mon.freqs,
@@ -686,4 +695,6 @@ def assemble(disc: Discretization, raw: Dict[str, np.ndarray], log: str = "", di
                                          plan if pfull is None else pfull))
         else:
             raise DataError(f"unknown monitor plan kind '{plan.kind}'")
+    if notes:
+        log = "\n".join(([log] if log else []) + notes)
     return SimulationData(simulation=sim, data=tuple(out), log=log, diverged=diverged)

@@ -141,9 +141,11 @@ def slab_discretization(sim, n_steps: Optional[int] = None):
     return discretize(sim, n_steps=n_steps, device_paths=DevicePaths.all_host())
 
 
-def run(simulation, verbose: bool = True, n_steps: Optional[int] = None, lib=None, **kw):
+def run(simulation, verbose: bool = True, n_steps: Optional[int] = None, lib=None, exact_projection_device: Optional[bool] = None,
+        **kw):
     """Distributed counterpart of ``tidy3d_amd.web.run``: every rank calls it with the same
-    Simulation; rank 0 returns the SimulationData, the others None."""
+    Simulation; rank 0 returns the SimulationData, the others None.  ``exact_projection_device``: as in ``web.run``; rank 0's
+    GPU takes the integrals of the exact projections."""
     import torch.distributed as dist
     from .data import assemble
     from .web import _as_mirror
@@ -160,4 +162,5 @@ def run(simulation, verbose: bool = True, n_steps: Optional[int] = None, lib=Non
     if rank != 0:
         return None
     return assemble(disc, raw, log=f"distributed run over {eng.n_ranks} z-slabs", diverged=bool(stats.diverged),
-                    n_steps_run=int(stats.steps_done))
+                    n_steps_run=int(stats.steps_done), device=int(kw.get("device") or 0),
+                    exact_projection_device=exact_projection_device, exact_lib=eng.lib)

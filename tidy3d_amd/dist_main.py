@@ -23,6 +23,8 @@ def main(argv=None) -> int:
     ap.add_argument("--n-steps", type=int, default=-1)
     ap.add_argument("--lib", default=None, help="explicit path of the solver library (tests)")
     ap.add_argument("--hook", default=None, help="module:function called with the loaded library before the run (tests)")
+    ap.add_argument("--exact-projection-device", default="auto", choices=["auto", "on", "off"],
+                    help="web.run's exact_projection_device: None / True / False")
     args = ap.parse_args(argv)
     import torch
     import torch.distributed as dist
@@ -47,7 +49,8 @@ def main(argv=None) -> int:
         with open(args.sim, "rb") as f:
             sim = pickle.load(f)
         sd = tdist.run(sim, verbose=False, n_steps=None if args.n_steps < 0 else args.n_steps, lib=lib,
-                       device=local if args.backend == "nccl" else 0)
+                       device=local if args.backend == "nccl" else 0,
+                       exact_projection_device={"auto": None, "on": True, "off": False}[args.exact_projection_device])
         if rank == 0:
             with open(args.out, "wb") as f:
                 pickle.dump(sd, f, protocol=pickle.HIGHEST_PROTOCOL)

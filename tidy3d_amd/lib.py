@@ -41,6 +41,7 @@ SYMBOLS = (
     "fdtd_far_field", "fdtd_set_mirror_plus", "fdtd_add_aniso", "fdtd_add_aniso_bloch", "fdtd_get_seam_stats",
     "fdtd_get_sweep_words", "fdtd_sweep_table", "fdtd_add_flux_time_monitor", "fdtd_get_monitor_bytes",
     "fdtd_add_field_time_monitor", "fdtd_add_field_dft_monitor", "fdtd_add_lattice_dft_monitor", "fdtd_add_modulation",
+    "fdtd_near_field", "fdtd_near_field_chunks",
 )
 
 BC_PEC, BC_PMC, BC_PERIODIC, BC_NEIGHBOR = 0, 1, 2, 3
@@ -151,6 +152,8 @@ class FdtdLib:
         d.fdtd_set_option.argtypes = [vp, C.c_int, C.c_int]
         f64 = C.c_double
         d.fdtd_far_field.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, f64, f64, f64, C.c_int, vp, vp, vp, vp]
+        d.fdtd_near_field.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, f64, f64, f64, C.c_int, vp, vp, vp, vp]
+        d.fdtd_near_field_chunks.argtypes = [C.c_int, C.c_int, C.c_int]
 
     def far_field(self, u, v, wu, wv, currents, w0: float, k: complex, r_u, r_v, r_w, device: int = 0):
         """Surface integrals of the near -> far projection on the device (``fdtd_far_field``): ``currents`` [4, n_u, n_v]
@@ -166,6 +169,27 @@ class FdtdLib:
                                            float(np.real(k)), float(np.imag(k)), int(r_u.size), p(r_u), p(r_v), p(r_w), p(out)),
                    None, "fdtd_far_field")
         return out
+
+    def near_field(self, u, v, wu, wv, currents, w0: float, k: complex, p_u, p_v, p_w, device: int = 0):
+        """Surface integrals of the exact (far_field_approx=False) projection on the device (``fdtd_near_field``): ``currents``
+        [4, n_u, n_v] complex (J_u, J_v, M_u, M_v), observation points by their coordinates along u, v and the surface normal
+        -> complex [n_pts, 12]: I_J, I_M, C_J, C_M with three components (u, v, normal) each."""
+        import numpy as np
+        u, v, wu, wv = (np.ascontiguousarray(a, dtype=np.float64) for a in (u, v, wu, wv))
+        cur = np.ascontiguousarray(currents, dtype=np.complex128)
+        assert cur.shape == (4, u.size, v.size), cur.shape
+        p_u, p_v, p_w = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (p_u, p_v, p_w))
+        assert p_u.size == p_v.size == p_w.size
+        out = np.empty((p_u.size, 12), dtype=np.complex128)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)           # noqa: E731
+        self.check(self.dll.fdtd_near_field(int(device), int(u.size), int(v.size), p(u), p(v), p(wu), p(wv), p(cur), float(w0),
+                                            float(np.real(k)), float(np.imag(k)), int(p_u.size), p(p_u), p(p_v), p(p_w), p(out)),
+                   None, "fdtd_near_field")
+        return out
+
+    def near_field_chunks(self, n_pts: int, n_u: int, n_v: int) -> int:
+        """Lattice chunks ``fdtd_near_field`` works in for ``n_pts`` points over an ``n_u`` x ``n_v`` lattice."""
+        return self.check(self.dll.fdtd_near_field_chunks(int(n_pts), int(n_u), int(n_v)), None, "fdtd_near_field_chunks")
 
     def sweep_table(self):
         """Every instantiation (LB, OPT) of the two-step sweep this library holds (``fdtd_sweep_table``), in list order."""

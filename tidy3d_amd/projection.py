@@ -10,7 +10,8 @@ currents J = n x H, M = -n x E (ref field_projection.py:231-278), resampled to a
     E_theta = -(L_phi + eta N_theta),  E_phi = L_theta - eta N_phi,  H = r_hat x E / eta
 
 (Balanis 8.33-8.34, ref :370-521), times the propagation factor -i k exp(i k r) / (4 pi r)
-(ref monitor_data.py:2170-2178).  Far-field approximation only.
+(ref monitor_data.py:2170-2178).  ``far_field_approx=False``: the exact Green's function at finite distance
+(``_exact_fields``; its surface integrals on the device by ``fdtd_near_field``, docs/history/EXACT_PROJECTION.md).
 """
 from __future__ import annotations
 
@@ -230,14 +231,19 @@ def _far_fields(disc, plan, raw, norm, theta: np.ndarray, phi: np.ndarray, mediu
     return e_t, e_p, k_f, eta_f
 
 
-def _exact_fields(disc, plan, raw, norm, points: np.ndarray, medium=None):
+def _exact_fields(disc, plan, raw, norm, points: np.ndarray, medium=None, lib=None, device=0):
     """E and H (Cartesian, [3, n_points, n_freq]) at the observation ``points`` [n, 3] (relative to the
     monitor's local origin) from the homogeneous-medium Green's function without the far-field
     approximation (ref field_projection.py:831-1010), e^{-i w t} convention:
 
         E = i w mu int [G J + (1/k^2) grad grad G . J] dS - int grad G x M dS
         H = i w eps int [G M + (1/k^2) grad grad G . M] dS + int grad G x J dS
-        G = exp(i k R) / (4 pi R),  grad G = R_hat G',  grad grad G = R_hat R_hat G'' + (1 - R_hat R_hat) G' / R."""
+        G = exp(i k R) / (4 pi R),  grad G = R_hat G',  grad grad G = R_hat R_hat G'' + (1 - R_hat R_hat) G' / R.
+
+    ``lib`` = the loaded HIP library: the surface integrals (points x lattice nodes x frequencies — all of the cost) run on
+    the device, one ``fdtd_near_field`` call (kernel K9b) per surface and frequency, in fp64; E and H are put together from
+    its twelve sums here, in complex128.  Without it the sums are taken in NumPy point by point — the reference the device
+    path is tested against (``exact_on_device`` chooses for ``web.run``)."""
     from .constants import EPSILON_0, MU_0
     mon, sim = plan.monitor, disc.sim
     freqs = np.asarray(mon.freqs, float)
@@ -255,7 +261,18 @@ def _exact_fields(disc, plan, raw, norm, points: np.ndarray, medium=None):
             Mc = [zero, zero, zero]
             for a in (u, v):
                 Jc[a], Mc[a] = J[a][:, :, i_f], M[a][:, :, i_f]
-            for n, pt in enumerate(points):
+            if lib is not None:
+                # the points in the surface's (u, v, normal) frame, like r_hat in _far_fields; (u, v, axis) is left-handed for
+                # axis 1, where the kernel's cross products (of a right-handed frame) change sign
+                cur = np.stack([Jc[u], Jc[v], Mc[u], Mc[v]])
+                got = lib.near_field(pts[u], pts[v], _trap_weights(pts[u]), _trap_weights(pts[v]), cur, float(pts[axis][0]), k,
+                                     points[:, u] + origin[u], points[:, v] + origin[v], points[:, axis] + origin[axis], device=device)
+                hand = -1.0 if axis == 1 else 1.0
+                ce, ch = 1j * w * MU_0, 1j * w * EPSILON_0 * eps_f[i_f]
+                for j, a in enumerate((u, v, axis)):
+                    E[a, :, i_f] += ce * got[:, j] - hand * got[:, 9 + j]
+                    H[a, :, i_f] += ch * got[:, 3 + j] + hand * got[:, 6 + j]
+            for n, pt in (enumerate(points) if lib is None else ()):
                 Rv = (pt + origin)[None, None, :] - src
                 R = np.sqrt(np.sum(Rv ** 2, axis=-1))
                 Rh = [Rv[..., a] / R for a in range(3)]
@@ -273,6 +290,35 @@ def _exact_fields(disc, plan, raw, norm, points: np.ndarray, medium=None):
                     for a in range(3):
                         out[a, n, i_f] += sgn * _trapz2(G1 * cx[a], pts[u], pts[v])
     return E, H
+
+
+EXACT_HOST_PAIRS = 1 << 22          # point-node pairs (x frequencies, summed over surfaces) below which exact projections stay on the host
+
+
+def exact_pairs(disc, plan, n_points: int, medium=None) -> int:
+    """The work of one exact projection: sum over the monitor's surfaces of n_points x n_u x n_v x n_freq."""
+    mon = plan.monitor
+    total = 0
+    for _, box, axis, _ in flux_surfaces(mon):
+        pts = surface_lattice(disc.sim, mon, box, axis, medium)
+        total += int(n_points) * int(np.prod([len(p) for p in pts])) * len(mon.freqs)
+    return total
+
+
+def exact_on_device(disc, plan, n_points: int, lib, exact_device: Optional[bool], notes: Optional[list] = None) -> bool:
+    """Where the exact projection (far_field_approx=False) of one monitor takes its surface integrals.  ``exact_device`` False:
+    on the host; True: on the device (an error without a library); None: on the device where the work is at least
+    ``EXACT_HOST_PAIRS`` pairs and a library is at hand — a design choice, not a measurement: below it the host finishes in
+    seconds and every small projection stays on the host path bit for bit.  ``notes`` receives the line for SimulationData.log."""
+    from .exceptions import SolverLibraryError
+    pairs = exact_pairs(disc, plan, n_points)
+    if exact_device and lib is None:
+        raise SolverLibraryError(f"exact_projection_device=True: the exact projection of monitor '{plan.monitor.name}' on the device "
+                                 "needs the loaded HIP library (web.run, or assemble(..., device_lib=...))")
+    on_device = bool(exact_device) if exact_device is not None else (lib is not None and pairs >= EXACT_HOST_PAIRS)
+    if notes is not None:
+        notes.append(f"Exact projection of monitor '{plan.monitor.name}': {'device' if on_device else 'host'}, {pairs} point-node pairs.")
+    return on_device
 
 
 def _package_exact(cls, mon, E, H, theta, phi, shape, coords):
@@ -300,7 +346,8 @@ def _package(cls, mon, e_t, e_p, k_f, eta_f, r, shape, coords):
     return cls(monitor=mon, **{k: DataArray(v.reshape(shape), coords) for k, v in comps.items()})
 
 
-def project_angle(disc, plan, raw, norm, lib=None, device: int = 0) -> FieldProjectionAngleData:
+def project_angle(disc, plan, raw, norm, lib=None, device: int = 0, exact_device: Optional[bool] = False,
+                  notes: Optional[list] = None) -> FieldProjectionAngleData:
     mon = plan.monitor
     freqs = np.asarray(mon.freqs, float)
     theta, phi = np.asarray(mon.theta, float), np.asarray(mon.phi, float)
@@ -309,7 +356,8 @@ def project_angle(disc, plan, raw, norm, lib=None, device: int = 0) -> FieldProj
     if not mon.far_field_approx:
         t, p_, r0 = T.ravel(), P.ravel(), float(mon.proj_distance)
         pts = r0 * np.stack([np.sin(t) * np.cos(p_), np.sin(t) * np.sin(p_), np.cos(t)], axis=1)
-        E, H = _exact_fields(disc, plan, raw, norm, pts)
+        on_device = exact_on_device(disc, plan, len(pts), lib, exact_device, notes)
+        E, H = _exact_fields(disc, plan, raw, norm, pts, lib=lib if on_device else None, device=device)
         return _package_exact(FieldProjectionAngleData, mon, E, H, t, p_, (1, len(theta), len(phi), len(freqs)), coords)
     e_t, e_p, k_f, eta_f = _far_fields(disc, plan, raw, norm, T.ravel(), P.ravel(), lib=lib, device=device)
     r = np.full(T.size, float(mon.proj_distance))
@@ -326,7 +374,8 @@ class FieldProjectionKSpaceData(FieldProjectionAngleData):
     """ref monitor_data.py FieldProjectionKSpaceData: dims (ux, uy, r, f)."""
 
 
-def project_cartesian(disc, plan, raw, norm, lib=None, device: int = 0) -> FieldProjectionCartesianData:
+def project_cartesian(disc, plan, raw, norm, lib=None, device: int = 0, exact_device: Optional[bool] = False,
+                      notes: Optional[list] = None) -> FieldProjectionCartesianData:
     """Observation points on a plane at ``proj_distance`` along ``proj_axis`` (ref field_projection.py:665-746)."""
     mon = plan.monitor
     freqs = np.asarray(mon.freqs, float)
@@ -338,7 +387,9 @@ def project_cartesian(disc, plan, raw, norm, lib=None, device: int = 0) -> Field
     phi = np.arctan2(Y.ravel(), X.ravel())
     coords = {"x": loc[0], "y": loc[1], "z": loc[2], "f": freqs}
     if not mon.far_field_approx:
-        E, H = _exact_fields(disc, plan, raw, norm, np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=1))
+        pts = np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=1)
+        on_device = exact_on_device(disc, plan, len(pts), lib, exact_device, notes)
+        E, H = _exact_fields(disc, plan, raw, norm, pts, lib=lib if on_device else None, device=device)
         return _package_exact(FieldProjectionCartesianData, mon, E, H, theta, phi, X.shape + (len(freqs),), coords)
     e_t, e_p, k_f, eta_f = _far_fields(disc, plan, raw, norm, theta, phi, lib=lib, device=device)
     return _package(FieldProjectionCartesianData, mon, e_t, e_p, k_f, eta_f, r, X.shape + (len(freqs),), coords)

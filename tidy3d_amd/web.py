@@ -96,7 +96,7 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         return_tidy3d: Optional[bool] = None, devices=None, _dist_options: Optional[dict] = None,
         mode_grid_dispersion: Optional[bool] = None, flux_time_device: Optional[bool] = None,
         field_time_device: Optional[bool] = None, field_dft_device: Optional[bool] = None,
-        projection_device: Optional[bool] = None) -> SimulationData:
+        projection_device: Optional[bool] = None, exact_projection_device: Optional[bool] = None) -> SimulationData:
     """Solve ``simulation`` on the local MI355X and return its ``SimulationData``.
 
     Cloud-only arguments (``folder_name``, ``callback_url``, ``progress_callback_*``,
@@ -119,7 +119,11 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     (angle, Cartesian, k-space) — accumulate every surface on its sampling lattice of 10 points per wavelength only, on the device
     (True), over the whole padded surface boxes with colocation and resampling on the host (False), or per monitor (None: on the
     device where the whole-box accumulators of all its surfaces would exceed the threshold and the lattice holds fewer nodes).  The
-    projected fields agree within a few fp32 roundings of the largest near field; coordinates, dtypes and files are the same."""
+    projected fields agree within a few fp32 roundings of the largest near field; coordinates, dtypes and files are the same.
+    ``exact_projection_device``: where angle and Cartesian projection monitors with ``far_field_approx=False`` take their surface
+    integrals after the run — on the device in fp64 (True: ``fdtd_near_field``), in NumPy on the host (False), or per monitor (None: on
+    the device from ``projection.EXACT_HOST_PAIRS`` point-node pairs on); ``SimulationData.log`` names the path per monitor.  With
+    more than one GPU in ``devices`` the first one integrates."""
     from .engine import HipEngine
 
     sim, was_tidy3d = _as_mirror(simulation)
@@ -130,7 +134,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         if any(isinstance(m, td.Medium) and m.is_time_modulated for m in sim.mediums):
             raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media together with devices= with more than one GPU are "
                                             "not supported")
-        sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose, _dist_options or {})
+        sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose,
+                                   dict(_dist_options or {}, exact_projection_device=exact_projection_device))
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
         if want_td:
             from .adapter import to_tidy3d
@@ -185,7 +190,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
                      + (f" Projection monitor accumulated on its lattice on the device: {', '.join(on_lattice)}." if on_lattice else ""))
     lines += ["", f"Setup time (s):  {setup_s:.4f}", f"Solver time (s): {solve_s:.4f}",
               f"Time-stepping speed (cells/s): {spec.n_cells * steps_done / max(solve_s, 1e-9):.2e}"]
-    sim_data = assemble(disc, raw, log="\n".join(lines), diverged=diverged, n_steps_run=steps_done, device_lib=used_lib, device=device)
+    sim_data = assemble(disc, raw, log="\n".join(lines), diverged=diverged, n_steps_run=steps_done, device_lib=used_lib, device=device,
+                        exact_projection_device=exact_projection_device)
 
     # post-run warnings, ref web/api/tidy3d_stub.py:219-233
     if diverged:
@@ -245,6 +251,8 @@ def _run_on_devices(sim, devices, n_steps, verbose: bool, opt: dict) -> Simulati
                     cmd += ["--lib", opt["lib"]]
                 if opt.get("hook"):
                     cmd += ["--hook", opt["hook"]]
+                if opt.get("exact_projection_device") is not None:
+                    cmd += ["--exact-projection-device", "on" if opt["exact_projection_device"] else "off"]
                 # stderr goes to a FILE per rank: a pipe nobody drains blocks its rank after ~64 KiB (HIP / RCCL warnings,
                 # AMD_LOG_LEVEL) — and with it every sibling waiting for that rank in a collective
                 lf = open(os.path.join(tmp, f"rank{rank}.attempt{attempt}.err"), "w+")
