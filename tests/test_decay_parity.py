@@ -9,6 +9,7 @@ import pytest
 import tidy3d_amd.schema as td
 from cases import CASES, DL, PULSE
 from oracle.fdtd_numpy import OracleFdtd
+from tidy3d_amd import lib as L
 from tidy3d_amd.discretize import discretize
 from tidy3d_amd.engine import HipEngine
 
@@ -68,7 +69,44 @@ def check_divergence(lib, **kw):
     return o, st
 
 
+def check_bloch_shutoff(lib, variant):
+    """The decay path of fdtd_run_bloch (complex fields as a Re / Im pair of handles): 16 x 12 x 10 cells between the CPML layers,
+    Bloch x / y, CPML z, a lossy slab through the cell (the fields are gone within a hundred steps of the short pulse), a check every
+    6 steps and a shutoff level that is reached.  The run stops at a check, both handles report the same verdict, and stopping changes
+    nothing: the six complex fields are those of a fresh engine run for exactly that many steps with the check off, bit for bit."""
+    import dataclasses
+    from cases import _sim
+    slab = td.Structure(geometry=td.Box(center=(0, 0, 0), size=(td.inf, td.inf, 0.3)), medium=td.Medium(permittivity=2.5, conductivity=0.05))
+    bspec = td.BoundarySpec(x=td.Boundary.bloch(0.2), y=td.Boundary.bloch(0.35), z=td.Boundary.pml(num_layers=4))
+    spec = discretize(_sim((16, 12, 10), bspec, [slab]), n_steps=300).spec
+    assert spec.bloch is not None
+    spec.shutoff, spec.decay_every, spec.decay_ref_step = 3e-2, 6, 60
+    with HipEngine(spec, lib=lib, variant=variant) as e:
+        st, tw = e.run(), e.twin.stats()
+        got = [e.get_field(c) for c in range(6)]
+    print("steps_done", st.steps_done, "field_decay", st.field_decay, tw.field_decay)
+    assert st.stopped_early == 1 and tw.stopped_early == 1 and st.diverged == 0 and tw.diverged == 0
+    assert spec.decay_ref_step < st.steps_done < spec.n_steps and st.steps_done % spec.decay_every == 0
+    assert tw.steps_done == st.steps_done
+    assert st.field_decay == tw.field_decay and 0 < st.field_decay < spec.shutoff
+    with HipEngine(dataclasses.replace(spec, shutoff=0.0, decay_every=0), lib=lib, variant=variant) as e:
+        ref_st = e.run(int(st.steps_done))
+        ref = [e.get_field(c) for c in range(6)]
+    assert ref_st.stopped_early == 0 and ref_st.steps_done == st.steps_done
+    for c in range(6):
+        assert np.iscomplexobj(got[c]) and np.abs(got[c].imag).max() > 0
+        assert np.array_equal(got[c], ref[c]), c
+
+
+BLOCH_VARIANTS = {"fused": L.VARIANT_FUSED, "two_pass": L.VARIANT_ZMARCH}
+
+
 # ---------------------------------------------------------------- CPU: the HIP sources under the emulator
+@pytest.mark.parametrize("variant", list(BLOCH_VARIANTS))
+def test_emu_bloch_shutoff_stops_both_handles_and_changes_nothing(variant, emu_lib):
+    check_bloch_shutoff(emu_lib, BLOCH_VARIANTS[variant])
+
+
 @pytest.mark.parametrize("name,shutoff", [("pml_box", 1e-2), ("media_mix", 3e-1), ("absorber_mix", 3e-2), ("drude_in_pml", 3e-2)])
 def test_emu_shutoff_matches_oracle(name, shutoff, emu_lib):
     check_shutoff(emu_lib, name, shutoff)

@@ -703,6 +703,13 @@ def test_axis_renaming_on_the_gpu(case, hip_lib):
             assert np.abs(outs[s][1][k] - v).max() <= 2e-6 * max(np.abs(v).max(), 1e-30), (s, k)
 
 
+@pytest.mark.parametrize("variant", ["fused", "two_pass"])
+def test_bloch_shutoff_stops_both_handles_and_changes_nothing(variant, hip_lib):
+    """The emulator's pin of fdtd_run_bloch's decay path (tests/test_decay_parity.py), same size, on the device."""
+    from test_decay_parity import BLOCH_VARIANTS, check_bloch_shutoff
+    check_bloch_shutoff(hip_lib, BLOCH_VARIANTS[variant])
+
+
 def test_near_to_far_projection_from_gpu_fields(hip_lib):
     """the near fields a FieldProjectionAngleMonitor needs are accumulated ON the device
     (running DFT on the six surfaces of its box, K6) and the N / L integrals over those surfaces are taken ON the

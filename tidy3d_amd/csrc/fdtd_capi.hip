@@ -320,7 +320,7 @@ struct FdtdSolver {
   bool streams_shared = false;       // comm_stream is an alias of stream (fallback)
   // slab-interleaved two-step schedule (fdtd_run): planes per slab; 0 = off, -1 = default
   int tblock = -1;
-  int edge_zchunk = -1;
+  int edge_zchunk = -1;              // z-chunk of the edge launches of a CPML step: -1 = about one wave of workgroups, 0 = as the interior, N = planes
   // Captured step pairs (small grids): a run of steps without monitor records or field-decay checks is replayed as
   // hipGraphs of TWO steps each (set a -> b -> a, psi parity back where it was), one per (field set, psi parity) state
   int use_graph = -1;                // -1 = default (= never: no gain measured, fdtd_run), 0 = never, 1 = whenever possible
@@ -330,7 +330,7 @@ struct FdtdSolver {
   long long step_dev_off = 0;
   long long graph_pairs = 0;
   int mirror_wall[3] = {-1, -1, -1}; // PMC on plus faces: wall index per axis (fdtd_set_mirror_plus), -1 = none
-  int graph_status = 0;              // 0 = no capture attempted, 1 = captured, < 0 = -(100 * stage + hipError) of the failed capture              // z-chunk of the edge launches of a CPML step: -1 = about one wave of workgroups, 0 = as the interior, N = planes
+  int graph_status = 0;              // 0 = no capture attempted, 1 = captured, < 0 = -(100 * stage + hipError) of the failed capture
   long long two_step_pairs = 0;
   int tblock_used = 0;
   // two time steps per sweep (fused2_step_kernel): waves per workgroup (0 = off) and planes per chunk
@@ -2468,6 +2468,7 @@ void advance_tfsf_aux(FdtdSolver* h, bool e_side, long long n, hipStream_t st, b
 
 // fully anisotropic bodies: E^n of the neighbour nodes, saved in front of the E update ...
 void aniso_save(FdtdSolver* h, hipStream_t st) {
+  if (h->aniso.empty()) return;
   dbg_sync(h);
   for (AnisoGroup& a : h->aniso) {
     const float* b1 = field_ptr(h, (a.comp + 1) % 3);
@@ -2477,6 +2478,7 @@ void aniso_save(FdtdSolver* h, hipStream_t st) {
 }
 // ... and the coupling, behind the E update and its sources: every component's correction from the unpatched values, then applied
 void aniso_apply(FdtdSolver* h, hipStream_t st) {
+  if (h->aniso.empty()) return;
   dbg_sync(h);
   for (AnisoGroup& a : h->aniso) {
     const float* b1 = field_ptr(h, (a.comp + 1) % 3);
@@ -2557,6 +2559,43 @@ void launch_ade(FdtdSolver* h, int kbeg, int kend, hipStream_t st, const FieldP*
                        (const uint32_t*)a.cell + t0, a.e_old + t0, a.q + t0, t1 - t0, a.n, zlo, zhi, a.p,
                        paged ? h->disp.cs : nullptr, paged ? (const uint32_t*)a.qoff + t0 : nullptr);
   }
+}
+
+// ---- the terms around the field update of ONE SINGLE step, in the order that is part of the arithmetic -------------------------
+// Every schedule that issues a single step (Run::fused_one, two_pass_step, tb_pair, the z-slab ranks' h_pre / e_post, BlochRun::step)
+// calls these; the order is stated here and nowhere else.  (Step PAIRS — plain_pair, shell_pair, shell2_pair, slab_pair, middle_step —
+// keep their own lists: what they launch depends on what their sweep has already applied.)  Each launcher returns without a launch
+// when its list or layer count is empty, so a schedule that cannot carry a term (tb_pair: no CPML) launches nothing for it.
+// `axes`: the CPML axes that run as slab kernels (7 & ~ the axes inside the sweep); `replica`: the comm stream's copy of the TFSF
+// incident grids.  What stays with the caller, because its place differs between the schedules: fill_mirror, aniso_save /
+// modulation_save, advance_tfsf_aux, the ghost fills, record_monitors.
+// H side, in FRONT of the update of step n, planes [k0, k1): absorber damping of H^{n-1/2}, then H-side sources / TFSF corrections
+// (they only read E^n), then the CPML slabs — the summation order of the fused sweep
+void h_side_terms(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, int axes = 7, bool replica = false) {
+  launch_damp(h, false, k0, k1, st);
+  launch_sources(h, false, n, k0, k1, st, replica);
+  launch_pml(h, false, k0, k1, st, axes);
+}
+// E side, BEHIND the update of step n.  Head: the CPML slabs, then the E-side sources / TFSF corrections ...
+void e_side_head(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, int axes = 7, bool replica = false) {
+  launch_pml(h, true, k0, k1, st, axes);
+  launch_sources(h, true, n, k0, k1, st, replica);
+}
+// ... tail: absorber damping, then the ADE pass (its stored E^{n+1} is the damped one), then the time-modulation patch (the end of
+// the E phase: E_lin of the listed nodes is complete).  Between the two, the fully anisotropic coupling: aniso_apply, or
+// aniso_apply_bloch where it reads both parts of a Bloch pair (BlochRun::step cuts in there).
+// `whole_grid`: the call covers every plane of the grid.  The anisotropic and modulation lists are whole-grid lists, not plane-ranged:
+// they are applied only then.  A caller that works on a plane range (tb_pair's slabs, the cs / st halves of a z-slab rank) passes
+// false — exactly the schedules whose set-up refuses those lists (Run::setup, Run::setup_schedules, BlochRun::setup say where).
+void e_side_tail(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, bool whole_grid) {
+  launch_damp(h, true, k0, k1, st);
+  launch_ade(h, k0, k1, st);
+  if (whole_grid) modulation_apply(h, n, st);
+}
+void e_side_terms(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, bool whole_grid, int axes = 7, bool replica = false) {
+  e_side_head(h, n, k0, k1, st, axes, replica);
+  if (whole_grid) aniso_apply(h, st);
+  e_side_tail(h, n, k0, k1, st, whole_grid);
 }
 
 // behind a two-step sweep that carried the ADE update of its first step (launch_fused2 with use_disp; set B = `fs` or the current
@@ -4002,10 +4041,11 @@ int fdtd_reset(FdtdSolver* h) {
 }
 
 // ---- fdtd_run ---------------------------------------------------------------------------------------------------------------
-// (struct Run, one object per call: fdtd_run.hpp)
+// (struct Run, one object per call: fdtd_run.hpp; struct BlochRun, the same for fdtd_run_bloch: fdtd_run_bloch.hpp)
 }  // extern "C"
 namespace {
 #include "fdtd_run.hpp"
+#include "fdtd_run_bloch.hpp"
 }  // namespace
 extern "C" {
 
@@ -4018,246 +4058,13 @@ int fdtd_run(FdtdSolver* h, int64_t n_steps, FdtdProgressFn progress, void* user
   if (r.loop()) { flush_seams(h, h->stream); return -1; }      // (an error leaves no stale seam columns either)
   return r.finish();
 }
-// Complex (Bloch-periodic) fields: two solvers carry Re and Im of the same simulation (identical grid,
-// media, CPML, ADE and monitors; the Im solver's source weights are the Re solver's times -i) and are
-// stepped together on the Re solver's stream; they only meet in the ghost fills (fdtd_kernels.hpp).
-// phase[a] = 2 pi bloch_vec of axis a (ref boundary.py:55-79 bloch_phase).  n_real[a] > 0 (a = x, y): the
-// axis carries ghost cells at device index 0 and n_real[a] + 1 (the host builds the grid that way and
-// declares PEC walls); z uses its ghost planes when the z faces are FDTD_BC_PERIODIC.  One GPU; the
-// fused sweep unless the handles ask for the two-pass kernels.
+// Complex (Bloch-periodic) fields as a (Re, Im) pair of solvers stepped together (struct BlochRun, one object per call: fdtd_run_bloch.hpp)
 int fdtd_run_bloch(FdtdSolver* hr, FdtdSolver* hi, int64_t n_steps, const double phase[3], const int n_real[3],
                    FdtdProgressFn progress, void* user) {
   if (!hr || !hi) return -1;
-  for (const FdtdSolver* hh : {hr, hi}) if (refuse_whole_grid_monitors(hr, hh, "fdtd_run_bloch", true)) return -1;
-  if (hi->comm) return fail(hr, "fdtd_run_bloch: the communicator of a z-slab belongs to the first (real-part) handle");
-  // fully anisotropic bodies: the Re handle's lists (wrap codes included) drive both parts; the Im handle's carry the same rows
-  const bool aniso = !hr->aniso.empty();
-  if (hi->aniso.size() != hr->aniso.size())
-    return fail(hr, "fdtd_run_bloch: the two solvers must carry the same fully anisotropic lists");
-  for (size_t k = 0; k < hr->aniso.size(); ++k)
-    if (hi->aniso[k].comp != hr->aniso[k].comp || hi->aniso[k].n != hr->aniso[k].n)
-      return fail(hr, "fdtd_run_bloch: the two solvers must carry the same fully anisotropic lists");
-  for (int a = 0; a < 3; ++a)
-    if (hr->mirror_wall[a] >= 0 || hi->mirror_wall[a] >= 0) return fail(hr, "fdtd_run_bloch: PMC on a plus face is not available together with Bloch boundaries");
-  // z-slab decomposition (hr->comm): both parts exchange their ghost planes through the real-part handle's
-  // communicator; the planes that wrap around a Bloch z axis (rank n-1 <-> rank 0) are rotated by exp(-+ i phi_z)
-  // on arrival.  Two-pass kernels, exchanges on the step stream (correct by construction; not overlapped).
-  const bool multi = hr->comm != nullptr;
-  const bool nb_lo = hr->cfg.bc[4] == FDTD_BC_NEIGHBOR, nb_hi = hr->cfg.bc[5] == FDTD_BC_NEIGHBOR;
-  if ((nb_lo || nb_hi) && !multi) return fail(hr, "fdtd_run_bloch: neighbour faces need fdtd_comm_init on the first handle");
-  if (multi && aniso) return fail(hr, "fdtd_run_bloch: fully anisotropic media are not available on z-slabs");
-  // time-modulated media: the update is linear with real coefficients — each part is patched by its own handle's lists, the same rows
-  const bool modulated = !hr->modulation.empty();
-  if (hi->modulation.size() != hr->modulation.size())
-    return fail(hr, "fdtd_run_bloch: the two solvers must carry the same time-modulation lists");
-  for (size_t k = 0; k < hr->modulation.size(); ++k)
-    if (hi->modulation[k].comp != hr->modulation[k].comp || hi->modulation[k].n != hr->modulation[k].n)
-      return fail(hr, "fdtd_run_bloch: the two solvers must carry the same time-modulation lists");
-  if (multi && modulated) return fail(hr, "fdtd_run_bloch: time-modulated media are not available on z-slabs");
-  if (hi->cfg.bc[4] != hr->cfg.bc[4] || hi->cfg.bc[5] != hr->cfg.bc[5])
-    return fail(hr, "fdtd_run_bloch: the two solvers must have the same z faces");
-  if (hr->g.nx != hi->g.nx || hr->g.ny != hi->g.ny || hr->g.nz != hi->g.nz || hr->cfg.device != hi->cfg.device ||
-      hr->mons.size() != hi->mons.size() || hr->step != hi->step)
-    return fail(hr, "fdtd_run_bloch: the two solvers must describe the same simulation");
-  const GridP& g = hr->g;
-  const int nz = g.nz;
-  const int N[3] = {g.nx, g.ny, nz};
-  for (int a = 0; a < 2; ++a)
-    if (n_real[a] < 0 || (n_real[a] > 0 && n_real[a] + 2 > N[a]))
-      return fail(hr, "fdtd_run_bloch: axis %d has %d cells, cannot hold %d real cells + 2 ghost cells", a, N[a], n_real[a]);
-  HIPCHK(hr, hipSetDevice(hr->cfg.device));
-  hipStream_t st = hr->stream;
-  HIPCHK(hr, hipStreamSynchronize(hi->stream));
-  FdtdSolver* both[2] = {hr, hi};
-  for (FdtdSolver* h : both) {
-    for (hipEvent_t e : h->kev) hipEventDestroy(e);
-    h->kev.clear(); h->kev_kind.clear();
-    h->stats.stopped_early = 0;
-  }
-  HIPCHK(hr, hipEventRecord(hr->ev0, st));
-  const bool per_z = hr->cfg.bc[4] == FDTD_BC_PERIODIC;
-  const bool fused = !multi && !hr->mat4b && (g.nx % 4 == 0) && hr->rows_f <= 15 &&
-                     (hr->cfg.variant == FDTD_VARIANT_FUSED || hr->cfg.variant == FDTD_VARIANT_AUTO);
-  if (fused) for (FdtdSolver* h : both) if (ensure_second_set(h)) return -1;
-  if (fused && !hr->tuned && !hr->user_geometry && !hi->user_geometry &&
-      (n_cells(hr) >= (1LL << 20) || hr->autotune == 2)) {
-    // same rule as fdtd_run: probe the tile shape when the default one launches less than a wave of workgroups
-    const long long wgs = (long long)((g.nx + 255) / 256) * ((g.ny + hr->rows_f - 1) / hr->rows_f) *
-                          ((nz + hr->zchunk_f - 1) / hr->zchunk_f);
-    if (wgs < 768 || hr->autotune) {
-      if (autotune_fused(hr, st)) return -1;
-      hi->rows_f = hr->rows_f; hi->zchunk_f = hr->zchunk_f; hi->tuned = true;
-    }
-  }
-  float cph[3], sph[3];
-  for (int a = 0; a < 3; ++a) { cph[a] = (float)std::cos(phase[a]); sph[a] = (float)std::sin(phase[a]); }
-  // (cos, sin) of each wrap code of the coupling lists: the sum of the phases the ghost fills apply on the axes it crosses
-  AnisoPhaseTab wrap_tab{};
-  if (aniso) {
-    const double ph[3] = {n_real[0] > 0 ? phase[0] : 0.0, n_real[1] > 0 ? phase[1] : 0.0, per_z ? phase[2] : 0.0};
-    for (int c = 0; c < kWrapCodes; ++c) {
-      double p = 0.0;
-      for (int a = 0; a < 3; ++a) {
-        const int w = (c >> (2 * a)) & 3;
-        p += w == 1 ? ph[a] : (w == 2 ? -ph[a] : 0.0);
-      }
-      wrap_tab.r[c] = make_float2((float)std::cos(p), (float)std::sin(p));
-    }
-  }
-  // E-side tail of a step: CPML and sources of both parts, the coupling (it reads both parts), then damping and ADE
-  auto e_tail = [&](long long n) {
-    if (!aniso) {
-      for (FdtdSolver* h : both) {
-        launch_pml(h, true, 0, nz, st);
-        launch_sources(h, true, n, 0, nz, st);
-        launch_damp(h, true, 0, nz, st);
-        launch_ade(h, 0, nz, st);
-        modulation_apply(h, n, st);
-      }
-      return;
-    }
-    for (FdtdSolver* h : both) {
-      launch_pml(h, true, 0, nz, st);
-      launch_sources(h, true, n, 0, nz, st);
-    }
-    aniso_apply_bloch(hr, hi, wrap_tab, st);
-    for (FdtdSolver* h : both) {
-      launch_damp(h, true, 0, nz, st);
-      launch_ade(h, 0, nz, st);
-      modulation_apply(h, n, st);
-    }
-  };
-  const long long pc = plane_cells(hr);
-  // (pointers are taken at call time: the fused sweep swaps the field sets every step)
-  auto six = [&]() { Cplx6P F; for (int c = 0; c < 6; ++c) { F.f[c].re = field_ptr(hr, c); F.f[c].im = field_ptr(hi, c); } return F; };
-  auto fill_xy = [&]() {          // y first, then x over all rows (ghost rows included): corners get both phases
-    for (int a = 1; a >= 0; --a) {
-      if (n_real[a] <= 0) continue;
-      const long long cells = (long long)(a == 0 ? g.ny : g.nx) * nz;
-      hipLaunchKernelGGL(bloch_ghost_fill_kernel, dim3(nblk(cells)), dim3(256), 0, st, g, a, n_real[a], six(), cph[a], sph[a], nz);
-    }
-  };
-  auto plane = [&](int c, long long dst_plane, long long src_plane, float s) {
-    hipLaunchKernelGGL(bloch_plane_kernel, dim3(nblk(pc)), dim3(256), 0, st, field_ptr(hr, c) + dst_plane * pc,
-                       field_ptr(hi, c) + dst_plane * pc, (const float*)(field_ptr(hr, c) + src_plane * pc),
-                       (const float*)(field_ptr(hi, c) + src_plane * pc), cph[2], s, pc);
-  };
-  // ghost-plane exchange of both parts with the z neighbours (two-pass schedule): H phase = top H_x, H_y planes
-  // up, E phase = bottom E_x, E_y planes down; a plane that crossed the periodic wrap is rotated where it lands
-  const int lo_rank = (hr->rank - 1 + hr->n_ranks) % hr->n_ranks, hi_rank = (hr->rank + 1) % hr->n_ranks;
-  const bool wrap_lo = nb_lo && hr->rank == 0, wrap_hi = nb_hi && hr->rank == hr->n_ranks - 1;
-  auto exchange_pair = [&](bool e_side) -> int {
-    const int c0 = e_side ? 0 : 3;
-    NCCLCHK(hr, ncclGroupStart());
-    for (FdtdSolver* h : both)
-      for (int c = c0; c < c0 + 2; ++c) {
-        float* f = field_ptr(h, c);
-        if (!e_side && nb_hi) NCCLCHK(hr, ncclSend(f + (long long)(nz - 1) * pc, pc, ncclFloat, hi_rank, hr->comm, st));
-        if (e_side && nb_lo) NCCLCHK(hr, ncclSend(f, pc, ncclFloat, lo_rank, hr->comm, st));
-      }
-    for (FdtdSolver* h : both)
-      for (int c = c0; c < c0 + 2; ++c) {
-        float* f = field_ptr(h, c);
-        if (!e_side && nb_lo) NCCLCHK(hr, ncclRecv(f - pc, pc, ncclFloat, lo_rank, hr->comm, st));
-        if (e_side && nb_hi) NCCLCHK(hr, ncclRecv(f + (long long)nz * pc, pc, ncclFloat, hi_rank, hr->comm, st));
-      }
-    NCCLCHK(hr, ncclGroupEnd());
-    if (!e_side && wrap_lo) { plane(3, -1, -1, -sph[2]); plane(4, -1, -1, -sph[2]); }       // exp(-i phi_z), in place
-    if (e_side && wrap_hi) { plane(0, nz, nz, sph[2]); plane(1, nz, nz, sph[2]); }          // exp(+i phi_z)
-    return 0;
-  };
-  int64_t done = 0;
-  for (; done < n_steps; ++done) {
-    const long long n = hr->step;
-    bool rec = false;
-    for (Monitor& m : hr->mons) if (m.next < m.steps.size() && m.steps[m.next] == n) rec = true;
-    if (rec) for (FdtdSolver* h : both) record_monitors(h, n, false, st);
-    if (aniso) aniso_save_bloch(hr, hi, st);     // (E^n of the nodes around fully anisotropic cells, in front of either sweep)
-    for (FdtdSolver* h : both) modulation_save(h, st);      // (E^n of the nodes inside time-modulated media, likewise)
-    // H-side corrections of both parts, then the ghost cells (they must carry the corrections too)
-    for (FdtdSolver* h : both) {
-      launch_damp(h, false, 0, nz, st);
-      launch_sources(h, false, n, 0, nz, st);
-      launch_pml(h, false, 0, nz, st);
-    }
-    fill_xy();
-    if (fused) {
-      if (per_z) {       // ghost(-1) = exp(-i phi_z) [E (3 comps), H_x, H_y][nz-1];  ghost(nz) = exp(+i phi_z) E_{x,y}[0]
-        for (int c = 0; c < 5; ++c) plane(c, -1, nz - 1, -sph[2]);
-        plane(0, nz, 0, sph[2]);
-        plane(1, nz, 0, sph[2]);
-      }
-      for (FdtdSolver* h : both) if (launch_fused(h, st, 0)) return -1;
-      if (rec) for (FdtdSolver* h : both) record_monitors(h, n, true, st);
-      e_tail(n);
-    } else {
-      if (per_z) { plane(0, nz, 0, sph[2]); plane(1, nz, 0, sph[2]); }      // E ghost(nz) of E^n (first step / after set_field)
-      if (multi && exchange_pair(true)) return -1;                          // ... or the upper neighbour's bottom plane
-      for (FdtdSolver* h : both) launch_h_main(h, 0, nz, st);
-      if (per_z) { plane(3, -1, nz - 1, -sph[2]); plane(4, -1, nz - 1, -sph[2]); }
-      else if (!nb_lo) for (FdtdSolver* h : both) fill_ghost_h(h, st);
-      if (multi && exchange_pair(false)) return -1;
-      if (rec) for (FdtdSolver* h : both) record_monitors(h, n, true, st);
-      if (aniso) {
-        for (FdtdSolver* h : both) launch_e_main(h, 0, nz, st);
-        e_tail(n);
-      } else {
-        for (FdtdSolver* h : both) {
-          launch_e_main(h, 0, nz, st);
-          launch_pml(h, true, 0, nz, st);
-          launch_sources(h, true, n, 0, nz, st);
-          launch_damp(h, true, 0, nz, st);
-          launch_ade(h, 0, nz, st);
-          modulation_apply(h, n, st);
-        }
-      }
-      if (!per_z && !nb_hi) for (FdtdSolver* h : both) fill_ghost_e(h, st);
-    }
-    hr->step = hi->step = n + 1;
-    // ---------------- field decay / divergence (|E|^2 of both parts) ----------------
-    if (hr->decay_every > 0 && (hr->step % hr->decay_every) == 0) {
-      double en = 0.0;
-      for (FdtdSolver* h : both) {
-        double part = 0.0;
-        if (eval_energy(h, st, &part)) { hr->err = h->err; return -1; }
-        en += part;
-      }
-      if (multi) {            // sum over the ranks (same stream as every other RCCL call of this run)
-        double* tmp = hr->energy_dev;
-        HIPCHK(hr, hipMemcpyAsync(tmp, &en, sizeof(double), hipMemcpyHostToDevice, st));
-        NCCLCHK(hr, ncclAllReduce(tmp, tmp, 1, ncclDouble, ncclSum, hr->comm, st));
-        HIPCHK(hr, hipMemcpyAsync(&en, tmp, sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hr, hipStreamSynchronize(st));
-      }
-      if (!std::isfinite(en)) {
-        hr->stats.diverged = hi->stats.diverged = 1;
-        ++done;
-        break;
-      }
-      if (en > hr->energy_max) hr->energy_max = hi->energy_max = en;
-      hr->stats.field_decay = hi->stats.field_decay = hr->energy_max > 0 ? en / hr->energy_max : 1.0;
-      if (progress && progress(hr->step, 0.0, hr->stats.field_decay, user)) { ++done; break; }
-      if (hr->shutoff > 0 && hr->step > hr->decay_ref && hr->stats.field_decay < hr->shutoff) {
-        hr->stats.stopped_early = hi->stats.stopped_early = 1;
-        ++done;
-        break;
-      }
-    }
-  }
-  // leave the ghost cells of E^n, H^{n-1/2} consistent for whoever reads the fields next
-  fill_xy();
-  HIPCHK(hr, hipEventRecord(hr->ev1, st));
-  HIPCHK(hr, hipStreamSynchronize(st));
-  HIPCHK(hr, hipGetLastError());
-  float ms = 0.f;
-  HIPCHK(hr, hipEventElapsedTime(&ms, hr->ev0, hr->ev1));
-  for (FdtdSolver* h : both) {
-    h->stats.run_ms = ms;
-    h->stats.steps_done = h->step;
-    h->stats.h_kernel_ms = h->stats.e_kernel_ms = h->stats.fused_kernel_ms = 0.0;
-    h->stats.h_kernel_launches = h->stats.e_kernel_launches = h->stats.fused_kernel_launches = 0;
-  }
-  return 0;
+  BlochRun r{hr, hi, n_steps, phase, n_real, progress, user};
+  if (r.setup() || r.loop()) return -1;
+  return r.finish();
 }
 
 int fdtd_set_option(FdtdSolver* h, int key, int value) {

@@ -9,6 +9,78 @@
 //   the loop except field-decay checks.  FDTD_OPT_DEBUG_SYNC = 1 puts a device-wide synchronisation behind every launch
 //   (time_end) and every step: a schedule whose result then differs from the normal run has a missing edge
 //   (tests/test_gpu_parity.py::test_schedules_do_not_depend_on_stream_timing).
+//   The order of the correction launches around a single step's field update is defined in ONE place, h_side_terms / e_side_terms
+//   (fdtd_capi.hip, beside the launchers): every single-step schedule here and in fdtd_run_bloch.hpp calls them.
+
+// ---- what fdtd_run (Run) and fdtd_run_bloch (BlochRun, fdtd_run_bloch.hpp) share: free functions over one handle or the two of a
+// Bloch pair (the first handle is the one whose events, communicator and shutoff settings count) ------------------------------------
+using Handles = std::initializer_list<FdtdSolver*>;
+// run entry: the last run's per-launch timing events go, no early stop yet, the run's clock starts on st
+int run_begin(Handles hs, hipStream_t st) {
+  for (FdtdSolver* h : hs) {
+    for (hipEvent_t e : h->kev) hipEventDestroy(e);
+    h->kev.clear(); h->kev_kind.clear();
+    h->stats.stopped_early = 0;
+  }
+  FdtdSolver* h0 = *hs.begin();
+  HIPCHK(h0, hipEventRecord(h0->ev0, st));
+  return 0;
+}
+// a monitor records at step n
+bool rec_at(const FdtdSolver* h, long long n) {
+  for (const Monitor& m : h->mons) if (m.next < m.steps.size() && m.steps[m.next] == n) return true;
+  return false;
+}
+// Tile-shape probing by default: when the default shape launches fewer workgroups than this.  The two runs differ ON RECORD, not
+// by design: fdtd_run probes below two waves of workgroups at 4 waves per SIMD (256 CUs x 4 x 2), fdtd_run_bloch kept the earlier
+// "one wave at 3" (256 x 3); and fdtd_run applies the size threshold (n_cells, autotune == 2) to a probe on request too, while
+// fdtd_run_bloch applies it in front of both conditions.  Results do not depend on the shape.
+constexpr long long kProbeBelowWgs = 2048, kProbeBelowWgsBloch = 768;
+long long default_shape_wgs(const FdtdSolver* h) {
+  return (long long)((h->g.nx + 255) / 256) * ((h->g.ny + h->rows_f - 1) / h->rows_f) * ((h->g.nz + h->zchunk_f - 1) / h->zchunk_f);
+}
+// the energy summed over the ranks of h's communicator (1 double every decay_every steps), on stream s — every RCCL call of a
+// communicator is issued on ONE stream, in the same order on all ranks: the comm stream in fdtd_run, the step stream in fdtd_run_bloch
+int allreduce_energy(FdtdSolver* h, double* en, hipStream_t s) {
+  double* tmp = h->energy_dev;
+  HIPCHK(h, hipMemcpyAsync(tmp, en, sizeof(double), hipMemcpyHostToDevice, s));
+  NCCLCHK(h, ncclAllReduce(tmp, tmp, 1, ncclDouble, ncclSum, h->comm, s));
+  HIPCHK(h, hipMemcpyAsync(en, tmp, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  return 0;
+}
+// the verdict of a field-decay check on the summed energy `en`, written to every handle.  -> 1: the run ends here (diverged, the
+// caller's progress callback asked for it, or the shutoff level is reached)
+int decay_verdict(Handles hs, double en, FdtdProgressFn progress, void* user) {
+  FdtdSolver* h0 = *hs.begin();
+  if (!std::isfinite(en)) {
+    for (FdtdSolver* h : hs) h->stats.diverged = 1;
+    return 1;
+  }
+  if (en > h0->energy_max) for (FdtdSolver* h : hs) h->energy_max = en;
+  const double decay = h0->energy_max > 0 ? en / h0->energy_max : 1.0;
+  for (FdtdSolver* h : hs) h->stats.field_decay = decay;
+  if (progress && progress(h0->step, 0.0, decay, user)) return 1;
+  if (h0->shutoff > 0 && h0->step > h0->decay_ref && decay < h0->shutoff) {
+    for (FdtdSolver* h : hs) h->stats.stopped_early = 1;
+    return 1;
+  }
+  return 0;
+}
+// the end of a run: its time (ev0 -> ev1 of the first handle) and step count into every handle's stats, the per-kernel timers at zero
+int run_stats(Handles hs) {
+  FdtdSolver* h0 = *hs.begin();
+  float ms = 0.f;
+  HIPCHK(h0, hipEventElapsedTime(&ms, h0->ev0, h0->ev1));
+  for (FdtdSolver* h : hs) {
+    h->stats.run_ms = ms;
+    h->stats.steps_done = h->step;
+    h->stats.h_kernel_ms = h->stats.e_kernel_ms = h->stats.fused_kernel_ms = h->stats.shell_kernel_ms = h->stats.seam_kernel_ms = h->seam_flush_ms = 0.0;
+    h->stats.h_kernel_launches = h->stats.e_kernel_launches = h->stats.fused_kernel_launches = h->stats.shell_kernel_launches = h->stats.seam_kernel_launches = 0;
+  }
+  return 0;
+}
+
 struct GraphRec { const float* set; int parity; hipGraphExec_t exec; };
 // The form steps n and n + 1 take when they go out as one pair (Run::choose_pair decides, Run::loop dispatches):
 //   Plain: one two-step sweep over the whole grid; Shell: the bulk as a two-step sweep, the CPML shell as two single steps (round-4 form);
@@ -74,16 +146,12 @@ struct Run {
   // a debugging aid (FDTD_OPT_DEBUG_SYNC): everything issued so far has finished before anything else is issued
   void sync_point() { if (h->debug_sync) (void)hipDeviceSynchronize(); }
   bool decay_at(long long m) const { return h->decay_every > 0 && (m % h->decay_every) == 0; }
-  bool rec_at(long long n) const {
-    for (const Monitor& m : h->mons) if (m.next < m.steps.size() && m.steps[m.next] == n) return true;
-    return false;
-  }
   // `count` steps from step n on may go out with nothing of the host's between them: that many are left, no decay check falls behind
   // any but the last (at n + 1 ... n + count - 1), and no monitor records at the steps named
   bool steps_free(long long n, int count, std::initializer_list<long long> no_rec = {}) const {
     if (done + count > n_steps) return false;
     for (int q = 1; q < count; ++q) if (decay_at(n + q)) return false;
-    for (long long m : no_rec) if (rec_at(m)) return false;
+    for (long long m : no_rec) if (rec_at(h, m)) return false;
     return true;
   }
   bool two_steps_free(long long n, std::initializer_list<long long> no_rec = {}) const { return steps_free(n, 2, no_rec); }
@@ -122,6 +190,8 @@ struct Run {
     multi = h->comm != nullptr;     // also true for a 1-rank communicator (self exchange)
     nb_lo = h->cfg.bc[4] == FDTD_BC_NEIGHBOR, nb_hi = h->cfg.bc[5] == FDTD_BC_NEIGHBOR;
     if ((nb_lo || nb_hi) && !multi) return fail(h, "fdtd_run: neighbour faces need fdtd_comm_init");
+    // (these two refusals are what every plane-range call of e_side_terms on a z-slab rank relies on — e_post, the cs / st halves of
+    //  two_pass_step pass "not the whole grid", and the whole-grid lists are empty there)
     if (multi && !h->aniso.empty()) return fail(h, "fdtd_run: fully anisotropic media are not available on z-slabs");
     if (multi && !h->modulation.empty()) return fail(h, "fdtd_run: time-modulated media are not available on z-slabs");
     // (PMC on a plus face of a z-slab rank: x / y walls are local to every plane; a z wall belongs to the rank without an upper
@@ -133,10 +203,7 @@ struct Run {
     // runs that use BOTH streams first make sure the two really overlap (once per engine; falls back to one stream)
     if ((multi || any_pml(h) || h->tblock > 4096) && probe_stream_overlap(h)) return -1;
     st = h->stream, cs = h->comm_stream;
-    for (hipEvent_t e : h->kev) hipEventDestroy(e);
-    h->kev.clear(); h->kev_kind.clear();
-    h->stats.stopped_early = 0;
-    HIPCHK(h, hipEventRecord(h->ev0, st));
+    if (run_begin({h}, st)) return -1;
     if (multi && (nb_lo || nb_hi) && nz < 2) return fail(h, "fdtd_run: a z-slab needs at least 2 planes");
     // the fused sweep is the default single-GPU path whenever rows are float4-aligned
     // (a wide material table — more than 1023 media, 16-bit indices, no LDS copy: on one GPU the single-step sweep reads it on
@@ -170,11 +237,7 @@ struct Run {
     // profiles/r01m_narrow_grid_axis_shift.log) and the probe costs a dozen sweeps once.  Results do not depend
     // on the shape.  (autotune == 2 lifts the size threshold: test aid for the emulated library)
     bool under_one_wave = false;
-    if (fused && !h->tuned && !h->user_geometry) {
-      const long long wgs = (long long)((h->g.nx + 255) / 256) * ((h->g.ny + h->rows_f - 1) / h->rows_f) *
-                            ((nz + h->zchunk_f - 1) / h->zchunk_f);
-      under_one_wave = wgs < 2048;       // (two waves of workgroups at 4 waves per SIMD)
-    }
+    if (fused && !h->tuned && !h->user_geometry) under_one_wave = default_shape_wgs(h) < kProbeBelowWgs;
     if ((fused || fused_multi) && (h->autotune || under_one_wave) && !h->tuned && !h->user_geometry &&
         (n_cells(h) >= (1LL << 20) || h->autotune == 2)) {
       if (autotune_fused(h, st)) return -1;
@@ -206,21 +269,16 @@ struct Run {
     psi_ghosts = fused_multi && (pml_in_m & 3) != 0;
     return 0;
   }
-  void e_post(long long n, int k0, int k1, hipStream_t s, bool replica) {
-    launch_pml(h, true, k0, k1, s, 7 & ~pml_in_m);
-    launch_sources(h, true, n, k0, k1, s, replica);
-    launch_damp(h, true, k0, k1, s);       // before the ADE pass: its stored E^{n+1} is the damped one
-    launch_ade(h, k0, k1, s);
-  }
+  // z-slab ranks, planes [k0, k1): the E-side terms of step n (a plane range: no whole-grid lists — setup refuses them on z-slabs) ...
+  void e_post(long long n, int k0, int k1, hipStream_t s, bool replica) { e_side_terms(h, n, k0, k1, s, false, 7 & ~pml_in_m, replica); }
+  // ... and the H-side terms (E^n and H^{n-1/2} of these planes are complete: the images beyond PMC plus walls first)
   void h_pre(long long n, int k0, int k1, hipStream_t s, bool replica) {
-    fill_mirror(h, s, k0, k1);             // (E^n and H^{n-1/2} of these planes are complete: the images beyond PMC plus walls first)
-    launch_damp(h, false, k0, k1, s);
-    launch_sources(h, false, n, k0, k1, s, replica);
-    launch_pml(h, false, k0, k1, s, 7 & ~pml_in_m);
+    fill_mirror(h, s, k0, k1);
+    h_side_terms(h, n, k0, k1, s, 7 & ~pml_in_m, replica);
   }
   // all planes on st: monitors of step n, H-side pre-corrections, then the exchange on cs
   int prime(long long n) {
-    if (rec_at(n)) record_monitors(h, n, false, st);
+    if (rec_at(h, n)) record_monitors(h, n, false, st);
     h_pre(n, 0, nz, st, false);
     advance_tfsf_aux(h, false, n, st, false);
     advance_tfsf_aux(h, false, n, st, true);
@@ -264,6 +322,8 @@ struct Run {
     // pairs in which no monitor records and no field-decay check falls on the middle step.
     tb_req = h->tblock < 0 ? 0 : (h->tblock % 4096);
     tb_two_streams = h->tblock > 4096 && h->stream_overlap == 1;
+    // (tb_pair's slabs are plane ranges: its e_side_terms pass "not the whole grid" — hence no fully anisotropic and no modulation lists
+    //  here; and no CPML: the launch_pml inside h_side_terms / e_side_terms launches nothing on this schedule)
     tb_ok = fused && tb_req > 0 && !any_pml(h) && h->tfsf.empty() && h->cfg.bc[4] != FDTD_BC_PERIODIC &&
                        h->mirror_wall[0] < 0 && h->mirror_wall[1] < 0 && h->mirror_wall[2] < 0 && h->aniso.empty() &&
                        h->modulation.empty() && nz >= 2 * tb_req;
@@ -297,13 +357,10 @@ struct Run {
       hipStream_t q = st;
       if (tb_two_streams && s >= 3) HIPCHK(h, hipStreamWaitEvent(q, tb_ev[(size_t)2 * (s - 3) + 1], 0));   // stay <= 3 slabs ahead of B
       const int k0 = zs(s), k1 = zs(s + 1);
-      launch_damp(h, false, k0, k1, q);
-      launch_sources(h, false, n, k0, k1, q);
+      h_side_terms(h, n, k0, k1, q);
       if (launch_fused_range(h, q, {.k0 = k0, .k1 = k1})) return -1;
       swap_sets(h);                                        // h->f = b: the E-side corrections of step n act on E^{n+1}
-      launch_sources(h, true, n, k0, k1, q);
-      launch_damp(h, true, k0, k1, q);
-      launch_ade(h, k0, k1, q);
+      e_side_terms(h, n, k0, k1, q, false);
       swap_sets(h);
       if (tb_two_streams) HIPCHK(h, hipEventRecord(tb_ev[(size_t)2 * s], q));
       return 0;
@@ -313,14 +370,11 @@ struct Run {
       if (tb_two_streams) HIPCHK(h, hipStreamWaitEvent(q, tb_ev[(size_t)2 * std::min(s + 1, S - 1)], 0));
       const int k0 = zs(s), k1 = zs(s + 1);
       swap_sets(h);                                        // h->f = b (E^{n+1}, H^{n+1/2}), h->f2 = a
-      launch_damp(h, false, k0, k1, q);
-      launch_sources(h, false, n + 1, k0, k1, q);
+      h_side_terms(h, n + 1, k0, k1, q);
       const int rc = launch_fused_range(h, q, {.k0 = k0, .k1 = k1});
       swap_sets(h);                                        // h->f = a again: slab s now holds E^{n+2}, H^{n+3/2}
       if (rc) return -1;
-      launch_sources(h, true, n + 1, k0, k1, q);
-      launch_damp(h, true, k0, k1, q);
-      launch_ade(h, k0, k1, q);
+      e_side_terms(h, n + 1, k0, k1, q, false);
       if (tb_two_streams) HIPCHK(h, hipEventRecord(tb_ev[(size_t)2 * s + 1], q));
       return 0;
     };
@@ -350,9 +404,7 @@ struct Run {
     fill_mirror(h, st, h->cfg.bc[4] == FDTD_BC_PERIODIC ? -1 : 0, h->cfg.bc[4] == FDTD_BC_PERIODIC ? nz + 1 : nz);
     aniso_save(h, st);                     // (E^n of the nodes around fully anisotropic cells: the sweep's read set is this set)
     modulation_save(h, st);                // (E^n of the nodes inside time-modulated media)
-    launch_damp(h, false, 0, nz, st);
-    launch_sources(h, false, n, 0, nz, st);
-    launch_pml(h, false, 0, nz, st, 7 & ~pml_in);
+    h_side_terms(h, n, 0, nz, st, 7 & ~pml_in);
     advance_tfsf_aux(h, false, n, st);
     if (h->cfg.bc[4] == FDTD_BC_PERIODIC) fill_ghost_h(h, st);   // ghost(-1) must carry the pre-corrections too
     // small grids are bound by dependent launches, not by occupancy: one launch of the all-axes instantiation
@@ -378,12 +430,7 @@ struct Run {
       swap_psi_h(h, pml_in);
     }
     if (rec_post) record_monitors(h, n, true, st);
-    launch_pml(h, true, 0, nz, st, 7 & ~pml_in);
-    launch_sources(h, true, n, 0, nz, st);
-    aniso_apply(h, st);
-    launch_damp(h, true, 0, nz, st);
-    launch_ade(h, 0, nz, st);
-    modulation_apply(h, n, st);            // (the end of the E phase: E_lin of the listed nodes is complete)
+    e_side_terms(h, n, 0, nz, st, true, 7 & ~pml_in);
     advance_tfsf_aux(h, true, n, st);
     fill_ghost_fused(h, st);
     return 0;
@@ -589,7 +636,7 @@ struct Run {
     HIPCHK(h, hipStreamWaitEvent(st, h->ev_shell_b, 0));
     swap_sets(h);
     pair_record(h, tb, n, st);
-    if (rec_at(n + 1)) record_monitors(h, n + 1, true, st);
+    if (rec_at(h, n + 1)) record_monitors(h, n + 1, true, st);
     launch_sources(h, true, n + 1, 0, nz, st);
     launch_ade(h, 0, nz, st);
     advance_tfsf_aux(h, true, n + 1, st);
@@ -675,7 +722,7 @@ struct Run {
     swap_psi_h(h, 7);
     swap_psi_e(h);
     pair_record(h, tb, n, st);
-    if (rec_at(n + 1)) record_monitors(h, n + 1, true, st);
+    if (rec_at(h, n + 1)) record_monitors(h, n + 1, true, st);
     if (!holes && !pc.spg) {
       advance_tfsf_aux(h, true, n, st);
       advance_tfsf_aux(h, false, n + 1, st);
@@ -762,7 +809,7 @@ struct Run {
   // the step about to be issued: does a monitor record at it (rec), can steps n and n + 1 go out as one sweep, in which form (pc)
   int begin_step() {
     n = h->step;
-    rec = !fused_multi && rec_at(n);
+    rec = !fused_multi && rec_at(h, n);
     if (rec) flush_seams(h, st);
     if (rec && multi) {
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
@@ -905,8 +952,8 @@ struct Run {
     }
     swap_sets(h);
     swap_psi_h(h, pml_in_m);
-    const bool rec_post = rec_at(n);
-    if (rec_post || last || rec_at(n + 1)) {
+    const bool rec_post = rec_at(h, n);
+    if (rec_post || last || rec_at(h, n + 1)) {
       // joined tail: everything after the sweeps on st
       HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));
       if (rec_post) record_monitors(h, n, true, st);
@@ -950,7 +997,7 @@ struct Run {
                           !h->step_dev_mode && !h->debug_sync;
     if (launch_fused2(h, n, st, tb, &sources2_done, &damp2_done, nullptr, pc.disp, false, pc.spg ? spg_params(h) : SrcP{}, defer_ok)) return -1;
     pair_record(h, tb, n, st);                           // (H^{n+3/2} is not touched by the E-side sources that follow)
-    if (rec_at(n + 1)) record_monitors(h, n + 1, true, st);      // DFT records at the middle step: their H terms, from the write set
+    if (rec_at(h, n + 1)) record_monitors(h, n + 1, true, st);      // DFT records at the middle step: their H terms, from the write set
     if (!sources2_done) launch_sources(h, true, n + 1, 0, nz, st);
     if (h->has_damp && !damp2_done) launch_damp(h, true, 0, nz, st);
     if (pc.disp) launch_ade2(h, st);                     // (the ADE update of step n + 1 follows its sources and damping, as launch_ade does)
@@ -976,17 +1023,13 @@ struct Run {
     }
     if (multi && nb_hi) {
       HIPCHK(h, hipStreamWaitEvent(cs, h->ev_e_int, 0));
-      launch_damp(h, false, h_top, nz, cs);          // absorber layers damp H^{n-1/2} before anything is added
-      launch_sources(h, false, n, h_top, nz, cs);    // H-side corrections first (they only read E^n),
-      launch_pml(h, false, h_top, nz, cs);           // in the summation order of the fused sweep
+      h_side_terms(h, n, h_top, nz, cs);
       launch_h_main(h, h_top, nz, cs);
       HIPCHK(h, hipEventRecord(h->ev_h_bnd, cs));
     }
     if (multi) HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
     if (!multi) fill_mirror(h, st, 0, nz);
-    launch_damp(h, false, 0, h_top, st);
-    launch_sources(h, false, n, 0, h_top, st);
-    launch_pml(h, false, 0, h_top, st);
+    h_side_terms(h, n, 0, h_top, st);
     launch_h_main(h, 0, h_top, st);
     advance_tfsf_aux(h, false, n, st);
     if (multi) {
@@ -1005,22 +1048,14 @@ struct Run {
     if (multi && nb_lo) {
       HIPCHK(h, hipStreamWaitEvent(cs, h->ev_h_int, 0));
       launch_e_main(h, 0, e_bot, cs);
-      launch_pml(h, true, 0, e_bot, cs);
-      launch_sources(h, true, n, 0, e_bot, cs);
-      launch_damp(h, true, 0, e_bot, cs);
-      launch_ade(h, 0, e_bot, cs);
+      e_side_terms(h, n, 0, e_bot, cs, false);
       HIPCHK(h, hipEventRecord(h->ev_e_bnd, cs));
     }
     if (multi && nb_hi) HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));
     aniso_save(h, st);                     // (these kernels update E in place: E^n of the nodes around fully anisotropic cells first)
     modulation_save(h, st);
     launch_e_main(h, e_bot, nz, st);
-    launch_pml(h, true, e_bot, nz, st);
-    launch_sources(h, true, n, e_bot, nz, st);
-    aniso_apply(h, st);
-    launch_damp(h, true, e_bot, nz, st);
-    launch_ade(h, e_bot, nz, st);
-    modulation_apply(h, n, st);
+    e_side_terms(h, n, e_bot, nz, st, !multi);     // (one GPU: [e_bot, nz) is the whole grid; a z-slab rank carries no whole-grid lists — setup)
     advance_tfsf_aux(h, true, n, st);
     if (multi) {
       HIPCHK(h, hipEventRecord(h->ev_e_int, st));
@@ -1034,32 +1069,12 @@ struct Run {
   }
   // field decay / divergence every decay_every steps (joins the streams; the only host synchronisation of the loop).  -> 1: the run ends here
   int decay_check() {
-    if (decay_at(h->step)) {
-      if (multi) HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
-      double en = 0.0;
-      if (eval_energy(h, st, &en)) return -1;
-      if (multi) {
-        // sum over ranks (1 double every decay_every steps).  Every RCCL call of this communicator
-        // is issued on the comm stream, in the same order on all ranks — never from two streams.
-        double* tmp = h->energy_dev;
-        HIPCHK(h, hipMemcpyAsync(tmp, &en, sizeof(double), hipMemcpyHostToDevice, cs));
-        NCCLCHK(h, ncclAllReduce(tmp, tmp, 1, ncclDouble, ncclSum, h->comm, cs));
-        HIPCHK(h, hipMemcpyAsync(&en, tmp, sizeof(double), hipMemcpyDeviceToHost, cs));
-        HIPCHK(h, hipStreamSynchronize(cs));
-      }
-      if (!std::isfinite(en)) {
-        h->stats.diverged = 1;
-        return 1;
-      }
-      if (en > h->energy_max) h->energy_max = en;
-      h->stats.field_decay = h->energy_max > 0 ? en / h->energy_max : 1.0;
-      if (progress && progress(h->step, 0.0, h->stats.field_decay, user)) return 1;
-      if (h->shutoff > 0 && h->step > h->decay_ref && h->stats.field_decay < h->shutoff) {
-        h->stats.stopped_early = 1;
-        return 1;
-      }
-    }
-    return 0;
+    if (!decay_at(h->step)) return 0;
+    if (multi) HIPCHK(h, hipStreamWaitEvent(st, h->ev_e_bnd, 0));
+    double en = 0.0;
+    if (eval_energy(h, st, &en)) return -1;
+    if (multi && allreduce_energy(h, &en, cs)) return -1;
+    return decay_verdict({h}, en, progress, user);
   }
   // joins the streams, reads the timers
   int finish() {
@@ -1075,12 +1090,7 @@ struct Run {
     for (hipEvent_t e : tb_ev) hipEventDestroy(e);
     for (const GraphRec& r : graphs) hipGraphExecDestroy(r.exec);
     HIPCHK(h, hipGetLastError());
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->stats.run_ms = ms;
-    h->stats.steps_done = h->step;
-    h->stats.h_kernel_ms = h->stats.e_kernel_ms = h->stats.fused_kernel_ms = h->stats.shell_kernel_ms = h->stats.seam_kernel_ms = h->seam_flush_ms = 0.0;
-    h->stats.h_kernel_launches = h->stats.e_kernel_launches = h->stats.fused_kernel_launches = h->stats.shell_kernel_launches = h->stats.seam_kernel_launches = 0;
+    if (run_stats({h})) return -1;
     for (size_t i = 0; i < h->kev_kind.size(); ++i) {
       float t = 0.f;
       if (hipEventElapsedTime(&t, h->kev[2 * i], h->kev[2 * i + 1]) != hipSuccess) continue;
