@@ -136,7 +136,8 @@ enum { FDTD_F2_OFF_NONE = 0,
        FDTD_F2_OFF_SHELL = 12,            /* CPML shell too large a part of the grid for shell pairs to pay (cost model, fdtd_capi.hip shell_why_not) */
        FDTD_F2_OFF_MEMORY = 13,           /* no room for the third field set that shell pairs / slab pairs keep the middle step in (+ 50 % field memory) */
        FDTD_F2_OFF_WIDE_TABLE = 14,       /* more than 1023 media (16-bit indices, two words per cell): the single-step sweep reads them, the two-step and shell sweeps do not */
-       FDTD_F2_OFF_MODULATION = 15 };     /* time-modulated media (fdtd_add_modulation): their list kernels run in front of and behind every single step */
+       FDTD_F2_OFF_MODULATION = 15,       /* time-modulated media (fdtd_add_modulation): their list kernels run in front of and behind every single step */
+       FDTD_F2_OFF_CONFORMAL = 16 };      /* PEC-conformal boundaries (fdtd_add_pec_conformal): their list kernel runs in front of every single step */
 
 /* progress callback: (step, time [s], field_decay) -> non-zero aborts the run (Ctrl-C path).
  * Mirrors the (perc_done, field_decay) pair the cloud reports (ref web/core/task_core.py:537). */
@@ -263,6 +264,20 @@ int fdtd_add_aniso_bloch(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_
 int fdtd_add_modulation(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t* cell_index, const float* ca, const float* eps_bar,
                         const float* s_bar, const float* d_eps /* [2 n] */, const float* d_s /* [2 n] */, double omega_eps,
                         double omega_sigma);
+
+/* PEC-conformal boundaries (ref tidy3d components/subpixel_spec.py PECConformal; the Dey-Mittra scheme): n faces of H component
+ * `comp` (3..5) cut by a PEC surface.  In front of the H update of every step the library adds
+ *     H_comp[cell_index[i]] += sum_{k = 0..3} d[k n + i] E_k[nbr_index[k n + i]]        (E^n; summed in the order k = 0..3)
+ * with c = comp - 3, a1 = (c + 1) % 3, a2 = (c + 2) % 3: slots k = 0, 1 read E_a2 (one node up along a1, the face's own index),
+ * k = 2, 3 read E_a1 (one node up along a2, the face's own index); nbr_index 0xFFFFFFFF = no node.  d[k] = -(dt / mu0) s_k
+ * (l_k / A - 1) * inv_step_k with s = (+, -, -, +), l_k the free fraction of the edge, A the (clamped) free fraction of the face and
+ * inv_step_k the float32 inverse PRIMAL step of fdtd_set_steps along a1 (k = 0, 1) / a2 (k = 2, 3): the sweep applies the same sum
+ * with l_k / A = 1.  nbr_index and d are [4][n] (structure of arrays).  Cell indexing as in fdtd_add_aniso; a face is listed at most
+ * once per component.  A handle with such a list takes single steps only (FDTD_F2_OFF_CONFORMAL), no captured graphs, no
+ * slab-interleaved schedule, and is refused on z-slabs (FDTD_BC_NEIGHBOR faces, fdtd_comm_init).  fdtd_reset keeps the lists.
+ * fdtd_run_bloch: give both handles the same lists (the correction is linear with real coefficients). */
+int fdtd_add_pec_conformal(FdtdSolver* h, int comp, int64_t n_faces, const uint32_t* cell_index, const uint32_t* nbr_index,
+                           const float* d);
 
 /* current source: F[comp[p]][index[p]] += w_re[p]*Re(wave[n]) - w_im[p]*Im(wave[n]);
  * E components use wave_e (sampled at t_n + dt/2), H components wave_h (t_n);

@@ -23,6 +23,7 @@
 #include "fdtd_shell2_host.hpp"
 #include "fdtd_aniso.hpp"
 #include "fdtd_modulation.hpp"
+#include "fdtd_conformal.hpp"
 #include "fdtd_near_field.hpp"
 #include "fdtd_flux_time.hpp"
 #include "fdtd_field_time.hpp"
@@ -101,6 +102,14 @@ struct ModGroup {                   // fdtd_modulation.hpp: the nodes of E compo
   float *ca, *eps_bar, *s_bar, *old;
   float2 *d_eps, *d_s;
   double w_eps, w_sig;              // phase advance per time step (rad) of the permittivity / conductivity modulation
+};
+
+struct ConformalGroup {            // fdtd_conformal.hpp: the faces of H component `comp` cut by a PEC surface, structure of arrays
+  int comp;                         // 3..5
+  long long n;
+  uint32_t* cell;                   // [n]
+  uint32_t* nbr;                    // [4][n] edge nodes, kNoNode = none
+  float* d;                         // [4][n]
 };
 
 struct PointSrc {
@@ -253,6 +262,7 @@ struct FdtdSolver {
   int disp_on = -1;                  // FDTD_OPT_DISP: dispersive cells inside the two-step sweeps: -1 = default (on), 0 = off (their planes as z holes, round 5)
   std::vector<AnisoGroup> aniso;
   std::vector<ModGroup> modulation;
+  std::vector<ConformalGroup> conformal;
   std::vector<PointSrc> psrc;
   std::vector<Tfsf> tfsf;
   std::vector<Monitor> mons;
@@ -1014,6 +1024,7 @@ int fused2_why_not(const FdtdSolver* h, bool slab_rank = false, bool shell = fal
   if (!h->ade.empty() && !shell && h->disp.state != 1) return FDTD_F2_OFF_ADE;
   if (!h->aniso.empty()) return FDTD_F2_OFF_ADE;               // fully anisotropic bodies: their coupling follows every single step
   if (!h->modulation.empty()) return FDTD_F2_OFF_MODULATION;   // time-modulated media: their list kernels follow every single step
+  if (!h->conformal.empty()) return FDTD_F2_OFF_CONFORMAL;     // PEC-conformal boundaries: their list kernel runs in front of every single step
   // (sources are judged step by step, fused2_sources_why_not: a TFSF box or a mode plane keeps single steps only while it injects)
   // PEC walls; the min faces may be PMC (the symmetry planes of a half / quarter / eighth domain)
   // (a z-slab rank: a neighbour face is no wall — the sweep stays two planes clear of it, fdtd_run)
@@ -2542,6 +2553,17 @@ void modulation_apply(FdtdSolver* h, long long n, hipStream_t st) {
   }
 }
 
+// PEC-conformal boundaries: H of the cut faces gains what the conformal weights add to the sweep's own curl term (E^n alone)
+void conformal_apply(FdtdSolver* h, hipStream_t st) {
+  if (h->conformal.empty()) return;
+  dbg_sync(h);
+  for (ConformalGroup& c : h->conformal) {
+    const int a = c.comp - 3;
+    hipLaunchKernelGGL(conformal_h_kernel, dim3(nblk(c.n)), dim3(256), 0, st, field_ptr(h, c.comp), (const float*)field_ptr(h, (a + 2) % 3),
+                       (const float*)field_ptr(h, (a + 1) % 3), (const uint32_t*)c.cell, (const uint32_t*)c.nbr, (const float*)c.d, c.n);
+  }
+}
+
 void launch_ade(FdtdSolver* h, int kbeg, int kend, hipStream_t st, const FieldP* fs = nullptr) {
   dbg_sync(h);
   if (kend <= kbeg) return;
@@ -2570,11 +2592,15 @@ void launch_ade(FdtdSolver* h, int kbeg, int kend, hipStream_t st, const FieldP*
 // incident grids.  What stays with the caller, because its place differs between the schedules: fill_mirror, aniso_save /
 // modulation_save, advance_tfsf_aux, the ghost fills, record_monitors.
 // H side, in FRONT of the update of step n, planes [k0, k1): absorber damping of H^{n-1/2}, then H-side sources / TFSF corrections
-// (they only read E^n), then the CPML slabs — the summation order of the fused sweep
+// (they only read E^n), then the CPML slabs — the summation order of the fused sweep — then the PEC-conformal correction of the cut
+// faces (it reads E^n alone as well).  The conformal lists are whole-grid lists like the anisotropic and modulation ones: they are
+// applied only by a call that covers every plane (Run::fused_one, the H pass of Run::two_pass_step on one GPU, BlochRun::step); the
+// schedules that work on plane ranges refuse them (Run::setup, Run::setup_schedules, BlochRun::setup).
 void h_side_terms(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, int axes = 7, bool replica = false) {
   launch_damp(h, false, k0, k1, st);
   launch_sources(h, false, n, k0, k1, st, replica);
   launch_pml(h, false, k0, k1, st, axes);
+  if (k0 == 0 && k1 == h->g.nz) conformal_apply(h, st);
 }
 // E side, BEHIND the update of step n.  Head: the CPML slabs, then the E-side sources / TFSF corrections ...
 void e_side_head(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, int axes = 7, bool replica = false) {
@@ -3552,6 +3578,32 @@ int fdtd_add_modulation(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell
   return 0;
 }
 
+int fdtd_add_pec_conformal(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index, const uint32_t* nbr_index, const float* d) {
+  if (!h) return -1;
+  if (comp < 3 || comp > 5) return fail(h, "fdtd_add_pec_conformal: comp must be 3..5");
+  if (n <= 0) return 0;
+  if (h->comm) return fail(h, "fdtd_add_pec_conformal: PEC-conformal boundaries are not available on z-slabs");
+  for (int f = 4; f < 6; ++f)
+    if (h->cfg.bc[f] == FDTD_BC_NEIGHBOR) return fail(h, "fdtd_add_pec_conformal: PEC-conformal boundaries are not available on z-slabs");
+  for (const ConformalGroup& c : h->conformal)
+    if (c.comp == comp) return fail(h, "fdtd_add_pec_conformal: component %d has a list already (a face is listed once)", comp);
+  const uint64_t ncell = (uint64_t)n_cells(h);
+  for (int64_t i = 0; i < n; ++i)
+    if (cell_index[i] >= ncell) return fail(h, "fdtd_add_pec_conformal: cell index out of range");
+  for (int64_t q = 0; q < 4 * n; ++q) {
+    if (nbr_index[q] != kNoNode && nbr_index[q] >= ncell) return fail(h, "fdtd_add_pec_conformal: neighbour index out of range");
+    if (!std::isfinite(d[q])) return fail(h, "fdtd_add_pec_conformal: weight %lld is not finite", (long long)q);
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  ConformalGroup c{};
+  c.comp = comp; c.n = n;
+  if (dev_upload(h, &c.cell, cell_index, (size_t)n) || dev_upload(h, &c.nbr, nbr_index, (size_t)(4 * n)) ||
+      dev_upload(h, &c.d, d, (size_t)(4 * n)))
+    return -1;
+  h->conformal.push_back(c);
+  return 0;
+}
+
 int fdtd_add_point_source(FdtdSolver* h, int64_t n, const int32_t* comp, const uint32_t* cell, const float* w_re,
                           const float* w_im, int64_t n_steps, const float* wave_e, const float* wave_h) {
   if (!h) return -1;
@@ -3990,6 +4042,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   std::memcpy(&u, id, 128);
   if (refuse_whole_grid_monitors(h, h, "fdtd_comm_init")) return -1;
   if (!h->modulation.empty()) return fail(h, "fdtd_comm_init: time-modulated media are not available on z-slabs");
+  if (!h->conformal.empty()) return fail(h, "fdtd_comm_init: PEC-conformal boundaries are not available on z-slabs");
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)

@@ -56,6 +56,9 @@ struct BlochRun {
     // time-modulated media: the update is linear with real coefficients — each part is patched by its own handle's lists, the same rows
     if (!same_lists(hr->modulation, hi->modulation)) return fail(hr, "fdtd_run_bloch: the two solvers must carry the same time-modulation lists");
     if (multi && !hr->modulation.empty()) return fail(hr, "fdtd_run_bloch: time-modulated media are not available on z-slabs");
+    // PEC-conformal boundaries: linear with real coefficients as well — each handle corrects its own part (h_side_terms)
+    if (!same_lists(hr->conformal, hi->conformal)) return fail(hr, "fdtd_run_bloch: the two solvers must carry the same PEC-conformal lists");
+    if (multi && !hr->conformal.empty()) return fail(hr, "fdtd_run_bloch: PEC-conformal boundaries are not available on z-slabs");
     if (hi->cfg.bc[4] != hr->cfg.bc[4] || hi->cfg.bc[5] != hr->cfg.bc[5])
       return fail(hr, "fdtd_run_bloch: the two solvers must have the same z faces");
     if (hr->g.nx != hi->g.nx || hr->g.ny != hi->g.ny || hr->g.nz != hi->g.nz || hr->cfg.device != hi->cfg.device ||

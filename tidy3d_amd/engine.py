@@ -234,9 +234,14 @@ def permute_spec(spec: SolverSpec, s: int) -> SolverSpec:
                 for m in monitors]
     # sparse field-time and sparse DFT monitors: every component's per-axis tables (hence its kept-node counts) are renamed with the axes
     monitors = [m if m.kind not in SPARSE_KINDS else dataclasses.replace(m, taps=tuple(pick(t) for t in m.taps)) for m in monitors]
+    # PEC-conformal lists: faces, edges and components are renamed with the axes; a cyclic renaming keeps the slot order (a1, a2 follow c)
+    conformal = [dataclasses.replace(cs, comp=int(comp_map(cs.comp)), ijk=np.ascontiguousarray(cs.ijk[:, sig]),
+                                     nbr_comp=tuple(int(v) for v in comp_map(cs.nbr_comp)),
+                                     nbr_ijk=np.ascontiguousarray(cs.nbr_ijk[:, :, sig]))
+                 for cs in (getattr(spec, "conformal", None) or [])]
     return dataclasses.replace(
         spec, shape=pick(spec.shape), boundaries=pick(spec.boundaries), bc=pick(spec.bc), pml=pick(spec.pml),
-        mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors,
+        mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors, conformal=conformal,
         absorber=None if spec.absorber is None else list(pick(spec.absorber)),
         bloch=None if spec.bloch is None else pick(spec.bloch),
         mirror_plus=None if getattr(spec, "mirror_plus", None) is None else pick(spec.mirror_plus))
@@ -636,6 +641,25 @@ class HipEngine:
                 self._chk(d.fdtd_add_modulation(h, int(ms.comp), n, _ptr(cells), *[_ptr(a) for a in arrs],
                                                 2.0 * np.pi * float(ms.freq_eps) * spec.dt, 2.0 * np.pi * float(ms.freq_sigma) * spec.dt),
                           "fdtd_add_modulation")
+        # PEC-conformal boundaries (spec.ConformalSet): the cut faces per H component, edges and weights as [4][n]
+        conformal = getattr(spec, "conformal", None) or []
+        if conformal:
+            from .exceptions import Tidy3dNotImplementedError
+            if self.n_ranks > 1 or self.force_comm or (z0, z1) != (0, nz):
+                raise Tidy3dNotImplementedError("PECConformal is not available in z-slab (multi-GPU) runs")
+            if spec.bloch is not None:
+                raise Tidy3dNotImplementedError("PECConformal together with Bloch boundaries is not supported")
+            for cs in conformal:
+                n = len(cs.ijk)
+                if n == 0:
+                    continue
+                ijk = np.asarray(cs.ijk, np.int64)
+                cells = np.ascontiguousarray((ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32))
+                j = np.asarray(cs.nbr_ijk, np.int64)
+                nbr = np.where(j[:, :, 0] >= 0, j[:, :, 2] * sxy + j[:, :, 1] * nx + j[:, :, 0], 0xFFFFFFFF).astype(np.uint32)
+                nbr32, d32 = np.ascontiguousarray(nbr.T), _f32(np.asarray(cs.d).T)
+                self._chk(d.fdtd_add_pec_conformal(h, int(cs.comp), n, _ptr(cells), _ptr(nbr32), _ptr(d32)), "fdtd_add_pec_conformal")
+            self.n_conformal_faces = sum(len(cs.ijk) for cs in conformal)
         # sources
         from .spec import BC_PEC
         for s in spec.sources:

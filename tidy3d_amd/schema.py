@@ -2637,11 +2637,37 @@ class Staircasing(_Model):
 
 @_register
 @dataclass
+class PECConformal(_Model):
+    """ref components/subpixel_spec.py PECConformal: conformal treatment of PEC surfaces at a time step reduced by
+    ``timestep_reduction``.  The reference's algorithm is server-side; here it is the published scheme the name refers to, the
+    Dey-Mittra conformal H update with a local area clamp (tidy3d_amd/conformal.py, docs/history/PEC_CONFORMAL.md) — parity
+    unpinned, pinned physically (tests/test_emu_pec_conformal.py)."""
+
+    timestep_reduction: float = 0.3
+
+    def __post_init__(self):
+        self.timestep_reduction = float(self.timestep_reduction)
+        if not (0.0 <= self.timestep_reduction < 1.0):
+            raise ValidationError("PECConformal.timestep_reduction must be in [0, 1).")
+
+    @property
+    def courant_ratio(self) -> float:
+        return 1.0 - self.timestep_reduction
+
+
+@_register
+@dataclass
 class SubpixelSpec(_Model):
     """ref components/subpixel_spec.py:117.  ``dielectric``: PolarizedAveraging (default) /
     VolumetricAveraging / Staircasing are honoured by the rasteriser (discretize._subpixel_average —
-    the published methods; the reference's own code is server-side); ``metal`` / ``pec`` interfaces
-    are staircased; ``courant_ratio`` follows :148."""
+    the published methods; the reference's own code is server-side); ``pec``: a ``PECConformal`` turns the
+    Dey-Mittra conformal scheme on wherever the simulation holds a PEC medium (tidy3d_amd/conformal.py; the time
+    step shrinks by its ``timestep_reduction``), anything else (``None``, ``Staircasing``, ``HeuristicPECStaircasing``)
+    staircases PEC surfaces; ``metal`` interfaces are staircased; ``courant_ratio`` follows :148.
+
+    Deviation from the reference: there ``Simulation.subpixel = True`` means ``SubpixelSpec()`` whose ``pec`` is a
+    ``PECConformal``.  Here ``True`` and the mirror's ``SubpixelSpec()`` (``pec`` = None) keep the PEC staircase (``True`` also keeps
+    the reduced time step it always had): the conformal scheme is on only where a ``SubpixelSpec`` names ``PECConformal``."""
 
     dielectric: Any = None
     metal: Any = None

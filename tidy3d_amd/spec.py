@@ -80,6 +80,29 @@ class ModulationSet:
 
 
 @dataclass
+class ConformalSet:
+    """The faces of one H component cut by a PEC surface under the Dey-Mittra conformal scheme (SubpixelSpec.pec = PECConformal;
+    tidy3d_amd/conformal.py, docs/history/PEC_CONFORMAL.md).  A cut face is advanced with
+
+        H_c^{n+1/2} = H_c^{n-1/2} - (dt / mu0) / (A S) sum_k s_k l_k L_k E_k^n,      k = its four edges
+
+    (l_k the free fraction of edge k, A the free fraction of the face's area, enlarged to ``area_eff`` for stability).  The sweep
+    applies the same sum with l_k / A = 1, so the solver adds, in front of the sweep,  H_c += sum_k d[k] E_k^n  with
+    d[k] = -(dt / mu0) s_k (l_k / area_eff - 1) / step_k (csrc/fdtd_conformal.hpp).  Slots: c = comp - 3, a1 = (c + 1) % 3,
+    a2 = (c + 2) % 3;  k = 0: E_a2 one node up along a1 (s = +1), 1: E_a2 at the face's own index (-1), 2: E_a1 one node up along
+    a2 (-1), 3: E_a1 at the face's own index (+1); step_k the primal step along a1 (k = 0, 1) or a2 (k = 2, 3)."""
+
+    comp: int                         # H component, 3..5
+    ijk: np.ndarray                   # [n, 3] faces (i, j, k), each at most once
+    nbr_comp: Tuple[int, ...]         # [4] E component of every slot
+    nbr_ijk: np.ndarray               # [n, 4, 3]; -1 = no node (a PEC edge, or beyond a non-periodic wall): E is zero there
+    d: np.ndarray                     # [n, 4] float32
+    l: np.ndarray                     # [n, 4] float64 free fractions of the four edges
+    area: np.ndarray                  # [n] float64 free fraction of the face (a straight cut through the edge crossings)
+    area_eff: np.ndarray              # [n] float64 what the weights divide by: max(area, clamp * max_k l_k)
+
+
+@dataclass
 class PmlFace:
     """CPML profile of one face (ref boundary.py:195-254; units of sigma/alpha: 2 eps0/dt)."""
 
@@ -243,6 +266,7 @@ class SolverSpec:
     mirror_plus: Optional[Tuple[int, int, int]] = None
     aniso: List[AnisoSet] = field(default_factory=list)   # fully anisotropic bodies: off-diagonal coupling per E component
     modulation: List[ModulationSet] = field(default_factory=list)   # time-modulated media: their nodes per E component and medium
+    conformal: List[ConformalSet] = field(default_factory=list)     # PEC-conformal boundaries: the cut faces per H component
     shutoff: float = 0.0                                # 0 disables the early stop
     decay_every: int = 0                                # 0 = never evaluate field decay
     decay_ref_step: int = 0                             # steps before this never shut off

@@ -134,6 +134,10 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         if any(isinstance(m, td.Medium) and m.is_time_modulated for m in sim.mediums):
             raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media together with devices= with more than one GPU are "
                                             "not supported")
+        from .conformal import pec_conformal_of
+        if pec_conformal_of(sim) is not None:
+            raise Tidy3dNotImplementedError("PECConformal together with devices= with more than one GPU is not supported "
+                                            "(SubpixelSpec(pec=Staircasing()) is)")
         sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose,
                                    dict(_dist_options or {}, exact_projection_device=exact_projection_device))
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
@@ -157,6 +161,9 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
              f"Number of time steps: {spec.n_steps:.4e}",
              f"Time step size (dt): {spec.dt:.4e}s", "",
              "Running solver for %d time steps..." % spec.n_steps]
+    if spec.conformal:
+        lines.insert(-2, "PEC-conformal boundaries (Dey-Mittra): %d cut faces listed; single time steps."
+                     % sum(len(cs.ijk) for cs in spec.conformal))
 
     def progress(step, t, decay):
         ln = _log_line(step, spec.n_steps, t, decay)
