@@ -137,7 +137,8 @@ enum { FDTD_F2_OFF_NONE = 0,
        FDTD_F2_OFF_MEMORY = 13,           /* no room for the third field set that shell pairs / slab pairs keep the middle step in (+ 50 % field memory) */
        FDTD_F2_OFF_WIDE_TABLE = 14,       /* more than 1023 media (16-bit indices, two words per cell): the single-step sweep reads them, the two-step and shell sweeps do not */
        FDTD_F2_OFF_MODULATION = 15,       /* time-modulated media (fdtd_add_modulation): their list kernels run in front of and behind every single step */
-       FDTD_F2_OFF_CONFORMAL = 16 };      /* PEC-conformal boundaries (fdtd_add_pec_conformal): their list kernel runs in front of every single step */
+       FDTD_F2_OFF_CONFORMAL = 16,        /* PEC-conformal boundaries (fdtd_add_pec_conformal): their list kernel runs in front of every single step */
+       FDTD_F2_OFF_NONLINEAR = 17 };      /* Kerr media (fdtd_add_nonlinear): their fixed-point iterations follow every single step */
 
 /* progress callback: (step, time [s], field_decay) -> non-zero aborts the run (Ctrl-C path).
  * Mirrors the (perc_done, field_decay) pair the cloud reports (ref web/core/task_core.py:537). */
@@ -278,6 +279,27 @@ int fdtd_add_modulation(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t
  * fdtd_run_bloch: give both handles the same lists (the correction is linear with real coefficients). */
 int fdtd_add_pec_conformal(FdtdSolver* h, int comp, int64_t n_faces, const uint32_t* cell_index, const uint32_t* nbr_index,
                            const float* d);
+
+/* Kerr media (ref tidy3d components/medium.py NonlinearSpec / NonlinearSusceptibility): n nodes of E component `comp` with the
+ * instantaneous third-order response D = eps0 (eps_bar + chi3 I) E, I = |E|^2 at the node:
+ *     I = E_a^2 + (mean of the four surrounding E_b nodes)^2 + (mean of the four surrounding E_c nodes)^2,   b = a + 1, c = a + 2 (cyclic)
+ * nbr_index is [8][n] (structure of arrays): slots 0..3 the E_b nodes, 4..7 the E_c nodes, in the order of fdtd_add_aniso's slots;
+ * 0xFFFFFFFF = no node (beyond a PEC / PMC wall): it contributes 0 to its mean of four.  The sweep advances these nodes with their
+ * static table medium, E_lin = Ca E^n + Cb K; at the end of the E phase the library solves
+ *     (D^{n+1} - D^n) / dt + sigma (E^{n+1} + E^n) / 2 = K
+ * by num_iters Jacobi fixed-point iterations, E^(0) = E_lin,
+ *     E^(m) = alpha_m E^n + beta_m (E_lin - ca E^n),   alpha_m = (eps_bar + chi3 I^n - s_bar) / (eps_bar + chi3 I^(m-1) + s_bar),
+ *                                                      beta_m  = (eps_bar + s_bar) / (eps_bar + chi3 I^(m-1) + s_bar)
+ * where I^(m-1) is formed from the fields as iteration m - 1 left them, every listed node of all three components before any is
+ * overwritten.  ca, eps_bar, s_bar: the node's own table coefficient and the host's eps_bar, s_bar of fdtd_add_modulation; ca must be
+ * (eps_bar - s_bar) / (eps_bar + s_bar) to 1e-5 (the library evaluates the iterate as E_lin + chi3 (I^n E^n - I^(m-1) E_lin) /
+ * (eps_bar + s_bar + chi3 I^(m-1)), which is the same number and the table update, bit for bit, where chi3 = 0).  Cell indexing as
+ * in fdtd_add_aniso; one list per component, a node at most once in it; 1 <= num_iters <= 64, the same for all lists of a handle.
+ * A handle with such a list takes single steps only (FDTD_F2_OFF_NONLINEAR), no captured graphs, no slab-interleaved schedule, no
+ * paged ADE memory terms, and is refused on z-slabs (FDTD_BC_NEIGHBOR faces, fdtd_comm_init), by fdtd_run_bloch (the update is not
+ * linear: the two parts cannot be patched separately) and together with fdtd_add_modulation lists.  fdtd_reset keeps the lists. */
+int fdtd_add_nonlinear(FdtdSolver* h, int comp, int64_t n_nodes, const uint32_t* cell_index, const uint32_t* nbr_index /* [8][n] */,
+                       const float* ca, const float* eps_bar, const float* s_bar, const float* chi3, int num_iters);
 
 /* current source: F[comp[p]][index[p]] += w_re[p]*Re(wave[n]) - w_im[p]*Im(wave[n]);
  * E components use wave_e (sampled at t_n + dt/2), H components wave_h (t_n);

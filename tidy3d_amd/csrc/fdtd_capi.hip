@@ -24,6 +24,7 @@
 #include "fdtd_aniso.hpp"
 #include "fdtd_modulation.hpp"
 #include "fdtd_conformal.hpp"
+#include "fdtd_nonlinear.hpp"
 #include "fdtd_near_field.hpp"
 #include "fdtd_flux_time.hpp"
 #include "fdtd_field_time.hpp"
@@ -110,6 +111,15 @@ struct ConformalGroup {            // fdtd_conformal.hpp: the faces of H compone
   uint32_t* cell;                   // [n]
   uint32_t* nbr;                    // [4][n] edge nodes, kNoNode = none
   float* d;                         // [4][n]
+};
+
+struct NonlinearGroup {            // fdtd_nonlinear.hpp: the nodes of E component `comp` inside Kerr media, structure of arrays
+  int comp;
+  long long n;
+  uint32_t* cell;                   // [n]
+  uint32_t* nbr;                    // [8][n] the four E_b and the four E_c nodes around each node, kNoNode = none
+  float *den0, *chi3;               // [n] eps_bar + s_bar, chi3
+  float *old, *i_old, *lin, *next;  // [n] E^n, I^n, E_lin, the iterate being formed
 };
 
 struct PointSrc {
@@ -263,6 +273,8 @@ struct FdtdSolver {
   std::vector<AnisoGroup> aniso;
   std::vector<ModGroup> modulation;
   std::vector<ConformalGroup> conformal;
+  std::vector<NonlinearGroup> nonlinear;   // at most one list per E component
+  int nonlinear_iters = 0;           // fixed-point iterations per step, the same for every list of the handle
   std::vector<PointSrc> psrc;
   std::vector<Tfsf> tfsf;
   std::vector<Monitor> mons;
@@ -1025,6 +1037,7 @@ int fused2_why_not(const FdtdSolver* h, bool slab_rank = false, bool shell = fal
   if (!h->aniso.empty()) return FDTD_F2_OFF_ADE;               // fully anisotropic bodies: their coupling follows every single step
   if (!h->modulation.empty()) return FDTD_F2_OFF_MODULATION;   // time-modulated media: their list kernels follow every single step
   if (!h->conformal.empty()) return FDTD_F2_OFF_CONFORMAL;     // PEC-conformal boundaries: their list kernel runs in front of every single step
+  if (!h->nonlinear.empty()) return FDTD_F2_OFF_NONLINEAR;     // Kerr media: their fixed-point iterations follow every single step
   // (sources are judged step by step, fused2_sources_why_not: a TFSF box or a mode plane keeps single steps only while it injects)
   // PEC walls; the min faces may be PMC (the symmetry planes of a half / quarter / eighth domain)
   // (a z-slab rank: a neighbour face is no wall — the sweep stays two planes clear of it, fdtd_run)
@@ -2553,6 +2566,39 @@ void modulation_apply(FdtdSolver* h, long long n, hipStream_t st) {
   }
 }
 
+// Kerr media: E^n and I^n of the listed nodes, saved in front of the E update ...
+NonlinearP nonlinear_args(FdtdSolver* h, long long* n_max) {
+  NonlinearP p{};
+  *n_max = 0;
+  for (int c = 0; c < 3; ++c) p.e[c] = field_ptr(h, c);
+  for (const NonlinearGroup& g : h->nonlinear) {
+    p.l[g.comp] = NonlinearList{g.cell, g.nbr, g.den0, g.chi3, g.old, g.i_old, g.lin, g.next, g.n};
+    *n_max = std::max(*n_max, g.n);
+  }
+  return p;
+}
+void nonlinear_save(FdtdSolver* h, hipStream_t st) {
+  if (h->nonlinear.empty()) return;
+  dbg_sync(h);
+  long long n_max;
+  const NonlinearP p = nonlinear_args(h, &n_max);
+  hipLaunchKernelGGL(nonlinear_save_kernel, dim3(nblk(n_max), 3), dim3(256), 0, st, p);
+}
+// ... and the fixed-point iterations at the END of the E phase (behind CPML, sources, damping and ADE; in front of the ghost fills):
+// per iteration every listed node of all three components is computed from the fields as the last iteration left them, then all
+// are stored (Jacobi: no dependence on list or launch order)
+void nonlinear_apply(FdtdSolver* h, hipStream_t st) {
+  if (h->nonlinear.empty()) return;
+  dbg_sync(h);
+  long long n_max;
+  const NonlinearP p = nonlinear_args(h, &n_max);
+  const dim3 grid(nblk(n_max), 3);
+  for (int m = 0; m < h->nonlinear_iters; ++m) {
+    hipLaunchKernelGGL(nonlinear_iter_kernel, grid, dim3(256), 0, st, p, m == 0 ? 1 : 0);
+    hipLaunchKernelGGL(nonlinear_scatter_kernel, grid, dim3(256), 0, st, p);
+  }
+}
+
 // PEC-conformal boundaries: H of the cut faces gains what the conformal weights add to the sweep's own curl term (E^n alone)
 void conformal_apply(FdtdSolver* h, hipStream_t st) {
   if (h->conformal.empty()) return;
@@ -2590,7 +2636,7 @@ void launch_ade(FdtdSolver* h, int kbeg, int kend, hipStream_t st, const FieldP*
 // when its list or layer count is empty, so a schedule that cannot carry a term (tb_pair: no CPML) launches nothing for it.
 // `axes`: the CPML axes that run as slab kernels (7 & ~ the axes inside the sweep); `replica`: the comm stream's copy of the TFSF
 // incident grids.  What stays with the caller, because its place differs between the schedules: fill_mirror, aniso_save /
-// modulation_save, advance_tfsf_aux, the ghost fills, record_monitors.
+// modulation_save / nonlinear_save, advance_tfsf_aux, the ghost fills, record_monitors.
 // H side, in FRONT of the update of step n, planes [k0, k1): absorber damping of H^{n-1/2}, then H-side sources / TFSF corrections
 // (they only read E^n), then the CPML slabs — the summation order of the fused sweep — then the PEC-conformal correction of the cut
 // faces (it reads E^n alone as well).  The conformal lists are whole-grid lists like the anisotropic and modulation ones: they are
@@ -2608,7 +2654,8 @@ void e_side_head(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, int
   launch_sources(h, true, n, k0, k1, st, replica);
 }
 // ... tail: absorber damping, then the ADE pass (its stored E^{n+1} is the damped one), then the time-modulation patch (the end of
-// the E phase: E_lin of the listed nodes is complete).  Between the two, the fully anisotropic coupling: aniso_apply, or
+// the E phase: E_lin of the listed nodes is complete), then the Kerr media's fixed-point iterations (they read E_lin of all three
+// components; a handle carries either kind of list, not both).  Between the two, the fully anisotropic coupling: aniso_apply, or
 // aniso_apply_bloch where it reads both parts of a Bloch pair (BlochRun::step cuts in there).
 // `whole_grid`: the call covers every plane of the grid.  The anisotropic and modulation lists are whole-grid lists, not plane-ranged:
 // they are applied only then.  A caller that works on a plane range (tb_pair's slabs, the cs / st halves of a z-slab rank) passes
@@ -2617,6 +2664,7 @@ void e_side_tail(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, boo
   launch_damp(h, true, k0, k1, st);
   launch_ade(h, k0, k1, st);
   if (whole_grid) modulation_apply(h, n, st);
+  if (whole_grid) nonlinear_apply(h, st);
 }
 void e_side_terms(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, bool whole_grid, int axes = 7, bool replica = false) {
   e_side_head(h, n, k0, k1, st, axes, replica);
@@ -2645,7 +2693,7 @@ int disp_setup(FdtdSolver* h) {
   if (D.state != 0) return 0;
   D.state = -1;
   const GridP& g = h->g;
-  if (h->ade.empty() || h->disp_on == 0 || !h->mat4 || h->mat4b || h->comm || !h->aniso.empty() || !h->modulation.empty() || g.nx % 4 != 0) return 0;
+  if (h->ade.empty() || h->disp_on == 0 || !h->mat4 || h->mat4b || h->comm || !h->aniso.empty() || !h->modulation.empty() || !h->nonlinear.empty() || g.nx % 4 != 0) return 0;
   for (const AdeGroup& a : h->ade) if (!a.strict) return 0;
   const int nbx = (g.nx + 255) / 256;
   const size_t nseg = (size_t)g.nz * g.ny * nbx;
@@ -3555,6 +3603,7 @@ int fdtd_add_modulation(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell
   if (h->comm) return fail(h, "fdtd_add_modulation: time-modulated media are not available on z-slabs");
   for (int f = 4; f < 6; ++f)
     if (h->cfg.bc[f] == FDTD_BC_NEIGHBOR) return fail(h, "fdtd_add_modulation: time-modulated media are not available on z-slabs");
+  if (!h->nonlinear.empty()) return fail(h, "fdtd_add_modulation: time-modulated media are not available together with nonlinear media");
   if (!std::isfinite(omega_eps) || !std::isfinite(omega_sigma)) return fail(h, "fdtd_add_modulation: omega must be finite");
   const uint64_t ncell = (uint64_t)n_cells(h);
   for (int64_t i = 0; i < n; ++i) {
@@ -3601,6 +3650,47 @@ int fdtd_add_pec_conformal(FdtdSolver* h, int comp, int64_t n, const uint32_t* c
       dev_upload(h, &c.d, d, (size_t)(4 * n)))
     return -1;
   h->conformal.push_back(c);
+  return 0;
+}
+
+int fdtd_add_nonlinear(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index, const uint32_t* nbr_index, const float* ca,
+                       const float* eps_bar, const float* s_bar, const float* chi3, int num_iters) {
+  if (!h) return -1;
+  if (comp < 0 || comp > 2) return fail(h, "fdtd_add_nonlinear: comp must be 0..2");
+  if (num_iters < 1 || num_iters > 64) return fail(h, "fdtd_add_nonlinear: num_iters must be 1..64");
+  if (n <= 0) return 0;
+  if (h->comm) return fail(h, "fdtd_add_nonlinear: nonlinear media are not available on z-slabs");
+  for (int f = 4; f < 6; ++f)
+    if (h->cfg.bc[f] == FDTD_BC_NEIGHBOR) return fail(h, "fdtd_add_nonlinear: nonlinear media are not available on z-slabs");
+  if (!h->modulation.empty()) return fail(h, "fdtd_add_nonlinear: nonlinear media are not available together with time-modulated media");
+  for (const NonlinearGroup& g : h->nonlinear)
+    if (g.comp == comp) return fail(h, "fdtd_add_nonlinear: component %d has a list already (a node is listed once)", comp);
+  if (!h->nonlinear.empty() && h->nonlinear_iters != num_iters)
+    return fail(h, "fdtd_add_nonlinear: num_iters = %d, the handle's lists have %d (one value per handle)", num_iters, h->nonlinear_iters);
+  const uint64_t ncell = (uint64_t)n_cells(h);
+  std::vector<float> den0((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    if (cell_index[i] >= ncell) return fail(h, "fdtd_add_nonlinear: cell index out of range");
+    if (!std::isfinite(chi3[i])) return fail(h, "fdtd_add_nonlinear: node %lld: chi3 is not finite", (long long)i);
+    den0[(size_t)i] = eps_bar[i] + s_bar[i];
+    if (!(den0[(size_t)i] > 0.0f)) return fail(h, "fdtd_add_nonlinear: node %lld: eps_bar + s_bar = %g is not positive", (long long)i, (double)den0[(size_t)i]);
+    // (the kernel's form of the iterate rests on Ca = (eps_bar - s_bar) / (eps_bar + s_bar): the three must be one table entry's)
+    const double ca_of = ((double)eps_bar[i] - (double)s_bar[i]) / ((double)eps_bar[i] + (double)s_bar[i]);
+    if (!(std::fabs(ca_of - (double)ca[i]) <= 1e-5))
+      return fail(h, "fdtd_add_nonlinear: node %lld: ca = %g is not (eps_bar - s_bar) / (eps_bar + s_bar) = %g", (long long)i, (double)ca[i], ca_of);
+  }
+  for (int64_t q = 0; q < 8 * n; ++q)
+    if (nbr_index[q] != kNoNode && nbr_index[q] >= ncell) return fail(h, "fdtd_add_nonlinear: neighbour index out of range");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  NonlinearGroup g{};
+  g.comp = comp; g.n = n;
+  if (dev_upload(h, &g.cell, cell_index, (size_t)n) || dev_upload(h, &g.nbr, nbr_index, (size_t)(8 * n)) ||
+      dev_upload(h, &g.den0, (const float*)den0.data(), (size_t)n) || dev_upload(h, &g.chi3, chi3, (size_t)n) ||
+      dev_alloc(h, &g.old, (size_t)n) || dev_alloc(h, &g.i_old, (size_t)n) || dev_alloc(h, &g.lin, (size_t)n) ||
+      dev_alloc(h, &g.next, (size_t)n))
+    return -1;
+  h->nonlinear.push_back(g);
+  h->nonlinear_iters = num_iters;
   return 0;
 }
 
@@ -4043,6 +4133,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   if (refuse_whole_grid_monitors(h, h, "fdtd_comm_init")) return -1;
   if (!h->modulation.empty()) return fail(h, "fdtd_comm_init: time-modulated media are not available on z-slabs");
   if (!h->conformal.empty()) return fail(h, "fdtd_comm_init: PEC-conformal boundaries are not available on z-slabs");
+  if (!h->nonlinear.empty()) return fail(h, "fdtd_comm_init: nonlinear media are not available on z-slabs");
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)

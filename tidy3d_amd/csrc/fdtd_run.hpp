@@ -195,6 +195,7 @@ struct Run {
     if (multi && !h->aniso.empty()) return fail(h, "fdtd_run: fully anisotropic media are not available on z-slabs");
     if (multi && !h->modulation.empty()) return fail(h, "fdtd_run: time-modulated media are not available on z-slabs");
     if (multi && !h->conformal.empty()) return fail(h, "fdtd_run: PEC-conformal boundaries are not available on z-slabs");
+    if (multi && !h->nonlinear.empty()) return fail(h, "fdtd_run: nonlinear media are not available on z-slabs");
     // (PMC on a plus face of a z-slab rank: x / y walls are local to every plane; a z wall belongs to the rank without an upper
     //  neighbour, whose interior launch must hold the wall's two image planes and the two they mirror)
     // (six planes: the boundary chunk next to the lower neighbour is one plane thick below eight planes, two from there on)
@@ -327,7 +328,7 @@ struct Run {
     //  here; and no CPML: the launch_pml inside h_side_terms / e_side_terms launches nothing on this schedule)
     tb_ok = fused && tb_req > 0 && !any_pml(h) && h->tfsf.empty() && h->cfg.bc[4] != FDTD_BC_PERIODIC &&
                        h->mirror_wall[0] < 0 && h->mirror_wall[1] < 0 && h->mirror_wall[2] < 0 && h->aniso.empty() &&
-                       h->modulation.empty() && h->conformal.empty() && nz >= 2 * tb_req;
+                       h->modulation.empty() && h->conformal.empty() && h->nonlinear.empty() && nz >= 2 * tb_req;
     h->two_step_pairs = 0;
     h->tblock_used = tb_ok ? tb_req : 0;
     // ---- captured step pairs (hipGraph) ------------------------------------------------------------------------------
@@ -341,6 +342,7 @@ struct Run {
                            (((h->pml_fused < 0 ? 7 : h->pml_fused) & pml_in_sweep_mask(h)) & 6) != 0;
     graph_ok = fused && !tb_ok && !split_now && !(h->cfg.flags & FDTD_FLAG_TIME_KERNELS) && h->aniso.empty() &&
                     h->conformal.empty() &&       // (conformal lists: single steps only, as the modulation lists)
+                    h->nonlinear.empty() &&       // (Kerr lists likewise)
                     h->modulation.empty() &&      // (a graph bakes its kernel arguments: the modulation's phases change every step)
                     h->use_graph > 0;      // on request only: measured on ROCm 7.2 (profiles/r3i) a replayed pair is ~3 us per step
                                            // SLOWER than launching its kernels (64^3 17.6 -> 20.8, 128^3 28.8 -> 31.4, 200^3 81.5 -> 84.0)
@@ -406,6 +408,7 @@ struct Run {
     fill_mirror(h, st, h->cfg.bc[4] == FDTD_BC_PERIODIC ? -1 : 0, h->cfg.bc[4] == FDTD_BC_PERIODIC ? nz + 1 : nz);
     aniso_save(h, st);                     // (E^n of the nodes around fully anisotropic cells: the sweep's read set is this set)
     modulation_save(h, st);                // (E^n of the nodes inside time-modulated media)
+    nonlinear_save(h, st);                 // (E^n and I^n of the nodes inside Kerr media)
     h_side_terms(h, n, 0, nz, st, 7 & ~pml_in);
     advance_tfsf_aux(h, false, n, st);
     if (h->cfg.bc[4] == FDTD_BC_PERIODIC) fill_ghost_h(h, st);   // ghost(-1) must carry the pre-corrections too
@@ -1056,6 +1059,7 @@ struct Run {
     if (multi && nb_hi) HIPCHK(h, hipStreamWaitEvent(st, h->ev_h_bnd, 0));
     aniso_save(h, st);                     // (these kernels update E in place: E^n of the nodes around fully anisotropic cells first)
     modulation_save(h, st);
+    nonlinear_save(h, st);
     launch_e_main(h, e_bot, nz, st);
     e_side_terms(h, n, e_bot, nz, st, !multi);     // (one GPU: [e_bot, nz) is the whole grid; a z-slab rank carries no whole-grid lists — setup)
     advance_tfsf_aux(h, true, n, st);

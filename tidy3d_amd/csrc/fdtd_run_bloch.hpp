@@ -59,6 +59,8 @@ struct BlochRun {
     // PEC-conformal boundaries: linear with real coefficients as well — each handle corrects its own part (h_side_terms)
     if (!same_lists(hr->conformal, hi->conformal)) return fail(hr, "fdtd_run_bloch: the two solvers must carry the same PEC-conformal lists");
     if (multi && !hr->conformal.empty()) return fail(hr, "fdtd_run_bloch: PEC-conformal boundaries are not available on z-slabs");
+    // Kerr media: the update is not linear — the Re and Im parts cannot be patched separately
+    if (!hr->nonlinear.empty() || !hi->nonlinear.empty()) return fail(hr, "fdtd_run_bloch: nonlinear media are not available with Bloch boundaries");
     if (hi->cfg.bc[4] != hr->cfg.bc[4] || hi->cfg.bc[5] != hr->cfg.bc[5])
       return fail(hr, "fdtd_run_bloch: the two solvers must have the same z faces");
     if (hr->g.nx != hi->g.nx || hr->g.ny != hi->g.ny || hr->g.nz != hi->g.nz || hr->cfg.device != hi->cfg.device ||

@@ -239,9 +239,14 @@ def permute_spec(spec: SolverSpec, s: int) -> SolverSpec:
                                      nbr_comp=tuple(int(v) for v in comp_map(cs.nbr_comp)),
                                      nbr_ijk=np.ascontiguousarray(cs.nbr_ijk[:, :, sig]))
                  for cs in (getattr(spec, "conformal", None) or [])]
+    # Kerr lists: nodes, neighbour slots and components are renamed with the axes; a cyclic renaming keeps the slot order (b, c follow a)
+    nonlinear = [dataclasses.replace(ns, comp=int(comp_map(ns.comp)), ijk=np.ascontiguousarray(ns.ijk[:, sig]),
+                                     nbr_comp=tuple(int(v) for v in comp_map(ns.nbr_comp)),
+                                     nbr_ijk=np.ascontiguousarray(ns.nbr_ijk[:, :, sig]))
+                 for ns in (getattr(spec, "nonlinear", None) or [])]
     return dataclasses.replace(
         spec, shape=pick(spec.shape), boundaries=pick(spec.boundaries), bc=pick(spec.bc), pml=pick(spec.pml),
-        mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors, conformal=conformal,
+        mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors, conformal=conformal, nonlinear=nonlinear,
         absorber=None if spec.absorber is None else list(pick(spec.absorber)),
         bloch=None if spec.bloch is None else pick(spec.bloch),
         mirror_plus=None if getattr(spec, "mirror_plus", None) is None else pick(spec.mirror_plus))
@@ -660,6 +665,20 @@ class HipEngine:
                 nbr32, d32 = np.ascontiguousarray(nbr.T), _f32(np.asarray(cs.d).T)
                 self._chk(d.fdtd_add_pec_conformal(h, int(cs.comp), n, _ptr(cells), _ptr(nbr32), _ptr(d32)), "fdtd_add_pec_conformal")
             self.n_conformal_faces = sum(len(cs.ijk) for cs in conformal)
+        # Kerr media (spec.NonlinearSet)
+        self._table32 = (np.asarray(ca, np.float64), np.asarray(cb, np.float64))      # the float32 table, as the sweep reads it
+        self.n_nonlinear_nodes = 0
+        nonlinear = getattr(spec, "nonlinear", None) or []
+        if nonlinear:
+            from .exceptions import Tidy3dNotImplementedError
+            if aniso:
+                raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with FullyAnisotropicMedium are not supported")
+            if modulation:
+                raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with time-modulated (modulation_spec) media "
+                                                "are not supported")
+            if conformal:
+                raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with PECConformal are not supported")
+            self.add_nonlinear(nonlinear)
         # sources
         from .spec import BC_PEC
         for s in spec.sources:
@@ -811,6 +830,42 @@ class HipEngine:
         buf = (C.c_int64 * max(n, 1))()
         self._chk(self.lib.dll.fdtd_get_sweep_words(self.handle, buf, n), "fdtd_get_sweep_words")
         return [L.unpack_sweep_word(buf[i]) for i in range(n)]
+
+    def add_nonlinear(self, sets):
+        """Upload Kerr lists (spec.NonlinearSet, in the axes of ``self.spec``; at most one per E component of the handle): per node the
+        table coefficient the sweep applies there, the static medium recovered from it as for the modulation lists — eps_bar = dt /
+        (eps0 Cb) * 2 / (1 + Ca), s_bar = eps_bar (1 - Ca) / (1 + Ca) — chi3, and the eight neighbour slots as [8][n].  May be called
+        between runs: the next step forms I^n from the fields it finds."""
+        from .constants import EPSILON_0
+        from .exceptions import Tidy3dNotImplementedError
+        spec, d, h = self.spec, self.lib.dll, self.handle
+        _, ny, nz = spec.shape
+        if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz):
+            raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media are not available in z-slab (multi-GPU) runs")
+        if spec.bloch is not None:
+            raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with Bloch boundaries are not supported")
+        nx = self.nxp                       # row length on the device
+        sxy = nx * ny
+        ca32, cb32 = self._table32
+        for ns in sets:
+            n = len(ns.ijk)
+            if n == 0:
+                continue
+            ijk = np.asarray(ns.ijk, np.int64)
+            cells = np.ascontiguousarray((ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32))
+            j = np.asarray(ns.nbr_ijk, np.int64)
+            nbr = np.where(j[:, :, 0] >= 0, j[:, :, 2] * sxy + j[:, :, 1] * nx + j[:, :, 0], 0xFFFFFFFF).astype(np.uint32)
+            nbr32 = np.ascontiguousarray(nbr.T)
+            mi = spec.mat_idx[int(ns.comp)][ijk[:, 2], ijk[:, 1], ijk[:, 0]] if spec.mat_idx is not None else np.ones(n, np.int64)
+            ca_n, cb_n = ca32[mi], cb32[mi]
+            if not (cb_n > 0).all():
+                raise SolverLibraryError("a nonlinear node on a PEC cell")
+            eps_bar = spec.dt / (EPSILON_0 * cb_n) * 2.0 / (1.0 + ca_n)
+            s_bar = eps_bar * (1.0 - ca_n) / (1.0 + ca_n)
+            arrs = [_f32(ca_n), _f32(eps_bar), _f32(s_bar), _f32(np.asarray(ns.chi3, np.float64))]
+            self._chk(d.fdtd_add_nonlinear(h, int(ns.comp), n, _ptr(cells), _ptr(nbr32), *[_ptr(a) for a in arrs],
+                                           int(ns.num_iters)), "fdtd_add_nonlinear")
+            self.n_nonlinear_nodes += n
 
     def set_option(self, key: int, value: int):
         self._chk(self.lib.dll.fdtd_set_option(self.handle, key, value), "fdtd_set_option")

@@ -41,7 +41,7 @@ SYMBOLS = (
     "fdtd_far_field", "fdtd_set_mirror_plus", "fdtd_add_aniso", "fdtd_add_aniso_bloch", "fdtd_get_seam_stats",
     "fdtd_get_sweep_words", "fdtd_sweep_table", "fdtd_add_flux_time_monitor", "fdtd_get_monitor_bytes",
     "fdtd_add_field_time_monitor", "fdtd_add_field_dft_monitor", "fdtd_add_lattice_dft_monitor", "fdtd_add_modulation",
-    "fdtd_add_pec_conformal",
+    "fdtd_add_pec_conformal", "fdtd_add_nonlinear",
     "fdtd_near_field", "fdtd_near_field_chunks",
 )
 
@@ -55,7 +55,7 @@ F2_OFF_REASONS = {0: "", 1: "switched off", 2: "grid too small", 3: "z-slab rank
                   5: "dispersive media not confined to a few planes along z", 6: "TFSF box while it injects", 7: "Bloch / PMC-plus faces (or rows not a multiple of 4 cells)", 8: "magnetic sources with absorber layers",
                   9: "magnetic source node on a tile seam", 10: "too many source nodes", 11: "two-pass kernels",
                   12: "CPML shell too large a part of the grid", 13: "no device memory for the third field set", 14: "wide material table (more than 1023 media)",
-                  15: "time-modulated media", 16: "PEC-conformal boundaries"}
+                  15: "time-modulated media", 16: "PEC-conformal boundaries", 17: "nonlinear (Kerr) media"}
 
 
 class FdtdConfig(C.Structure):
@@ -132,6 +132,7 @@ class FdtdLib:
         d.fdtd_add_aniso_bloch.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp]
         d.fdtd_add_modulation.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double]
         d.fdtd_add_pec_conformal.argtypes = [vp, C.c_int, i64, vp, vp, vp]
+        d.fdtd_add_nonlinear.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, C.c_int]
         d.fdtd_add_point_source.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp]
         d.fdtd_add_tfsf.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, i64, vp,
                                     i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]

@@ -864,8 +864,55 @@ class ModulationSpec(_Model):
 
 @_register
 @dataclass
+class NonlinearSusceptibility(_Model):
+    """ref medium.py NonlinearSusceptibility: the instantaneous third-order response P_NL = eps0 chi3 |E|^2 E (chi3 in um^2 / V^2).
+    Real chi3 only; ``numiters`` is the reference's deprecated per-model iteration count: read, and ignored as there
+    (``NonlinearSpec.num_iters`` decides)."""
+
+    chi3: float = 0.0
+    numiters: Optional[int] = None
+
+    def __post_init__(self):
+        if isinstance(self.chi3, (complex, dict, tuple, list, Unsupported)):
+            z = _complex(self.chi3)
+            if z.imag != 0:
+                raise Tidy3dNotImplementedError("NonlinearSusceptibility with a complex chi3 is not supported")
+            self.chi3 = z.real
+        self.chi3 = float(self.chi3)
+        if not np.isfinite(self.chi3):
+            raise ValidationError("NonlinearSusceptibility.chi3 must be finite.")
+
+
+@_register
+@dataclass
+class NonlinearSpec(_Model):
+    """ref medium.py NonlinearSpec: the nonlinear models of a medium and the number of fixed-point iterations per time step.  Modelled:
+    ``NonlinearSusceptibility`` with real chi3 (several sum); every other model raises on use (``schema.with_nonlinear``)."""
+
+    models: Tuple[Any, ...] = ()
+    num_iters: int = 5
+
+    def __post_init__(self):
+        self.models = tuple(self.models or ())
+        for m in self.models:
+            if not isinstance(m, NonlinearSusceptibility):
+                raise Tidy3dNotImplementedError(f"NonlinearSpec model '{getattr(m, 'type', type(m).__name__)}' is not supported "
+                                                "(NonlinearSusceptibility with a real chi3 is)")
+        self.num_iters = int(self.num_iters)
+        if not 1 <= self.num_iters <= 64:          # (ref medium.py NONLINEAR_MAX_NUM_ITERS = 100; the solver library takes 64)
+            raise ValidationError("NonlinearSpec.num_iters must be between 1 and 64.")
+
+    @property
+    def chi3(self) -> float:
+        return float(sum(m.chi3 for m in self.models))
+
+
+@_register
+@dataclass
 class Medium(_AbstractMedium):
-    """Dispersionless medium (ref medium.py:1499), optionally time-modulated (``modulation_spec``)."""
+    """Dispersionless medium (ref medium.py:1499), optionally time-modulated (``modulation_spec``) or with an instantaneous Kerr
+    response (``nonlinear_spec``: a ``NonlinearSpec`` of ``NonlinearSusceptibility`` models; ``parse`` keeps a dict that carries one a
+    placeholder, ``with_nonlinear`` turns the placeholders the solver models into media)."""
 
     permittivity: float = 1.0
     conductivity: float = 0.0
@@ -873,10 +920,15 @@ class Medium(_AbstractMedium):
     frequency_range: Optional[Tuple[float, float]] = None
     allow_gain: bool = False
     modulation_spec: Any = None
+    nonlinear_spec: Any = None
 
     def __post_init__(self):
         if self.permittivity < 1.0:
             raise ValidationError("Medium.permittivity must be >= 1.")
+        if isinstance(self.nonlinear_spec, NonlinearSusceptibility):       # (the reference's older form: the model itself)
+            self.nonlinear_spec = NonlinearSpec(models=(self.nonlinear_spec,))
+        if self.nonlinear_spec is not None and not isinstance(self.nonlinear_spec, (NonlinearSpec, Unsupported)):
+            raise ValidationError("Medium.nonlinear_spec must be a NonlinearSpec.")
         ms = self.modulation_spec
         if ms is None or isinstance(ms, Unsupported):
             return
@@ -915,6 +967,81 @@ class Medium(_AbstractMedium):
         eps_c = (n + 1j * k) ** 2
         sigma = 2 * np.pi * freq * eps_c.imag * EPSILON_0
         return cls(permittivity=eps_c.real, conductivity=sigma, **kw)
+
+    @property
+    def is_nonlinear(self) -> bool:
+        """a ``nonlinear_spec`` with at least one model (chi3 = 0 included: its nodes are listed and advance as the linear medium,
+        bit for bit); ``n_cfl`` is that of the linear medium"""
+        ns = self.nonlinear_spec
+        if isinstance(ns, Unsupported):
+            ns.fail()
+        return isinstance(ns, NonlinearSpec) and len(ns.models) > 0
+
+
+NONLINEAR_PLACEHOLDER = "Medium with 'nonlinear_spec'"
+
+
+def _nonlinear_medium(u):
+    """The placeholder ``parse`` left for a ``Medium`` dict with a ``nonlinear_spec`` -> the ``Medium`` carrying the parsed spec where the
+    solver models it (NonlinearSusceptibility models with real chi3; several sum), a placeholder that names the model where it does
+    not (TwoPhotonAbsorption, KerrNonlinearity, complex chi3, no models), None for anything else."""
+    if not (isinstance(u, Unsupported) and u.type == NONLINEAR_PLACEHOLDER):
+        return None
+    raw = u.raw.get("nonlinear_spec")
+
+    def refuse(what):
+        return Unsupported(type=f"{NONLINEAR_PLACEHOLDER} {what}", raw=u.raw)
+    if not isinstance(raw, dict):
+        return refuse("that is no NonlinearSpec")
+    if raw.get("type") == "NonlinearSusceptibility":          # (the reference's older form: the model itself)
+        models, num_iters = [raw], 5
+    elif raw.get("type") == "NonlinearSpec":
+        models, num_iters = list(raw.get("models") or ()), raw.get("num_iters", 5)
+    else:
+        return refuse(f"of type '{raw.get('type')}'")
+    if not models:
+        return refuse("without models")
+    parsed = []
+    for m in models:
+        mtype = m.get("type") if isinstance(m, dict) else type(m).__name__
+        if mtype != "NonlinearSusceptibility":
+            return refuse(f"model '{mtype}'")
+        chi3 = m.get("chi3", 0.0)
+        if isinstance(chi3, (dict, complex, list, tuple)):
+            if _complex(chi3).imag != 0:
+                return refuse("model 'NonlinearSusceptibility' with a complex chi3")
+            chi3 = _complex(chi3).real
+        parsed.append(NonlinearSusceptibility(chi3=float(chi3), numiters=m.get("numiters")))     # (numiters: deprecated there, ignored here)
+    med = parse({k: v for k, v in u.raw.items() if k != "nonlinear_spec"})
+    if not isinstance(med, Medium):
+        return None
+    return dataclasses.replace(med, nonlinear_spec=NonlinearSpec(models=tuple(parsed), num_iters=5 if num_iters is None else num_iters))
+
+
+def with_nonlinear(sim):
+    """A copy of ``sim`` in which every placeholder of type "Medium with 'nonlinear_spec'" has become the ``Medium`` carrying the parsed
+    ``NonlinearSpec`` — where the raw spec holds NonlinearSusceptibility models with real chi3 — or a placeholder that names the model
+    the solver lacks.  ``parse`` itself keeps the placeholder (tests pin it); ``discretize`` and ``web.run`` call this first, so dicts,
+    JSON and .hdf5 files and real tidy3d objects run.  Placeholders of other media (``PoleResidue with 'nonlinear_spec'`` ...) and
+    those nested in other media stay as they are and raise on use."""
+    cache = {}
+
+    def conv(med):
+        if not (isinstance(med, Unsupported) and med.type == NONLINEAR_PLACEHOLDER):
+            return med
+        if id(med) not in cache:
+            cache[id(med)] = _nonlinear_medium(med) or med
+        return cache[id(med)]
+    medium = conv(sim.medium)
+    structures = tuple(s if conv(s.medium) is s.medium else dataclasses.replace(s, medium=conv(s.medium)) for s in sim.structures)
+    if medium is sim.medium and all(a is b for a, b in zip(structures, sim.structures)):
+        return sim
+    out = dataclasses.replace(sim, medium=medium, structures=structures)
+    names = {f.name for f in dataclasses.fields(sim)}
+    for k, v in vars(sim).items():                 # (what from_dict and the symmetry front end hang on the object)
+        if k not in names:
+            setattr(out, k, v)
+    return out
 
 
 def interp_dataset(arr, points: Dict[str, np.ndarray], method: str = "linear") -> np.ndarray:

@@ -103,6 +103,22 @@ class ConformalSet:
 
 
 @dataclass
+class NonlinearSet:
+    """The nodes of one E component inside Kerr media (ref medium.py NonlinearSpec with NonlinearSusceptibility models), merged over
+    the media:  D = eps0 (eps_bar + chi3 I) E,  I = E_a^2 + (mean of the four surrounding E_b nodes)^2 + (mean of the four surrounding
+    E_c nodes)^2.  eps_bar and the conductivity are the node's own static table medium (``mat_idx``, sub-pixel value included).  The
+    sweep advances the node with the static medium, E_lin = Ca E^n + Cb K; the solver replaces that by ``num_iters`` Jacobi
+    fixed-point iterations of (D^{n+1} - D^n) / dt + sigma (E^{n+1} + E^n) / 2 = K (csrc/fdtd_nonlinear.hpp)."""
+
+    comp: int                         # E component a
+    ijk: np.ndarray                   # [n, 3] nodes (i, j, k), each at most once
+    nbr_comp: Tuple[int, ...]         # [8] component of every slot: four of b = (a + 1) % 3, four of c = (a + 2) % 3
+    nbr_ijk: np.ndarray               # [n, 8, 3], the layout of AnisoSet.nbr_ijk; -1 = no node (beyond a non-periodic wall): 0 in its mean
+    chi3: np.ndarray                  # float64 [n], um^2 / V^2
+    num_iters: int = 5                # the same in every set of a spec
+
+
+@dataclass
 class PmlFace:
     """CPML profile of one face (ref boundary.py:195-254; units of sigma/alpha: 2 eps0/dt)."""
 
@@ -267,6 +283,7 @@ class SolverSpec:
     aniso: List[AnisoSet] = field(default_factory=list)   # fully anisotropic bodies: off-diagonal coupling per E component
     modulation: List[ModulationSet] = field(default_factory=list)   # time-modulated media: their nodes per E component and medium
     conformal: List[ConformalSet] = field(default_factory=list)     # PEC-conformal boundaries: the cut faces per H component
+    nonlinear: List[NonlinearSet] = field(default_factory=list)     # Kerr media: their nodes, one set per E component
     shutoff: float = 0.0                                # 0 disables the early stop
     decay_every: int = 0                                # 0 = never evaluate field decay
     decay_ref_step: int = 0                             # steps before this never shut off

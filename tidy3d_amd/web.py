@@ -127,6 +127,7 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     from .engine import HipEngine
 
     sim, was_tidy3d = _as_mirror(simulation)
+    sim = td.with_nonlinear(sim)      # (Medium placeholders with a NonlinearSpec of NonlinearSusceptibility models become media)
     sim.validate_pre_upload(source_required=True)
     paths = DevicePaths(flux_time_device, field_time_device, field_dft_device, projection_device)
     if devices is not None and len(devices) > 1:
@@ -138,6 +139,9 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         if pec_conformal_of(sim) is not None:
             raise Tidy3dNotImplementedError("PECConformal together with devices= with more than one GPU is not supported "
                                             "(SubpixelSpec(pec=Staircasing()) is)")
+        if any(isinstance(m, td.Medium) and m.is_nonlinear for m in sim.mediums):
+            raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with devices= with more than one GPU are not "
+                                            "supported")
         sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose,
                                    dict(_dist_options or {}, exact_projection_device=exact_projection_device))
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
@@ -164,6 +168,10 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     if spec.conformal:
         lines.insert(-2, "PEC-conformal boundaries (Dey-Mittra): %d cut faces listed; single time steps."
                      % sum(len(cs.ijk) for cs in spec.conformal))
+
+    if spec.nonlinear:
+        lines.insert(-2, "Nonlinear (Kerr) media: %d nodes listed, %d fixed-point iterations per step; single time steps."
+                     % (sum(len(ns.ijk) for ns in spec.nonlinear), spec.nonlinear[0].num_iters))
 
     def progress(step, t, decay):
         ln = _log_line(step, spec.n_steps, t, decay)
