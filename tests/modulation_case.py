@@ -10,7 +10,6 @@ and tests/test_gpu_modulation.py (device).  docs/history/MODULATION.md holds the
   condition  the fp64 reference WITHOUT the patch differs from it by at least 100 x the bar on the listed nodes (``visibility``): a
              scenario that cannot see the feature proves nothing."""
 import dataclasses
-import os
 
 import numpy as np
 
@@ -20,6 +19,7 @@ from tidy3d_amd.discretize import discretize
 from oracle.fdtd_numpy import OracleFdtd, _EPS0
 
 import dense_state as ds
+import list_case as lc
 from cases import DL, PULSE
 
 BAR = 2e-5
@@ -167,60 +167,24 @@ def bloch_xy():
 
 SCENARIOS = {"pec_box_blocks": pec_box_blocks, "seam_bar": seam_bar, "pml_slab": pml_slab, "graded_travelling_wave": graded_travelling_wave,
              "bloch_xy": bloch_xy}
-PATHS = ("fused", "twopass")
-_CACHE = {}
+PATHS = lc.PATHS
+GOLDEN = lc.golden("modulation")
 
 
-class Scenario:
-    """A spec with its state and its fp64 references (with and without the patch) per K, computed once per process and never changed."""
-
-    def __init__(self, label):
-        self.label, self.spec = label, SCENARIOS[label]()
-        assert self.spec.modulation, label
-        self.plain = dataclasses.replace(self.spec, modulation=[])
-        self.state, _ = ds.admissible_state(self.plain, seed=1)
-        self._ref, self._plain = {}, {}
-
-    def _run(self, cls, spec, K):
-        o = cls(spec)
-        ds._load(o, self.state)
-        for _ in range(K):
-            o.step()
-        return [np.array(f) for f in o.E + o.H]
-
-    def ref(self, K):
-        if K not in self._ref:
-            self._ref[K] = self._run(ModulatedOracle, self.spec, K)
-        return self._ref[K]
-
-    def ref_plain(self, K):
-        if K not in self._plain:
-            self._plain[K] = self._run(OracleFdtd, self.plain, K)
-        return self._plain[K]
-
-    def visibility(self, K):
-        """rel-L2 between the two fp64 references over the listed nodes (all E components together)"""
-        a, b = self.ref(K), self.ref_plain(K)
-        num = den = 0.0
-        for m in self.spec.modulation:
-            i = (m.ijk[:, 2], m.ijk[:, 1], m.ijk[:, 0])
-            num += float(np.sum(np.abs(a[m.comp][i] - b[m.comp][i]) ** 2))
-            den += float(np.sum(np.abs(a[m.comp][i]) ** 2))
-        return float(np.sqrt(num / den))
-
-    def errors(self, fields, K):
-        """per field |got - ref| / |ref| (L2 over the whole array) against the fp64 ModulatedOracle"""
-        ref = self.ref(K)
-        return [float(np.linalg.norm(np.asarray(fields[c], np.complex128) - ref[c]) / np.linalg.norm(ref[c])) for c in range(6)]
-
-    def run(self, lib, K, path, plain=False):
-        return ds.run_engine(self.plain if plain else self.spec, lib, self.state, K, path)
+class Scenario(lc.Scenario):
+    ATTR, TAG, ORACLE, SCENARIOS, BAR, GOLDEN = "modulation", "modulation", ModulatedOracle, SCENARIOS, BAR, GOLDEN
 
 
 def scenario(label):
-    if label not in _CACHE:
-        _CACHE[label] = Scenario(label)
-    return _CACHE[label]
+    return lc.scenario(Scenario, label)
+
+
+def emulator_record(lib):
+    return lc.emulator_record(Scenario, lib)
+
+
+def check_against_emulator_record(label, fields):
+    return lc.check_against_emulator_record(scenario(label), fields)
 
 
 def check_scenario(lib, label, K, what=""):
@@ -242,34 +206,3 @@ def check_scenario(lib, label, K, what=""):
         assert label != "bloch_xy"      # (Bloch x, periodic y, PEC z: tests/test_emu_fused.py holds the linear sweeps to equal bits)
         print(f"[modulation] {label} K={K}: the plain sweeps of this spec differ between the paths; no bit comparison")
     return worst, got
-
-
-# ---------------------------------------------------------------------------------------------------------------- emulator golden
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "modulation", "emulator_k7.npz")
-ULPS = 4
-
-
-def listed_values(label, fields):
-    """E at the listed nodes of ``label``, list after list: what the emulator's record under tests/golden/modulation holds (fp32 parts)"""
-    sc = scenario(label)
-    v = np.concatenate([np.asarray(fields[m.comp])[m.ijk[:, 2], m.ijk[:, 1], m.ijk[:, 0]] for m in sc.spec.modulation])
-    return v.astype(np.complex64 if np.iscomplexobj(v) else np.float32)
-
-
-def emulator_record(lib):
-    """label -> listed_values of the fused run of 7 steps (tests/test_emu_modulation.py holds the committed file to the emulator's bits)"""
-    return {label: listed_values(label, scenario(label).run(lib, 7, "fused").fields) for label in SCENARIOS}
-
-
-def check_against_emulator_record(label, fields):
-    """the device within ULPS fp32 ulps of the largest listed value of the emulator's run; -> (largest difference in those ulps, equal bits?)"""
-    want = np.load(GOLDEN)[label]
-    got = listed_values(label, fields)
-    assert got.shape == want.shape and got.dtype == want.dtype
-    big = float(np.abs(np.concatenate([want.real, want.imag]) if np.iscomplexobj(want) else want).max())
-    ulp = float(np.spacing(np.float32(big)))
-    diff = got.astype(np.complex128) - want.astype(np.complex128)
-    worst = float(max(np.abs(diff.real).max(), np.abs(diff.imag).max())) / ulp
-    print(f"[modulation] {label}: device against the emulator's record: {worst:.2f} ulp of the largest value, equal bits: {np.array_equal(got, want)}")
-    assert worst <= ULPS, (label, worst)
-    return worst, bool(np.array_equal(got, want))

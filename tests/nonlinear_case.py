@@ -12,7 +12,6 @@
   bar        2e-5 rel-L2 per field against the fp64 reference (the bar of tests/test_gpu_parity.py).
   condition  the fp64 reference WITHOUT the lists differs from it by at least 100 x the bar on the listed nodes (``visibility``)."""
 import dataclasses
-import os
 
 import numpy as np
 
@@ -20,6 +19,7 @@ import tidy3d_amd.schema as td
 from oracle.fdtd_numpy import OracleFdtd, _EPS0
 
 import dense_state as ds
+import list_case as lc
 import modulation_case as mc
 from cases import PULSE
 
@@ -170,8 +170,8 @@ def graded_two_media():
 
 SCENARIOS = {"pec_box_blocks": pec_box_blocks, "seam_bar": seam_bar, "periodic_xy": periodic_xy, "pml_slab": pml_slab,
              "graded_two_media": graded_two_media}
-PATHS = ("fused", "twopass")
-_CACHE = {}
+PATHS = lc.PATHS
+GOLDEN = lc.golden("nonlinear")
 
 
 def listed_eps(spec, s):
@@ -188,19 +188,15 @@ def with_lists(spec, scale=1.0, num_iters=None, reverse=False):
     return dataclasses.replace(spec, nonlinear=out[::-1] if reverse else out)
 
 
-class Scenario:
-    """A spec with its state, chi3 scaled to the state, and its fp64 references per (K, num_iters), computed once per process."""
+class Scenario(lc.Scenario):
+    """chi3 scaled to the state; the fp64 references per (K, num_iters)"""
+    ATTR, TAG, ORACLE, SCENARIOS, BAR, GOLDEN = "nonlinear", "nonlinear", NonlinearOracle, SCENARIOS, BAR, GOLDEN
 
     def __init__(self, label):
-        self.label = label
-        raw = SCENARIOS[label]()
-        assert raw.nonlinear, label
-        self.plain = dataclasses.replace(raw, nonlinear=[])
-        self.state, _ = ds.admissible_state(self.plain, seed=1)
-        s0 = self._strength(raw, self.state)
+        super().__init__(label)
+        s0 = self._strength(self.spec, self.state)
         assert s0 > 0
-        self.spec = with_lists(raw, scale=TARGET / s0)
-        self._ref, self._plain = {}, {}
+        self.spec = with_lists(self.spec, scale=TARGET / s0)
 
     @staticmethod
     def _strength(spec, fields):
@@ -211,38 +207,14 @@ class Scenario:
         """max |chi3| I / eps_bar over the listed nodes, of the initial state (K = 0) or of the reference after K steps"""
         return self._strength(self.spec, self.state if K == 0 else self.ref(K))
 
-    def _run(self, cls, spec, K):
-        o = cls(spec)
-        ds._load(o, self.state)
-        for _ in range(K):
-            o.step()
-        return [np.array(f) for f in o.E + o.H]
+    def ref_spec(self, num_iters):
+        return with_lists(self.spec, num_iters=num_iters)
 
     def ref(self, K, num_iters=5):
-        if (K, num_iters) not in self._ref:
-            self._ref[K, num_iters] = self._run(NonlinearOracle, with_lists(self.spec, num_iters=num_iters), K)
-        return self._ref[K, num_iters]
-
-    def ref_plain(self, K):
-        if K not in self._plain:
-            self._plain[K] = self._run(OracleFdtd, self.plain, K)
-        return self._plain[K]
-
-    def listed_diff(self, a, b):
-        """rel-L2 between two field sets over the listed nodes (all E components together)"""
-        num = den = 0.0
-        for s in self.spec.nonlinear:
-            i = (s.ijk[:, 2], s.ijk[:, 1], s.ijk[:, 0])
-            num += float(np.sum(np.abs(a[s.comp][i] - b[s.comp][i]) ** 2))
-            den += float(np.sum(np.abs(a[s.comp][i]) ** 2))
-        return float(np.sqrt(num / den))
-
-    def visibility(self, K):
-        return self.listed_diff(self.ref(K), self.ref_plain(K))
+        return super().ref(K, num_iters)
 
     def errors(self, fields, K, num_iters=5):
-        ref = self.ref(K, num_iters)
-        return [float(np.linalg.norm(np.asarray(fields[c], np.float64) - ref[c]) / np.linalg.norm(ref[c])) for c in range(6)]
+        return super().errors(fields, K, num_iters)
 
     def run(self, lib, K, path, num_iters=5, plain=False, **kw):
         spec = self.plain if plain else with_lists(self.spec, num_iters=num_iters, **kw)
@@ -250,9 +222,16 @@ class Scenario:
 
 
 def scenario(label):
-    if label not in _CACHE:
-        _CACHE[label] = Scenario(label)
-    return _CACHE[label]
+    return lc.scenario(Scenario, label)
+
+
+def emulator_record(lib):
+    """(num_iters 5)"""
+    return lc.emulator_record(Scenario, lib)
+
+
+def check_against_emulator_record(label, fields):
+    return lc.check_against_emulator_record(scenario(label), fields)
 
 
 def check_scenario(lib, label, K, num_iters, what=""):
@@ -272,31 +251,3 @@ def check_scenario(lib, label, K, num_iters, what=""):
     for c in range(6):
         assert np.array_equal(got["fused"].fields[c], got["twopass"].fields[c]), (label, K, num_iters, ds.COMP[c])
     return worst, got
-
-
-# ---------------------------------------------------------------------------------------------------------------- emulator golden
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nonlinear", "emulator_k7.npz")
-ULPS = 4
-
-
-def listed_values(label, fields):
-    """E at the listed nodes of ``label``, list after list: what the emulator's record under tests/golden/nonlinear holds (fp32)"""
-    sc = scenario(label)
-    return np.concatenate([np.asarray(fields[s.comp])[s.ijk[:, 2], s.ijk[:, 1], s.ijk[:, 0]] for s in sc.spec.nonlinear]).astype(np.float32)
-
-
-def emulator_record(lib):
-    """label -> listed_values of the fused run of 7 steps, num_iters 5 (tests/test_emu_nonlinear.py holds the committed file to the emulator's bits)"""
-    return {label: listed_values(label, scenario(label).run(lib, 7, "fused").fields) for label in SCENARIOS}
-
-
-def check_against_emulator_record(label, fields):
-    """the device within ULPS fp32 ulps of the largest listed value of the emulator's run; -> (largest difference in those ulps, equal bits?)"""
-    want = np.load(GOLDEN)[label]
-    got = listed_values(label, fields)
-    assert got.shape == want.shape and got.dtype == want.dtype
-    ulp = float(np.spacing(np.float32(np.abs(want).max())))
-    worst = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max()) / ulp
-    print(f"[nonlinear] {label}: device against the emulator's record: {worst:.2f} ulp of the largest value, equal bits: {np.array_equal(got, want)}")
-    assert worst <= ULPS, (label, worst)
-    return worst, bool(np.array_equal(got, want))

@@ -12,7 +12,6 @@ the scheme and the figures.
   condition  the fp64 oracle WITHOUT the correction differs from the reference by at least 2e-3 over the listed H nodes after one
              step (``visibility``)."""
 import dataclasses
-import os
 
 import numpy as np
 
@@ -21,6 +20,7 @@ from tidy3d_amd.discretize import discretize
 from oracle.fdtd_numpy import OracleFdtd, _EPS0, _MU0, _C0
 
 import dense_state as ds
+import list_case as lc
 from cases import DL, PULSE
 
 BAR = 2e-5
@@ -269,59 +269,24 @@ SCENARIOS = {"sphere_blocks": sphere_blocks, "seam_cylinder": seam_cylinder, "pm
              "graded_sphere": graded_sphere, "periodic_sphere": periodic_sphere}
 # label -> (scenario, axis_shift): the first scenario under the other two axis renamings as well
 RUNS = {**{k: (k, 0) for k in SCENARIOS}, "sphere_blocks_shift1": ("sphere_blocks", 1), "sphere_blocks_shift2": ("sphere_blocks", 2)}
-PATHS = ("fused", "twopass")
-_CACHE = {}
+PATHS = lc.PATHS
+GOLDEN = lc.golden("pec_conformal")
 
 
-class Scenario:
-    """A spec with its state and its fp64 references (with and without the correction) per K, computed once and never changed."""
-
-    def __init__(self, label):
-        self.label, self.spec = label, SCENARIOS[label]()
-        assert self.spec.conformal, label
-        self.plain = dataclasses.replace(self.spec, conformal=[])
-        self.state, _ = ds.admissible_state(self.plain, seed=1)
-        self._ref, self._plain = {}, {}
-
-    def _run(self, cls, spec, K):
-        o = cls(spec)
-        ds._load(o, self.state)
-        for _ in range(K):
-            o.step()
-        return [np.array(f) for f in o.E + o.H]
-
-    def ref(self, K):
-        if K not in self._ref:
-            self._ref[K] = self._run(ConformalOracle, self.spec, K)
-        return self._ref[K]
-
-    def ref_plain(self, K):
-        if K not in self._plain:
-            self._plain[K] = self._run(OracleFdtd, self.plain, K)
-        return self._plain[K]
-
-    def visibility(self, K=1):
-        """rel-L2 between the two fp64 references over the listed H nodes"""
-        a, b = self.ref(K), self.ref_plain(K)
-        num = den = 0.0
-        for cs in self.spec.conformal:
-            i = (cs.ijk[:, 2], cs.ijk[:, 1], cs.ijk[:, 0])
-            num += float(np.sum(np.abs(a[cs.comp][i] - b[cs.comp][i]) ** 2))
-            den += float(np.sum(np.abs(a[cs.comp][i]) ** 2))
-        return float(np.sqrt(num / den))
-
-    def errors(self, fields, K):
-        ref = self.ref(K)
-        return [float(np.linalg.norm(np.asarray(fields[c], np.float64) - ref[c]) / np.linalg.norm(ref[c])) for c in range(6)]
-
-    def run(self, lib, K, path, plain=False, axis_shift=0):
-        return ds.run_engine(self.plain if plain else self.spec, lib, self.state, K, path, axis_shift=axis_shift)
+class Scenario(lc.Scenario):
+    ATTR, TAG, ORACLE, SCENARIOS, BAR, GOLDEN = "conformal", "pec-conformal", ConformalOracle, SCENARIOS, BAR, GOLDEN
 
 
 def scenario(label):
-    if label not in _CACHE:
-        _CACHE[label] = Scenario(label)
-    return _CACHE[label]
+    return lc.scenario(Scenario, label)
+
+
+def emulator_record(lib):
+    return lc.emulator_record(Scenario, lib)
+
+
+def check_against_emulator_record(label, fields):
+    return lc.check_against_emulator_record(scenario(label), fields)
 
 
 def check_run(lib, run_label, K, what=""):
@@ -343,31 +308,3 @@ def check_run(lib, run_label, K, what=""):
     else:
         print(f"[pec-conformal] {run_label} K={K}: the plain sweeps of this spec differ between the paths; no bit comparison")
     return worst, got
-
-
-# ---------------------------------------------------------------------------------------------------------------- emulator golden
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pec_conformal", "emulator_k7.npz")
-ULPS = 4
-
-
-def listed_values(label, fields):
-    """H at the listed faces of ``label``, list after list (fp32): what the emulator's record under tests/golden/pec_conformal holds"""
-    sc = scenario(label)
-    return np.concatenate([np.asarray(fields[cs.comp])[cs.ijk[:, 2], cs.ijk[:, 1], cs.ijk[:, 0]] for cs in sc.spec.conformal]).astype(np.float32)
-
-
-def emulator_record(lib):
-    """label -> listed_values of the fused run of 7 steps"""
-    return {label: listed_values(label, scenario(label).run(lib, 7, "fused").fields) for label in SCENARIOS}
-
-
-def check_against_emulator_record(label, fields):
-    """the device within ULPS fp32 ulps of the largest listed value of the emulator's run; -> (largest difference in those ulps, equal bits?)"""
-    want = np.load(GOLDEN)[label]
-    got = listed_values(label, fields)
-    assert got.shape == want.shape and got.dtype == want.dtype
-    ulp = float(np.spacing(np.float32(np.abs(want).max())))
-    worst = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max()) / ulp
-    print(f"[pec-conformal] {label}: device against the emulator's record: {worst:.2f} ulp of the largest value, equal bits: {np.array_equal(got, want)}")
-    assert worst <= ULPS, (label, worst)
-    return worst, bool(np.array_equal(got, want))

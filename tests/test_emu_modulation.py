@@ -15,7 +15,7 @@ from tidy3d_amd.discretize import discretize
 from tidy3d_amd.engine import HipEngine
 from tidy3d_amd.exceptions import SetupError, Tidy3dNotImplementedError
 
-import dense_state as ds
+import list_case as lc
 import modulation_case as mc
 from cases import DL, PULSE
 
@@ -189,55 +189,14 @@ def test_off_reason(emu_lib):
                       [td.Structure(geometry=td.Box(center=(0, 0, 0), size=(0.4, 0.4, 0.4)), medium=mc.eps_modulated())])
     spec = discretize(sim, n_steps=4).spec
     spec.decay_every = 0
-    assert spec.shape == (128, 128, 64)
-    with HipEngine(spec, lib=emu_lib) as e:
-        st = e.run(4)
-    assert int(st.fused2_pairs) == 0 and int(st.fused2_off_reason) == 15
-    assert L.F2_OFF_REASONS[15] == "time-modulated media"
-    with HipEngine(dataclasses.replace(spec, modulation=[]), lib=emu_lib) as e:       # the same grid without the lists does take pairs
-        assert int(e.run(4).fused2_pairs) == 2
+    lc.off_reason(emu_lib, spec, dataclasses.replace(spec, modulation=[]), 15, "time-modulated media")
 
 
 # ---------------------------------------------------------------------------------------------------------------- lifecycle
 def lifecycle(lib, variant=L.VARIANT_AUTO):
-    """run(3) + run(4) == run(7); fdtd_reset repeats the bits; a set_field in mid-run is held to a handle that took its first three
-    steps from another state (the step count is part of the medium's state, nothing else is hidden in a PEC box)."""
-    sc = mc.scenario("pec_box_blocks")
-    state2 = ds.admissible_state(sc.plain, seed=2)[0]
-
-    def fields(e):
-        return [e.get_field(c) for c in range(6)]
-
-    def load(e, state):
-        for c in range(6):
-            e.set_field(c, state[c])
-    with HipEngine(sc.spec, lib=lib, variant=variant) as e:
-        load(e, sc.state)
-        e.run(7)
-        whole = fields(e)
-        e.reset()
-        load(e, sc.state)
-        e.run(3)
-        e.run(4)
-        split = fields(e)
-        e.reset()
-        load(e, sc.state)
-        e.run(3)
-        load(e, state2)
-        e.run(4)
-        mid = fields(e)
-    with HipEngine(sc.spec, lib=lib, variant=variant) as e:
-        load(e, state2)
-        e.run(3)
-        load(e, state2)
-        e.run(4)
-        fresh = fields(e)
-    for c in range(6):
-        assert np.array_equal(whole[c], split[c]), ds.COMP[c]
-        assert np.array_equal(mid[c], fresh[c]), ds.COMP[c]
-        assert not np.array_equal(mid[c], whole[c])
-    assert max(mc.scenario("pec_box_blocks").errors(whole, 7)) <= mc.BAR
-    return whole
+    """list_case.lifecycle on the PEC box, step pairs left on (the step count is part of the medium's state, nothing else is hidden
+    in a PEC box)"""
+    return lc.lifecycle(lib, mc.scenario("pec_box_blocks"), variant, twostep_off=False)
 
 
 @pytest.mark.parametrize("variant", ["fused", "twopass"])

@@ -17,6 +17,7 @@ from tidy3d_amd.engine import HipEngine, permute_spec
 from tidy3d_amd.exceptions import Tidy3dNotImplementedError
 
 import dense_state as ds
+import list_case as lc
 import modulation_case as mc
 import nonlinear_case as nc
 from cases import DL
@@ -250,13 +251,7 @@ def off_reason(lib):
     sim = mc._box_sim((128, 128, 64), nc._PEC3(), [nc._bx((0, 0, 0), (0.4, 0.4, 0.4), nc.kerr(chi3=1e-3))], sources=(nc.DIPOLE,))
     spec = discretize(sim, n_steps=4).spec
     spec.decay_every = 0
-    assert spec.shape == (128, 128, 64)
-    with HipEngine(spec, lib=lib) as e:
-        st = e.run(4)
-    assert int(st.fused2_pairs) == 0 and int(st.fused2_off_reason) == 17
-    assert L.F2_OFF_REASONS[17] == "nonlinear (Kerr) media"
-    with HipEngine(dataclasses.replace(spec, nonlinear=[]), lib=lib) as e:       # the same grid without the lists does take pairs
-        assert int(e.run(4).fused2_pairs) == 2
+    lc.off_reason(lib, spec, dataclasses.replace(spec, nonlinear=[]), 17, "nonlinear (Kerr) media")
 
 
 def test_off_reason(emu_lib):
@@ -265,70 +260,29 @@ def test_off_reason(emu_lib):
 
 # ---------------------------------------------------------------------------------------------------------------- lifecycle
 def lifecycle(lib, variant=L.VARIANT_AUTO):
-    """run(3) + run(4) == run(7); fdtd_reset repeats the bits; a list added to a live handle between runs, and a set_field in mid-run,
-    equal a fresh handle that reached the same step count and was given that state (I^n is formed from the fields in front of every
-    step, nothing is carried).  The graded PEC box: no CPML and no dispersive body, whose states a set_field would not replace."""
+    """list_case.lifecycle, and a list added to a live handle between runs against a fresh handle that reached the same step count and
+    was given that state (I^n is formed from the fields in front of every step, nothing is carried).  The graded PEC box: no CPML
+    and no dispersive body, whose states a set_field would not replace."""
     sc = nc.scenario("graded_two_media")
-    state2 = ds.admissible_state(sc.plain, seed=2)[0]
 
-    def fields(e):
-        return [e.get_field(c) for c in range(6)]
-
-    def load(e, state):
+    def late_list(engine, load, fields, whole):
+        """three steps with two components' lists, then the third's, against a fresh handle from that state"""
+        with engine(dataclasses.replace(sc.spec, nonlinear=[s for s in sc.spec.nonlinear if s.comp != 2])) as e:
+            load(e)
+            e.run(3)
+            at3 = fields(e)
+            e.add_nonlinear([s for s in sc.spec.nonlinear if s.comp == 2])
+            e.run(4)
+            late = fields(e)
+        with engine() as e:
+            load(e)
+            e.run(3)                 # (the step count is part of the state: the dipole's waveform follows it)
+            load(e, at3)
+            e.run(4)
+            late_fresh = fields(e)
         for c in range(6):
-            e.set_field(c, state[c])
-    with HipEngine(sc.spec, lib=lib, variant=variant) as e:
-        e.set_option(L.OPT_TWOSTEP, 0)
-        load(e, sc.state)
-        e.run(7)
-        whole = fields(e)
-        e.reset()
-        load(e, sc.state)
-        e.run(7)
-        again = fields(e)
-        e.reset()
-        load(e, sc.state)
-        e.run(3)
-        e.run(4)
-        split = fields(e)
-        e.reset()
-        load(e, sc.state)
-        e.run(3)
-        load(e, state2)
-        e.run(4)
-        mid = fields(e)
-    with HipEngine(sc.spec, lib=lib, variant=variant) as e:
-        e.set_option(L.OPT_TWOSTEP, 0)
-        load(e, state2)
-        e.run(3)                 # (the step count is part of the state: the dipole's waveform follows it)
-        load(e, state2)
-        e.run(4)
-        fresh = fields(e)
-    # a list added to a live handle between runs: three plain steps, then the lists, against a fresh handle from that state
-    two = [s for s in sc.spec.nonlinear if s.comp != 2]
-    with HipEngine(dataclasses.replace(sc.spec, nonlinear=two), lib=lib, variant=variant) as e:
-        e.set_option(L.OPT_TWOSTEP, 0)
-        load(e, sc.state)
-        e.run(3)
-        at3 = fields(e)
-        e.add_nonlinear([s for s in sc.spec.nonlinear if s.comp == 2])
-        e.run(4)
-        late = fields(e)
-    with HipEngine(sc.spec, lib=lib, variant=variant) as e:
-        e.set_option(L.OPT_TWOSTEP, 0)
-        load(e, sc.state)
-        e.run(3)
-        load(e, at3)
-        e.run(4)
-        late_fresh = fields(e)
-    for c in range(6):
-        assert np.array_equal(whole[c], again[c]), ds.COMP[c]
-        assert np.array_equal(whole[c], split[c]), ds.COMP[c]
-        assert np.array_equal(mid[c], fresh[c]), ds.COMP[c]
-        assert np.array_equal(late[c], late_fresh[c]), ds.COMP[c]
-        assert not np.array_equal(mid[c], whole[c]) and not np.array_equal(late[c], whole[c])
-    assert max(sc.errors(whole, 7)) <= nc.BAR
-    return whole
+            assert np.array_equal(late[c], late_fresh[c]) and not np.array_equal(late[c], whole[c]), ds.COMP[c]
+    return lc.lifecycle(lib, sc, variant, steps=late_list)
 
 
 @pytest.mark.parametrize("variant", ["fused", "twopass"])

@@ -18,7 +18,7 @@ from tidy3d_amd.discretize import discretize
 from tidy3d_amd.engine import HipEngine
 from tidy3d_amd.exceptions import Tidy3dNotImplementedError
 
-import dense_state as ds
+import list_case as lc
 import pec_conformal_case as pc
 from cases import DL, PULSE
 
@@ -179,47 +179,22 @@ def test_the_committed_record_is_the_emulators(emu_lib):
 def off_reason(lib):
     """128 x 128 x 64, 4 steps: no pairs under reason 16; the same grid staircased takes pairs"""
     body = td.Structure(geometry=td.Sphere(center=(0.013, 0.021, -0.008), radius=10.3 * DL), medium=td.PEC)
-    for sub, pairs, why in ((pc.CONFORMAL, 0, 16), (pc.STAIRCASE, 2, None)):
-        spec = pc._spec(pc._box_sim((128, 128, 64), pc.PEC_WALLS, [body], subpixel=sub), n_steps=4)
-        assert bool(spec.conformal) == (sub is pc.CONFORMAL)
-        with HipEngine(spec, lib=lib) as e:
-            st = e.run(4)
-        assert int(st.fused2_pairs) == pairs, (pairs, int(st.fused2_pairs), int(st.fused2_off_reason))
-        if why is not None:
-            assert int(st.fused2_off_reason) == why and L.F2_OFF_REASONS[why] == "PEC-conformal boundaries"
+    spec, stair = (pc._spec(pc._box_sim((128, 128, 64), pc.PEC_WALLS, [body], subpixel=sub), n_steps=4) for sub in (pc.CONFORMAL, pc.STAIRCASE))
+    assert spec.conformal and not stair.conformal
+    lc.off_reason(lib, spec, stair, 16, "PEC-conformal boundaries")
 
 
 def lifecycle(lib, variant):
-    """run(3) + run(4) == run(7); fdtd_reset repeats the bits and keeps the lists"""
+    """list_case.lifecycle without the set_field in mid-run (the Lorentz block's pole states); fdtd_reset keeps the lists"""
     sc = pc.scenario("sphere_blocks")
 
-    def fields(e):
-        return [e.get_field(c) for c in range(6)]
-
-    def load(e):
-        e.set_option(L.OPT_TWOSTEP, 0)
-        for c in range(6):
-            e.set_field(c, sc.state[c])
-    with HipEngine(sc.spec, lib=lib, variant=variant, axis_shift=0) as e:
-        load(e)
-        e.run(7)
-        whole = fields(e)
-        e.reset()
-        load(e)
-        e.run(3)
-        e.run(4)
-        split = fields(e)
-        e.reset()
-        load(e)
-        e.run(7)
-        again = fields(e)
-    with HipEngine(sc.plain, lib=lib, variant=variant, axis_shift=0) as e:
-        load(e)
-        e.run(7)
-        plain = fields(e)
-    for c in range(6):
-        assert np.array_equal(whole[c], split[c]) and np.array_equal(whole[c], again[c]), ds.COMP[c]
-    assert any(not np.array_equal(whole[c], plain[c]) for c in range(3, 6))      # the lists were there, also after the reset
+    def against_plain(engine, load, fields, whole):
+        with engine(sc.plain) as e:
+            load(e)
+            e.run(7)
+            plain = fields(e)
+        assert any(not np.array_equal(whole[c], plain[c]) for c in range(3, 6))      # the lists were there, also after the reset
+    lc.lifecycle(lib, sc, variant, mid=False, steps=against_plain, axis_shift=0)
 
 
 def test_off_reason(emu_lib):

@@ -88,39 +88,38 @@ struct Disp {
   long long pairs = 0;             // pairs of the last run whose sweep carried the ADE update of its first step
 };
 
-struct AnisoGroup {                 // fdtd_aniso.hpp: the off-diagonal coupling of E component `comp` inside fully anisotropic bodies
-  int comp;
-  long long n;
-  uint32_t *cell, *nbr;
+// ---- whole-grid node lists: structure-of-arrays lists of the nodes of one field component, applied by small kernels around every
+// single step (h_side_terms / e_side_terms say what a whole-grid list is, who applies it and who refuses it).  Four kinds:
+struct ListHead { int comp; long long n; uint32_t* cell; };      // the field component whose nodes are listed, how many, which [n]
+struct AnisoGroup : ListHead {      // fdtd_aniso.hpp: the off-diagonal coupling of E component `comp` inside fully anisotropic bodies
+  uint32_t* nbr;
   float *w_new, *w_old, *old, *delta;
   uint8_t* wrap;                    // [8n] wrap codes of the slots (fdtd_add_aniso_bloch), nullptr = none: read by fdtd_run_bloch only
 };
-
-struct ModGroup {                   // fdtd_modulation.hpp: the nodes of E component `comp` inside time-modulated media, structure of arrays
-  int comp;
-  long long n;
-  uint32_t* cell;
+struct ModGroup : ListHead {        // fdtd_modulation.hpp: the nodes of E component `comp` inside time-modulated media
   float *ca, *eps_bar, *s_bar, *old;
   float2 *d_eps, *d_s;
   double w_eps, w_sig;              // phase advance per time step (rad) of the permittivity / conductivity modulation
 };
-
-struct ConformalGroup {            // fdtd_conformal.hpp: the faces of H component `comp` cut by a PEC surface, structure of arrays
-  int comp;                         // 3..5
-  long long n;
-  uint32_t* cell;                   // [n]
+struct ConformalGroup : ListHead {  // fdtd_conformal.hpp: the faces of H component `comp` (3..5) cut by a PEC surface
   uint32_t* nbr;                    // [4][n] edge nodes, kNoNode = none
   float* d;                         // [4][n]
 };
-
-struct NonlinearGroup {            // fdtd_nonlinear.hpp: the nodes of E component `comp` inside Kerr media, structure of arrays
-  int comp;
-  long long n;
-  uint32_t* cell;                   // [n]
+struct NonlinearGroup : ListHead {  // fdtd_nonlinear.hpp: the nodes of E component `comp` inside Kerr media
   uint32_t* nbr;                    // [8][n] the four E_b and the four E_c nodes around each node, kNoNode = none
   float *den0, *chi3;               // [n] eps_bar + s_bar, chi3
   float *old, *i_old, *lin, *next;  // [n] E^n, I^n, E_lin, the iterate being formed
 };
+// One row per kind, in the order the step-pair off-reason names them; every kind keeps single steps and one GPU.  `early`: fdtd_add_*
+// and fdtd_comm_init refuse the kind on z-slabs already — the fully anisotropic lists are refused by Run::setup / BlochRun::setup
+// only (on record, not by design).  `bloch_lists`: what a Bloch pair's error calls the lists both handles must carry alike (linear
+// updates with real coefficients: each part is patched by its own); nullptr = refused with Bloch boundaries (Kerr: not linear).
+enum ListKind { kAniso, kModulation, kConformal, kNonlinear, kListKinds };
+constexpr struct { const char* noun; int f2_off; bool early; const char* bloch_lists; } kListKind[kListKinds] = {
+    {"fully anisotropic media", FDTD_F2_OFF_ADE, false, "fully anisotropic lists"},
+    {"time-modulated media", FDTD_F2_OFF_MODULATION, true, "time-modulation lists"},
+    {"PEC-conformal boundaries", FDTD_F2_OFF_CONFORMAL, true, "PEC-conformal lists"},
+    {"nonlinear media", FDTD_F2_OFF_NONLINEAR, true, nullptr}};
 
 struct PointSrc {
   long long n_e = 0, n_h = 0;      // points split by E / H components
@@ -422,6 +421,43 @@ int refuse_whole_grid_monitors(FdtdSolver* err, const FdtdSolver* h, const char*
       return fail(err, "%s: flux-time, sparse field-time and sparse DFT monitors%s", who,
                   bloch ? " (fdtd_add_flux_time_monitor, fdtd_add_field_time_monitor, fdtd_add_field_dft_monitor) are not available with Bloch boundaries (complex fields)"
                         : " are not available on z-slab handles");
+  return 0;
+}
+
+// ---- the whole-grid node lists of a handle (kListKind): how many of a kind, and list k < n_lists of them --------------------------
+size_t n_lists(const FdtdSolver* h, int kind) {
+  const size_t n[kListKinds] = {h->aniso.size(), h->modulation.size(), h->conformal.size(), h->nonlinear.size()};
+  return n[kind];
+}
+const ListHead& list_at(const FdtdSolver* h, int kind, size_t k) {
+  if (kind == kAniso) return h->aniso[k];
+  if (kind == kModulation) return h->modulation[k];
+  return kind == kConformal ? (const ListHead&)h->conformal[k] : h->nonlinear[k];
+}
+// the first kind the handle holds, kListKinds = none: step pairs, tb_pair's slabs and captured graphs are for handles without lists
+// (a graph bakes its kernel arguments, and the modulation's phases are arguments that change every step)
+int first_list_kind(const FdtdSolver* h) { int k = 0; while (k < kListKinds && !n_lists(h, k)) ++k; return k; }
+bool has_lists(const FdtdSolver* h) { return first_list_kind(h) < kListKinds; }
+// z-slabs refuse the lists `h` holds (the error goes to `err`).  `early`: asked by fdtd_add_* / fdtd_comm_init — the kinds whose row
+// says so; `adding`: the kind fdtd_add_* is about to add to `h`, refused where h is a z-slab handle by its faces or its communicator
+int refuse_lists_on_z_slabs(FdtdSolver* err, const FdtdSolver* h, const char* who, bool early = false, int adding = kListKinds) {
+  if (adding < kListKinds && !h->comm && h->cfg.bc[4] != FDTD_BC_NEIGHBOR && h->cfg.bc[5] != FDTD_BC_NEIGHBOR) return 0;
+  for (int kind = 0; kind < kListKinds; ++kind)
+    if ((kind == adding || n_lists(h, kind)) && (kListKind[kind].early || !early))
+      return fail(err, "%s: %s are not available on z-slabs", who, kListKind[kind].noun);
+  return 0;
+}
+// the two handles of a Bloch pair: the same lists (component and length, list by list), or none of a kind that Bloch boundaries refuse
+int check_bloch_lists(FdtdSolver* hr, const FdtdSolver* hi) {
+  for (int kind = 0; kind < kListKinds; ++kind) {
+    const char* name = kListKind[kind].bloch_lists;
+    if (!name && (n_lists(hr, kind) || n_lists(hi, kind)))
+      return fail(hr, "fdtd_run_bloch: %s are not available with Bloch boundaries", kListKind[kind].noun);
+    bool same = n_lists(hr, kind) == n_lists(hi, kind);
+    for (size_t k = 0; same && k < n_lists(hr, kind); ++k)
+      same = list_at(hr, kind, k).comp == list_at(hi, kind, k).comp && list_at(hr, kind, k).n == list_at(hi, kind, k).n;
+    if (!same) return fail(hr, "fdtd_run_bloch: the two solvers must carry the same %s", name);
+  }
   return 0;
 }
 
@@ -1034,10 +1070,7 @@ int fused2_why_not(const FdtdSolver* h, bool slab_rank = false, bool shell = fal
   // (a shell pair: the planes that hold dispersive cells are a z hole of the bulk; round 6: the pair advances them itself once
   //  their memory terms are paged, disp_setup)
   if (!h->ade.empty() && !shell && h->disp.state != 1) return FDTD_F2_OFF_ADE;
-  if (!h->aniso.empty()) return FDTD_F2_OFF_ADE;               // fully anisotropic bodies: their coupling follows every single step
-  if (!h->modulation.empty()) return FDTD_F2_OFF_MODULATION;   // time-modulated media: their list kernels follow every single step
-  if (!h->conformal.empty()) return FDTD_F2_OFF_CONFORMAL;     // PEC-conformal boundaries: their list kernel runs in front of every single step
-  if (!h->nonlinear.empty()) return FDTD_F2_OFF_NONLINEAR;     // Kerr media: their fixed-point iterations follow every single step
+  if (has_lists(h)) return kListKind[first_list_kind(h)].f2_off;   // whole-grid lists: their kernels go around every single step
   // (sources are judged step by step, fused2_sources_why_not: a TFSF box or a mode plane keeps single steps only while it injects)
   // PEC walls; the min faces may be PMC (the symmetry planes of a half / quarter / eighth domain)
   // (a z-slab rank: a neighbour face is no wall — the sweep stays two planes clear of it, fdtd_run)
@@ -2637,11 +2670,14 @@ void launch_ade(FdtdSolver* h, int kbeg, int kend, hipStream_t st, const FieldP*
 // `axes`: the CPML axes that run as slab kernels (7 & ~ the axes inside the sweep); `replica`: the comm stream's copy of the TFSF
 // incident grids.  What stays with the caller, because its place differs between the schedules: fill_mirror, aniso_save /
 // modulation_save / nonlinear_save, advance_tfsf_aux, the ghost fills, record_monitors.
+// WHOLE-GRID LISTS (kListKind: the fully anisotropic, modulation, PEC-conformal and Kerr lists) are not sorted by plane, so a launch
+// covers all their nodes or none: only a call that covers every plane applies them — h_side_terms with [0, nz), e_side_terms with
+// `whole_grid` (Run::fused_one, Run::two_pass_step and BlochRun::step on one GPU).  A caller that works on a plane range (tb_pair's
+// slabs, e_post and the cs / st halves of a z-slab rank) launches nothing for them: exactly the schedules whose set-up refuses the
+// lists — refuse_lists_on_z_slabs (fdtd_add_*, fdtd_comm_init, Run::setup, BlochRun::setup) — or is not chosen with them: has_lists.
 // H side, in FRONT of the update of step n, planes [k0, k1): absorber damping of H^{n-1/2}, then H-side sources / TFSF corrections
 // (they only read E^n), then the CPML slabs — the summation order of the fused sweep — then the PEC-conformal correction of the cut
-// faces (it reads E^n alone as well).  The conformal lists are whole-grid lists like the anisotropic and modulation ones: they are
-// applied only by a call that covers every plane (Run::fused_one, the H pass of Run::two_pass_step on one GPU, BlochRun::step); the
-// schedules that work on plane ranges refuse them (Run::setup, Run::setup_schedules, BlochRun::setup).
+// faces (it reads E^n alone as well).
 void h_side_terms(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, int axes = 7, bool replica = false) {
   launch_damp(h, false, k0, k1, st);
   launch_sources(h, false, n, k0, k1, st, replica);
@@ -2657,9 +2693,7 @@ void e_side_head(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, int
 // the E phase: E_lin of the listed nodes is complete), then the Kerr media's fixed-point iterations (they read E_lin of all three
 // components; a handle carries either kind of list, not both).  Between the two, the fully anisotropic coupling: aniso_apply, or
 // aniso_apply_bloch where it reads both parts of a Bloch pair (BlochRun::step cuts in there).
-// `whole_grid`: the call covers every plane of the grid.  The anisotropic and modulation lists are whole-grid lists, not plane-ranged:
-// they are applied only then.  A caller that works on a plane range (tb_pair's slabs, the cs / st halves of a z-slab rank) passes
-// false — exactly the schedules whose set-up refuses those lists (Run::setup, Run::setup_schedules, BlochRun::setup say where).
+// `whole_grid`: the call covers every plane of the grid (above).
 void e_side_tail(FdtdSolver* h, long long n, int k0, int k1, hipStream_t st, bool whole_grid) {
   launch_damp(h, true, k0, k1, st);
   launch_ade(h, k0, k1, st);
@@ -2693,6 +2727,7 @@ int disp_setup(FdtdSolver* h) {
   if (D.state != 0) return 0;
   D.state = -1;
   const GridP& g = h->g;
+  // (three kinds, not has_lists: Run::setup_pairs asks here whatever lists there are, and a handle with conformal lists has paged so far)
   if (h->ade.empty() || h->disp_on == 0 || !h->mat4 || h->mat4b || h->comm || !h->aniso.empty() || !h->modulation.empty() || !h->nonlinear.empty() || g.nx % 4 != 0) return 0;
   for (const AdeGroup& a : h->ade) if (!a.strict) return 0;
   const int nbx = (g.nx + 255) / 256;
@@ -3555,15 +3590,20 @@ int fdtd_add_ade(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_index,
 
 extern "C++" {
 namespace {
+// the fdtd_add_* of the whole-grid lists: every listed node, and every neighbour slot that is not kNoNode, is a cell of the grid
+int check_list_nodes(FdtdSolver* h, const char* who, const uint32_t* cell, int64_t n, const uint32_t* nbr = nullptr, int slots = 0) {
+  const uint64_t ncell = (uint64_t)n_cells(h);
+  for (int64_t i = 0; i < n; ++i) if (cell[i] >= ncell) return fail(h, "%s: cell index out of range", who);
+  for (int64_t q = 0; q < slots * n; ++q)
+    if (nbr[q] != kNoNode && nbr[q] >= ncell) return fail(h, "%s: neighbour index out of range", who);
+  return 0;
+}
 int add_aniso(FdtdSolver* h, const char* who, int comp, int64_t n, const uint32_t* cell_index, const uint32_t* nbr_index,
               const float* w_new, const float* w_old, const uint8_t* wrap) {
   if (!h) return -1;
   if (comp < 0 || comp > 2) return fail(h, "%s: comp must be 0..2", who);
   if (n <= 0) return 0;
-  const uint64_t ncell = (uint64_t)n_cells(h);
-  for (int64_t i = 0; i < n; ++i) if (cell_index[i] >= ncell) return fail(h, "%s: cell index out of range", who);
-  for (int64_t q = 0; q < 8 * n; ++q)
-    if (nbr_index[q] != kNoNode && nbr_index[q] >= ncell) return fail(h, "%s: neighbour index out of range", who);
+  if (check_list_nodes(h, who, cell_index, n, nbr_index, 8)) return -1;
   if (wrap)
     for (int64_t q = 0; q < 8 * n; ++q) {
       const int c = wrap[q];
@@ -3600,14 +3640,11 @@ int fdtd_add_modulation(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell
   if (!h) return -1;
   if (comp < 0 || comp > 2) return fail(h, "fdtd_add_modulation: comp must be 0..2");
   if (n <= 0) return 0;
-  if (h->comm) return fail(h, "fdtd_add_modulation: time-modulated media are not available on z-slabs");
-  for (int f = 4; f < 6; ++f)
-    if (h->cfg.bc[f] == FDTD_BC_NEIGHBOR) return fail(h, "fdtd_add_modulation: time-modulated media are not available on z-slabs");
-  if (!h->nonlinear.empty()) return fail(h, "fdtd_add_modulation: time-modulated media are not available together with nonlinear media");
+  if (refuse_lists_on_z_slabs(h, h, "fdtd_add_modulation", true, kModulation)) return -1;
+  if (n_lists(h, kNonlinear)) return fail(h, "fdtd_add_modulation: time-modulated media are not available together with nonlinear media");
   if (!std::isfinite(omega_eps) || !std::isfinite(omega_sigma)) return fail(h, "fdtd_add_modulation: omega must be finite");
-  const uint64_t ncell = (uint64_t)n_cells(h);
+  if (check_list_nodes(h, "fdtd_add_modulation", cell_index, n)) return -1;
   for (int64_t i = 0; i < n; ++i) {
-    if (cell_index[i] >= ncell) return fail(h, "fdtd_add_modulation: cell index out of range");
     // (the kernel divides by eps^{n+1} + s: the largest swing of both must leave it positive)
     const double swing = std::hypot((double)d_eps[2 * i], (double)d_eps[2 * i + 1]) + std::hypot((double)d_s[2 * i], (double)d_s[2 * i + 1]);
     if (!((double)eps_bar[i] + (double)s_bar[i] - swing > 0.0))
@@ -3631,18 +3668,12 @@ int fdtd_add_pec_conformal(FdtdSolver* h, int comp, int64_t n, const uint32_t* c
   if (!h) return -1;
   if (comp < 3 || comp > 5) return fail(h, "fdtd_add_pec_conformal: comp must be 3..5");
   if (n <= 0) return 0;
-  if (h->comm) return fail(h, "fdtd_add_pec_conformal: PEC-conformal boundaries are not available on z-slabs");
-  for (int f = 4; f < 6; ++f)
-    if (h->cfg.bc[f] == FDTD_BC_NEIGHBOR) return fail(h, "fdtd_add_pec_conformal: PEC-conformal boundaries are not available on z-slabs");
+  if (refuse_lists_on_z_slabs(h, h, "fdtd_add_pec_conformal", true, kConformal)) return -1;
   for (const ConformalGroup& c : h->conformal)
     if (c.comp == comp) return fail(h, "fdtd_add_pec_conformal: component %d has a list already (a face is listed once)", comp);
-  const uint64_t ncell = (uint64_t)n_cells(h);
-  for (int64_t i = 0; i < n; ++i)
-    if (cell_index[i] >= ncell) return fail(h, "fdtd_add_pec_conformal: cell index out of range");
-  for (int64_t q = 0; q < 4 * n; ++q) {
-    if (nbr_index[q] != kNoNode && nbr_index[q] >= ncell) return fail(h, "fdtd_add_pec_conformal: neighbour index out of range");
+  if (check_list_nodes(h, "fdtd_add_pec_conformal", cell_index, n, nbr_index, 4)) return -1;
+  for (int64_t q = 0; q < 4 * n; ++q)
     if (!std::isfinite(d[q])) return fail(h, "fdtd_add_pec_conformal: weight %lld is not finite", (long long)q);
-  }
   HIPCHK(h, hipSetDevice(h->cfg.device));
   ConformalGroup c{};
   c.comp = comp; c.n = n;
@@ -3659,18 +3690,15 @@ int fdtd_add_nonlinear(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_
   if (comp < 0 || comp > 2) return fail(h, "fdtd_add_nonlinear: comp must be 0..2");
   if (num_iters < 1 || num_iters > 64) return fail(h, "fdtd_add_nonlinear: num_iters must be 1..64");
   if (n <= 0) return 0;
-  if (h->comm) return fail(h, "fdtd_add_nonlinear: nonlinear media are not available on z-slabs");
-  for (int f = 4; f < 6; ++f)
-    if (h->cfg.bc[f] == FDTD_BC_NEIGHBOR) return fail(h, "fdtd_add_nonlinear: nonlinear media are not available on z-slabs");
-  if (!h->modulation.empty()) return fail(h, "fdtd_add_nonlinear: nonlinear media are not available together with time-modulated media");
+  if (refuse_lists_on_z_slabs(h, h, "fdtd_add_nonlinear", true, kNonlinear)) return -1;
+  if (n_lists(h, kModulation)) return fail(h, "fdtd_add_nonlinear: nonlinear media are not available together with time-modulated media");
   for (const NonlinearGroup& g : h->nonlinear)
     if (g.comp == comp) return fail(h, "fdtd_add_nonlinear: component %d has a list already (a node is listed once)", comp);
-  if (!h->nonlinear.empty() && h->nonlinear_iters != num_iters)
+  if (n_lists(h, kNonlinear) && h->nonlinear_iters != num_iters)
     return fail(h, "fdtd_add_nonlinear: num_iters = %d, the handle's lists have %d (one value per handle)", num_iters, h->nonlinear_iters);
-  const uint64_t ncell = (uint64_t)n_cells(h);
+  if (check_list_nodes(h, "fdtd_add_nonlinear", cell_index, n, nbr_index, 8)) return -1;
   std::vector<float> den0((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
-    if (cell_index[i] >= ncell) return fail(h, "fdtd_add_nonlinear: cell index out of range");
     if (!std::isfinite(chi3[i])) return fail(h, "fdtd_add_nonlinear: node %lld: chi3 is not finite", (long long)i);
     den0[(size_t)i] = eps_bar[i] + s_bar[i];
     if (!(den0[(size_t)i] > 0.0f)) return fail(h, "fdtd_add_nonlinear: node %lld: eps_bar + s_bar = %g is not positive", (long long)i, (double)den0[(size_t)i]);
@@ -3679,8 +3707,6 @@ int fdtd_add_nonlinear(FdtdSolver* h, int comp, int64_t n, const uint32_t* cell_
     if (!(std::fabs(ca_of - (double)ca[i]) <= 1e-5))
       return fail(h, "fdtd_add_nonlinear: node %lld: ca = %g is not (eps_bar - s_bar) / (eps_bar + s_bar) = %g", (long long)i, (double)ca[i], ca_of);
   }
-  for (int64_t q = 0; q < 8 * n; ++q)
-    if (nbr_index[q] != kNoNode && nbr_index[q] >= ncell) return fail(h, "fdtd_add_nonlinear: neighbour index out of range");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   NonlinearGroup g{};
   g.comp = comp; g.n = n;
@@ -4131,9 +4157,7 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   ncclUniqueId u;
   std::memcpy(&u, id, 128);
   if (refuse_whole_grid_monitors(h, h, "fdtd_comm_init")) return -1;
-  if (!h->modulation.empty()) return fail(h, "fdtd_comm_init: time-modulated media are not available on z-slabs");
-  if (!h->conformal.empty()) return fail(h, "fdtd_comm_init: PEC-conformal boundaries are not available on z-slabs");
-  if (!h->nonlinear.empty()) return fail(h, "fdtd_comm_init: nonlinear media are not available on z-slabs");
+  if (refuse_lists_on_z_slabs(h, h, "fdtd_comm_init", true)) return -1;
   NCCLCHK(h, ncclCommInitRank(&h->comm, n_ranks, u, rank));
   h->rank = rank; h->n_ranks = n_ranks;
   // what the communicator itself reports goes into FdtdStats (bench.py --gpus N prints it: proof that RCCL saw N ranks)

@@ -190,12 +190,7 @@ struct Run {
     multi = h->comm != nullptr;     // also true for a 1-rank communicator (self exchange)
     nb_lo = h->cfg.bc[4] == FDTD_BC_NEIGHBOR, nb_hi = h->cfg.bc[5] == FDTD_BC_NEIGHBOR;
     if ((nb_lo || nb_hi) && !multi) return fail(h, "fdtd_run: neighbour faces need fdtd_comm_init");
-    // (these two refusals are what every plane-range call of e_side_terms on a z-slab rank relies on — e_post, the cs / st halves of
-    //  two_pass_step pass "not the whole grid", and the whole-grid lists are empty there)
-    if (multi && !h->aniso.empty()) return fail(h, "fdtd_run: fully anisotropic media are not available on z-slabs");
-    if (multi && !h->modulation.empty()) return fail(h, "fdtd_run: time-modulated media are not available on z-slabs");
-    if (multi && !h->conformal.empty()) return fail(h, "fdtd_run: PEC-conformal boundaries are not available on z-slabs");
-    if (multi && !h->nonlinear.empty()) return fail(h, "fdtd_run: nonlinear media are not available on z-slabs");
+    if (multi && refuse_lists_on_z_slabs(h, h, "fdtd_run")) return -1;      // (whole-grid lists: h_side_terms, fdtd_capi.hip)
     // (PMC on a plus face of a z-slab rank: x / y walls are local to every plane; a z wall belongs to the rank without an upper
     //  neighbour, whose interior launch must hold the wall's two image planes and the two they mirror)
     // (six planes: the boundary chunk next to the lower neighbour is one plane thick below eight planes, two from there on)
@@ -324,11 +319,9 @@ struct Run {
     // pairs in which no monitor records and no field-decay check falls on the middle step.
     tb_req = h->tblock < 0 ? 0 : (h->tblock % 4096);
     tb_two_streams = h->tblock > 4096 && h->stream_overlap == 1;
-    // (tb_pair's slabs are plane ranges: its e_side_terms pass "not the whole grid" — hence no fully anisotropic and no modulation lists
-    //  here; and no CPML: the launch_pml inside h_side_terms / e_side_terms launches nothing on this schedule)
+    // (tb_pair's slabs are plane ranges: no whole-grid lists, h_side_terms in fdtd_capi.hip; no CPML: launch_pml launches nothing here)
     tb_ok = fused && tb_req > 0 && !any_pml(h) && h->tfsf.empty() && h->cfg.bc[4] != FDTD_BC_PERIODIC &&
-                       h->mirror_wall[0] < 0 && h->mirror_wall[1] < 0 && h->mirror_wall[2] < 0 && h->aniso.empty() &&
-                       h->modulation.empty() && h->conformal.empty() && h->nonlinear.empty() && nz >= 2 * tb_req;
+                       h->mirror_wall[0] < 0 && h->mirror_wall[1] < 0 && h->mirror_wall[2] < 0 && !has_lists(h) && nz >= 2 * tb_req;
     h->two_step_pairs = 0;
     h->tblock_used = tb_ok ? tb_req : 0;
     // ---- captured step pairs (hipGraph) ------------------------------------------------------------------------------
@@ -340,10 +333,7 @@ struct Run {
     // with the three-launch CPML split of large grids, not on z-slabs, not with per-launch timing events.
     split_now = (h->pml_split < 0 ? n_cells(h) >= (1LL << 24) : h->pml_split != 0) && any_pml(h) &&
                            (((h->pml_fused < 0 ? 7 : h->pml_fused) & pml_in_sweep_mask(h)) & 6) != 0;
-    graph_ok = fused && !tb_ok && !split_now && !(h->cfg.flags & FDTD_FLAG_TIME_KERNELS) && h->aniso.empty() &&
-                    h->conformal.empty() &&       // (conformal lists: single steps only, as the modulation lists)
-                    h->nonlinear.empty() &&       // (Kerr lists likewise)
-                    h->modulation.empty() &&      // (a graph bakes its kernel arguments: the modulation's phases change every step)
+    graph_ok = fused && !tb_ok && !split_now && !(h->cfg.flags & FDTD_FLAG_TIME_KERNELS) && !has_lists(h) &&    // (first_list_kind says why)
                     h->use_graph > 0;      // on request only: measured on ROCm 7.2 (profiles/r3i) a replayed pair is ~3 us per step
                                            // SLOWER than launching its kernels (64^3 17.6 -> 20.8, 128^3 28.8 -> 31.4, 200^3 81.5 -> 84.0)
     h->graph_pairs = 0;

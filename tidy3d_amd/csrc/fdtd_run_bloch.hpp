@@ -11,13 +11,6 @@
 // One `BlochRun` object per call, in the shape of Run: setup, step (one single step of both parts; the order of its correction
 // launches is h_side_terms / e_side_terms, fdtd_capi.hip), decay_check, finish.  Everything is issued on ONE stream, st.
 
-// both handles of a Bloch pair carry the same lists (component and length, list by list)
-template <typename G>
-bool same_lists(const std::vector<G>& a, const std::vector<G>& b) {
-  if (a.size() != b.size()) return false;
-  for (size_t k = 0; k < a.size(); ++k) if (a[k].comp != b[k].comp || a[k].n != b[k].n) return false;
-  return true;
-}
 struct BlochRun {
   FdtdSolver *hr, *hi;
   int64_t n_steps;
@@ -40,9 +33,9 @@ struct BlochRun {
   int setup() {
     for (const FdtdSolver* hh : {hr, hi}) if (refuse_whole_grid_monitors(hr, hh, "fdtd_run_bloch", true)) return -1;
     if (hi->comm) return fail(hr, "fdtd_run_bloch: the communicator of a z-slab belongs to the first (real-part) handle");
-    // fully anisotropic bodies: the Re handle's lists (wrap codes included) drive both parts; the Im handle's carry the same rows
-    aniso = !hr->aniso.empty();
-    if (!same_lists(hr->aniso, hi->aniso)) return fail(hr, "fdtd_run_bloch: the two solvers must carry the same fully anisotropic lists");
+    // whole-grid lists (kListKind): the same on both handles or refused; the Re handle's anisotropic lists (wrap codes included) drive both parts
+    if (check_bloch_lists(hr, hi)) return -1;
+    aniso = n_lists(hr, kAniso) > 0;
     for (int a = 0; a < 3; ++a)
       if (hr->mirror_wall[a] >= 0 || hi->mirror_wall[a] >= 0) return fail(hr, "fdtd_run_bloch: PMC on a plus face is not available together with Bloch boundaries");
     // z-slab decomposition (hr->comm): both parts exchange their ghost planes through the real-part handle's
@@ -51,16 +44,7 @@ struct BlochRun {
     multi = hr->comm != nullptr;
     nb_lo = hr->cfg.bc[4] == FDTD_BC_NEIGHBOR, nb_hi = hr->cfg.bc[5] == FDTD_BC_NEIGHBOR;
     if ((nb_lo || nb_hi) && !multi) return fail(hr, "fdtd_run_bloch: neighbour faces need fdtd_comm_init on the first handle");
-    // (this refusal and the one of time-modulated media below: a z-slab rank's step passes "not the whole grid" to e_side_terms)
-    if (multi && aniso) return fail(hr, "fdtd_run_bloch: fully anisotropic media are not available on z-slabs");
-    // time-modulated media: the update is linear with real coefficients — each part is patched by its own handle's lists, the same rows
-    if (!same_lists(hr->modulation, hi->modulation)) return fail(hr, "fdtd_run_bloch: the two solvers must carry the same time-modulation lists");
-    if (multi && !hr->modulation.empty()) return fail(hr, "fdtd_run_bloch: time-modulated media are not available on z-slabs");
-    // PEC-conformal boundaries: linear with real coefficients as well — each handle corrects its own part (h_side_terms)
-    if (!same_lists(hr->conformal, hi->conformal)) return fail(hr, "fdtd_run_bloch: the two solvers must carry the same PEC-conformal lists");
-    if (multi && !hr->conformal.empty()) return fail(hr, "fdtd_run_bloch: PEC-conformal boundaries are not available on z-slabs");
-    // Kerr media: the update is not linear — the Re and Im parts cannot be patched separately
-    if (!hr->nonlinear.empty() || !hi->nonlinear.empty()) return fail(hr, "fdtd_run_bloch: nonlinear media are not available with Bloch boundaries");
+    if (multi && refuse_lists_on_z_slabs(hr, hr, "fdtd_run_bloch")) return -1;
     if (hi->cfg.bc[4] != hr->cfg.bc[4] || hi->cfg.bc[5] != hr->cfg.bc[5])
       return fail(hr, "fdtd_run_bloch: the two solvers must have the same z faces");
     if (hr->g.nx != hi->g.nx || hr->g.ny != hi->g.ny || hr->g.nz != hi->g.nz || hr->cfg.device != hi->cfg.device ||

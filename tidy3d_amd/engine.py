@@ -13,8 +13,9 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import lib as L
+from .constants import EPSILON_0
 from .coeffs import damping_tables, h_coeff, inv_steps, material_table, pml_axis
-from .exceptions import SetupError, SolverLibraryError
+from .exceptions import SetupError, SolverLibraryError, Tidy3dNotImplementedError
 from .spec import BC_PERIODIC, SPARSE_KINDS, MonitorSpec, SolverSpec
 
 
@@ -325,6 +326,17 @@ _DEVICE_KINDS = {
 }
 
 
+# The whole-grid node lists (csrc/fdtd_capi.hip kListKind) by their attribute on the SolverSpec: what the refusals call the kind, its verb
+LIST_KINDS = {"aniso": ("FullyAnisotropicMedium", "is"), "modulation": ("time-modulated (modulation_spec) media", "are"),
+              "conformal": ("PECConformal", "is"), "nonlinear": ("nonlinear (nonlinear_spec) media", "are")}
+
+
+def refuse_together(kind, other, hint=""):
+    """``kind`` (a key of LIST_KINDS) together with ``other`` (another key, or a phrase) is not supported"""
+    phrase, verb = LIST_KINDS[kind]
+    raise Tidy3dNotImplementedError(f"{phrase} together with {LIST_KINDS.get(other, (other,))[0]} {verb} not supported{hint}")
+
+
 def _flat_taps(pairs):
     """(indices, weights) pairs in table order -> the int32 and float32 arrays the library takes."""
     pairs = list(pairs)
@@ -374,6 +386,7 @@ class HipEngine:
         nx, ny, nz = spec.shape
         self.z0, self.z1 = slab if slab is not None else (0, nz)
         self.nzl = self.z1 - self.z0
+        self.is_z_slab = n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz)
         if self.nzl < 1:
             raise SolverLibraryError("empty z-slab")
         self.handle = C.c_void_p()
@@ -461,6 +474,10 @@ class HipEngine:
         return all(lo <= z <= hi for z in cuts)
 
     # ------------------------------------------------------------------ setup
+    def _refuse_on_z_slabs(self, kind):
+        if self.is_z_slab:
+            raise Tidy3dNotImplementedError("%s %s not available in z-slab (multi-GPU) runs" % LIST_KINDS[kind])
+
     def _chk(self, st, what):
         return self.lib.check(st, self.handle, what)
 
@@ -477,7 +494,7 @@ class HipEngine:
             if a == 0 and pad:
                 p, q = _f32(np.append(p, [p[-1]] * pad)), _f32(np.append(q, [q[-1]] * pad))
             if a == 2:
-                if (z0, z1) != (0, nz) or self.n_ranks > 1 or self.force_comm:
+                if self.is_z_slab:
                     # a z-slab: the steps of the planes beyond its cuts come along as ghost entries (the library only knows how to
                     # wrap / replicate its own) — the neighbour's cell below, the neighbour's cell above; across a periodic z
                     # the wrap; beyond an outer wall the replica
@@ -573,10 +590,7 @@ class HipEngine:
         # coefficients of the neighbour nodes — the curl the sweep applied at node j is (E^{n+1} - Ca E^n) / Cb there
         aniso = getattr(spec, "aniso", None) or []
         if aniso:
-            if self.n_ranks > 1 or self.force_comm or (z0, z1) != (0, nz):
-                from .exceptions import Tidy3dNotImplementedError
-                raise Tidy3dNotImplementedError("FullyAnisotropicMedium is not available in z-slab (multi-GPU) runs")
-            from .constants import EPSILON_0
+            self._refuse_on_z_slabs("aniso")
             # Bloch device layout: the lists are on the user grid — every node moves by the ghost offset, a neighbour across a
             # periodic face is the real node on the far side (its own Ca / Cb), and the wrap codes carry the period crossed
             bloch = spec.bloch is not None
@@ -621,12 +635,9 @@ class HipEngine:
         # recovered from it — eps_bar = dt / (eps0 Cb) * 2 / (1 + Ca), s_bar = sigma_bar dt / (2 eps0) = eps_bar (1 - Ca) / (1 + Ca)
         modulation = getattr(spec, "modulation", None) or []
         if modulation:
-            from .exceptions import Tidy3dNotImplementedError
-            if self.n_ranks > 1 or self.force_comm or (z0, z1) != (0, nz):
-                raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media are not available in z-slab (multi-GPU) runs")
+            self._refuse_on_z_slabs("modulation")
             if aniso:
-                raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media together with FullyAnisotropicMedium are not supported")
-            from .constants import EPSILON_0
+                refuse_together("modulation", "aniso")
             off = np.asarray(self.ghost, np.int64)          # (Bloch device layout: every node moves by the ghost offset)
             ca32, cb32 = np.asarray(ca, np.float64), np.asarray(cb, np.float64)     # the float32 table, as the sweep reads it
             for ms in modulation:
@@ -649,11 +660,9 @@ class HipEngine:
         # PEC-conformal boundaries (spec.ConformalSet): the cut faces per H component, edges and weights as [4][n]
         conformal = getattr(spec, "conformal", None) or []
         if conformal:
-            from .exceptions import Tidy3dNotImplementedError
-            if self.n_ranks > 1 or self.force_comm or (z0, z1) != (0, nz):
-                raise Tidy3dNotImplementedError("PECConformal is not available in z-slab (multi-GPU) runs")
+            self._refuse_on_z_slabs("conformal")
             if spec.bloch is not None:
-                raise Tidy3dNotImplementedError("PECConformal together with Bloch boundaries is not supported")
+                refuse_together("conformal", "Bloch boundaries")
             for cs in conformal:
                 n = len(cs.ijk)
                 if n == 0:
@@ -670,14 +679,9 @@ class HipEngine:
         self.n_nonlinear_nodes = 0
         nonlinear = getattr(spec, "nonlinear", None) or []
         if nonlinear:
-            from .exceptions import Tidy3dNotImplementedError
-            if aniso:
-                raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with FullyAnisotropicMedium are not supported")
-            if modulation:
-                raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with time-modulated (modulation_spec) media "
-                                                "are not supported")
-            if conformal:
-                raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with PECConformal are not supported")
+            for other, sets in (("aniso", aniso), ("modulation", modulation), ("conformal", conformal)):
+                if sets:
+                    refuse_together("nonlinear", other)
             self.add_nonlinear(nonlinear)
         # sources
         from .spec import BC_PEC
@@ -744,7 +748,7 @@ class HipEngine:
             hi = np.asarray([m.hi[0], m.hi[1], hi2 - z0], dtype=np.int32)
             steps = np.ascontiguousarray(m.steps, dtype=np.int64)
             if m.kind in _DEVICE_KINDS:
-                if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz) or spec.bloch is not None:
+                if self.is_z_slab or spec.bloch is not None:
                     raise SolverLibraryError(f"monitor '{m.name}': a {_DEVICE_KINDS[m.kind][0]} on the device is not available on z-slabs "
                                              "(more than one GPU, force_comm) or with Bloch boundaries")
                 if m.kind == "flux_time":
@@ -836,14 +840,11 @@ class HipEngine:
         table coefficient the sweep applies there, the static medium recovered from it as for the modulation lists — eps_bar = dt /
         (eps0 Cb) * 2 / (1 + Ca), s_bar = eps_bar (1 - Ca) / (1 + Ca) — chi3, and the eight neighbour slots as [8][n].  May be called
         between runs: the next step forms I^n from the fields it finds."""
-        from .constants import EPSILON_0
-        from .exceptions import Tidy3dNotImplementedError
         spec, d, h = self.spec, self.lib.dll, self.handle
-        _, ny, nz = spec.shape
-        if self.n_ranks > 1 or self.force_comm or (self.z0, self.z1) != (0, nz):
-            raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media are not available in z-slab (multi-GPU) runs")
+        ny = spec.shape[1]
+        self._refuse_on_z_slabs("nonlinear")
         if spec.bloch is not None:
-            raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with Bloch boundaries are not supported")
+            refuse_together("nonlinear", "Bloch boundaries")
         nx = self.nxp                       # row length on the device
         sxy = nx * ny
         ca32, cb32 = self._table32

@@ -132,16 +132,14 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     paths = DevicePaths(flux_time_device, field_time_device, field_dft_device, projection_device)
     if devices is not None and len(devices) > 1:
         _device_refusals(sim, paths, "devices= with more than one GPU")
-        if any(isinstance(m, td.Medium) and m.is_time_modulated for m in sim.mediums):
-            raise Tidy3dNotImplementedError("time-modulated (modulation_spec) media together with devices= with more than one GPU are "
-                                            "not supported")
         from .conformal import pec_conformal_of
-        if pec_conformal_of(sim) is not None:
-            raise Tidy3dNotImplementedError("PECConformal together with devices= with more than one GPU is not supported "
-                                            "(SubpixelSpec(pec=Staircasing()) is)")
-        if any(isinstance(m, td.Medium) and m.is_nonlinear for m in sim.mediums):
-            raise Tidy3dNotImplementedError("nonlinear (nonlinear_spec) media together with devices= with more than one GPU are not "
-                                            "supported")
+        from .engine import refuse_together
+        media = [m for m in sim.mediums if isinstance(m, td.Medium)]
+        for kind, there, hint in (("modulation", any(m.is_time_modulated for m in media), ""),
+                                  ("conformal", pec_conformal_of(sim) is not None, " (SubpixelSpec(pec=Staircasing()) is)"),
+                                  ("nonlinear", any(m.is_nonlinear for m in media), "")):
+            if there:     # (the whole-grid node lists the engine would refuse on its z-slabs, named before any worker starts)
+                refuse_together(kind, "devices= with more than one GPU", hint)
         sim_data = _run_on_devices(sim, [int(d) for d in devices], n_steps, verbose,
                                    dict(_dist_options or {}, exact_projection_device=exact_projection_device))
         want_td = was_tidy3d if return_tidy3d is None else return_tidy3d
