@@ -16,7 +16,7 @@ from . import lib as L
 from .constants import EPSILON_0
 from .coeffs import damping_tables, h_coeff, inv_steps, material_table, pml_axis
 from .exceptions import SetupError, SolverLibraryError, Tidy3dNotImplementedError
-from .spec import BC_PERIODIC, SPARSE_KINDS, MonitorSpec, SolverSpec
+from .spec import BC_PEC, BC_PERIODIC, LIST_KINDS, SPARSE_KINDS, MonitorSpec, SolverSpec, refuse_together  # noqa: F401 (LIST_KINDS, refuse_together: also for web.py)
 
 
 def _f32(a) -> np.ndarray:
@@ -235,16 +235,13 @@ def permute_spec(spec: SolverSpec, s: int) -> SolverSpec:
                 for m in monitors]
     # sparse field-time and sparse DFT monitors: every component's per-axis tables (hence its kept-node counts) are renamed with the axes
     monitors = [m if m.kind not in SPARSE_KINDS else dataclasses.replace(m, taps=tuple(pick(t) for t in m.taps)) for m in monitors]
-    # PEC-conformal lists: faces, edges and components are renamed with the axes; a cyclic renaming keeps the slot order (a1, a2 follow c)
-    conformal = [dataclasses.replace(cs, comp=int(comp_map(cs.comp)), ijk=np.ascontiguousarray(cs.ijk[:, sig]),
-                                     nbr_comp=tuple(int(v) for v in comp_map(cs.nbr_comp)),
-                                     nbr_ijk=np.ascontiguousarray(cs.nbr_ijk[:, :, sig]))
-                 for cs in (getattr(spec, "conformal", None) or [])]
-    # Kerr lists: nodes, neighbour slots and components are renamed with the axes; a cyclic renaming keeps the slot order (b, c follow a)
-    nonlinear = [dataclasses.replace(ns, comp=int(comp_map(ns.comp)), ijk=np.ascontiguousarray(ns.ijk[:, sig]),
-                                     nbr_comp=tuple(int(v) for v in comp_map(ns.nbr_comp)),
-                                     nbr_ijk=np.ascontiguousarray(ns.nbr_ijk[:, :, sig]))
-                 for ns in (getattr(spec, "nonlinear", None) or [])]
+    def renamed(lists):
+        """node lists with neighbour slots: nodes, slots and components are renamed with the axes; a cyclic renaming keeps the slot
+        order (the PEC-conformal lists' a1, a2 follow c; the Kerr lists' b, c follow a)"""
+        return [dataclasses.replace(ls, comp=int(comp_map(ls.comp)), ijk=np.ascontiguousarray(ls.ijk[:, sig]),
+                                    nbr_comp=tuple(int(v) for v in comp_map(ls.nbr_comp)),
+                                    nbr_ijk=np.ascontiguousarray(ls.nbr_ijk[:, :, sig])) for ls in (lists or [])]
+    conformal, nonlinear = renamed(getattr(spec, "conformal", None)), renamed(getattr(spec, "nonlinear", None))
     return dataclasses.replace(
         spec, shape=pick(spec.shape), boundaries=pick(spec.boundaries), bc=pick(spec.bc), pml=pick(spec.pml),
         mat_idx=mat, sources=sources, tfsf=tfsf, monitors=monitors, conformal=conformal, nonlinear=nonlinear,
@@ -271,7 +268,6 @@ def bloch_device_spec(spec: SolverSpec):
     and monitors are shifted by the ghost offset, the ghost cells hold the background medium.  A Bloch
     z keeps its periodic faces: the z ghost planes the engine always had do the same job."""
     import dataclasses
-    from .spec import BC_PEC
     n_real = [0, 0, 0]
     bounds = [np.asarray(b, float) for b in spec.boundaries]
     bc = [tuple(b) for b in spec.bc]
@@ -324,17 +320,6 @@ _DEVICE_KINDS = {
     "dft_sparse": ("FieldMonitor accumulated", np.complex64, lambda m: (len(m.freqs), sum(int(np.prod(t)) for t in m.targets))),
     "dft_lattice": ("projection monitor accumulated on its lattice", np.complex64, lambda m: (len(m.freqs), sum(int(np.prod(t)) for t in m.targets))),
 }
-
-
-# The whole-grid node lists (csrc/fdtd_capi.hip kListKind) by their attribute on the SolverSpec: what the refusals call the kind, its verb
-LIST_KINDS = {"aniso": ("FullyAnisotropicMedium", "is"), "modulation": ("time-modulated (modulation_spec) media", "are"),
-              "conformal": ("PECConformal", "is"), "nonlinear": ("nonlinear (nonlinear_spec) media", "are")}
-
-
-def refuse_together(kind, other, hint=""):
-    """``kind`` (a key of LIST_KINDS) together with ``other`` (another key, or a phrase) is not supported"""
-    phrase, verb = LIST_KINDS[kind]
-    raise Tidy3dNotImplementedError(f"{phrase} together with {LIST_KINDS.get(other, (other,))[0]} {verb} not supported{hint}")
 
 
 def _flat_taps(pairs):
@@ -481,13 +466,53 @@ class HipEngine:
     def _chk(self, st, what):
         return self.lib.check(st, self.handle, what)
 
+    def _flat(self, ijk, off=None, z0: int = 0) -> np.ndarray:
+        """Node indices [..., 3] = (i, j, k) -> the flat uint32 index on the device: rows of ``nxp`` cells, planes of ``nxp * ny``; moved
+        by the ghost offset ``off`` first (Bloch device layout), local to a slab whose first plane is ``z0``."""
+        ijk = np.asarray(ijk, np.int64)
+        if off is not None:
+            ijk = ijk + np.asarray(off, np.int64)
+        return ((ijk[..., 2] - z0) * (self.nxp * self.spec.shape[1]) + ijk[..., 1] * self.nxp + ijk[..., 0]).astype(np.uint32)
+
+    def _nbr_table(self, nbr_ijk) -> np.ndarray:
+        """Neighbour nodes [n, slots, 3] (-1: no node) -> the [slots][n] uint32 table the library takes, 0xFFFFFFFF for no node."""
+        j = np.asarray(nbr_ijk, np.int64)
+        return np.ascontiguousarray(np.where(j[:, :, 0] >= 0, self._flat(j), np.uint32(0xFFFFFFFF)).T)
+
+    def _static_medium(self, comp: int, ijk: np.ndarray, what: str):
+        """Of the E_comp nodes ``ijk`` (on the device's layout): the table coefficient Ca the sweep applies there and the static medium
+        recovered from the float32 table, as the sweep reads it — eps_bar = dt / (eps0 Cb) * 2 / (1 + Ca), s_bar = sigma_bar dt /
+        (2 eps0) = eps_bar (1 - Ca) / (1 + Ca)."""
+        spec = self.spec
+        mi = spec.mat_idx[comp][ijk[:, 2], ijk[:, 1], ijk[:, 0]] if spec.mat_idx is not None else np.ones(len(ijk), np.int64)
+        ca_n, cb_n = self._table32[0][mi], self._table32[1][mi]
+        if not (cb_n > 0).all():
+            raise SolverLibraryError(f"a {what} node on a PEC cell")
+        eps_bar = spec.dt / (EPSILON_0 * cb_n) * 2.0 / (1.0 + ca_n)
+        return ca_n, eps_bar, eps_bar * (1.0 - ca_n) / (1.0 + ca_n)
+
     def _setup(self, spec: SolverSpec):
-        d, h = self.lib.dll, self.handle
-        nx0, ny, nz = spec.shape
-        pad = self.pad_x
-        nx = self.nxp                       # row length on the device
-        z0, z1, nzl = self.z0, self.z1, self.nzl
-        sxy = nx * ny
+        """Every library call of the set-up, in this order (``spec`` is ``self.spec``: the device's axes and layout)"""
+        self._set_steps(spec)
+        self._set_media(spec)
+        self._set_pml(spec)
+        self._set_mirror_plus(spec)
+        self._set_absorbers(spec)
+        self._add_ade(spec)
+        self._add_aniso(spec)
+        self._add_modulation(spec)
+        self._add_conformal(spec)
+        self._add_nonlinear(spec)
+        self._add_point_sources(spec)
+        self._add_tfsf(spec)
+        self.mon_ids: List[Tuple[MonitorSpec, int, Tuple[int, int]]] = []
+        self.add_monitors(spec.monitors)            # (intersected with the slab)
+        self._chk(self.lib.dll.fdtd_set_shutoff(self.handle, int(spec.decay_every), float(spec.shutoff), int(spec.decay_ref_step)),
+                  "fdtd_set_shutoff")
+
+    def _set_steps(self, spec):
+        d, h, pad = self.lib.dll, self.handle, self.pad_x
+        nz, z0, z1 = spec.shape[2], self.z0, self.z1
         ip, idl = inv_steps(spec)
         for a in range(3):
             p, q = _f32(ip[a]), _f32(idl[a])
@@ -506,18 +531,27 @@ class HipEngine:
                 else:
                     p, q = _f32(p[z0:z1]), _f32(q[z0:z1])
             self._chk(d.fdtd_set_steps(h, a, _ptr(p), _ptr(q), len(p)), "fdtd_set_steps")
+
+    def _set_media(self, spec):
+        """the material table (kept as ``mt``, and as ``_table32``: the float32 values the sweep reads) and the index volumes"""
+        d, h, pad = self.lib.dll, self.handle, self.pad_x
+        nx0, ny, _ = spec.shape
+        z0, z1 = self.z0, self.z1
         self.mt = mt = material_table(spec.media, spec.dt)
         ca, cb = _f32(mt.ca), _f32(mt.cb)
+        self._table32 = (np.asarray(ca, np.float64), np.asarray(cb, np.float64))
         self._chk(d.fdtd_set_media(h, _ptr(ca), _ptr(cb), len(ca)), "fdtd_set_media")
         if spec.mat_idx is not None or pad:
             wide = len(ca) > 256               # more than 8 bits of medium index: the 16-bit entry point
-            m = np.zeros((3, nzl, ny, nx), dtype=np.uint16 if wide else np.uint8)   # index 0 = PEC in the padding
+            m = np.zeros((3, self.nzl, ny, self.nxp), dtype=np.uint16 if wide else np.uint8)   # index 0 = PEC in the padding
             m[..., :nx0] = spec.mat_idx[:, z0:z1] if spec.mat_idx is not None else 1
             if wide:
                 self._chk(d.fdtd_set_material16(h, _ptr(m), m.size), "fdtd_set_material16")
             else:
                 self._chk(d.fdtd_set_material(h, _ptr(m), m.nbytes), "fdtd_set_material")
-        # CPML
+
+    def _set_pml(self, spec):
+        d, h, pad = self.lib.dll, self.handle, self.pad_x
         for a in range(3):
             P = pml_axis(spec, a)
             if P.n_lo + P.n_hi == 0:
@@ -529,46 +563,60 @@ class HipEngine:
                 tabs = [np.append(t, [v] * pad) for t, v in zip(tabs, ident)]
                 n_hi = n_hi + pad if n_hi else 0
             if a == 2:
-                tabs = [t[z0:z1] for t in tabs]
+                tabs = [t[self.z0:self.z1] for t in tabs]
                 n_lo, n_hi = _local_pml_counts(tabs)
                 if n_lo + n_hi == 0:
                     continue
             t32 = [_f32(t) for t in tabs]
             self._chk(d.fdtd_set_pml(h, a, n_lo, n_hi, *[_ptr(t) for t in t32], len(t32[0])),
                       "fdtd_set_pml")
-        # PMC on plus faces: the wall index of every mirrored axis (two ghost cells lie beyond it)
+
+    def _set_mirror_plus(self, spec):
+        """PMC on plus faces: the wall index of every mirrored axis (two ghost cells lie beyond it)"""
+        nz, z0, z1 = spec.shape[2], self.z0, self.z1
         mp = getattr(spec, "mirror_plus", None)
-        if mp is not None and any(w >= 0 for w in mp):
-            # (z-slab ranks: x / y walls cross every slab; a z wall and its two image planes belong to the last one)
-            # (decided from the split alone, so that every rank raises — a lone rank giving up would leave the others waiting)
-            if mp[2] >= 0 and (self.n_ranks > 1 or (z0, z1) != (0, nz)):
-                last = (self._all_slabs or split_slabs(nz, self.n_ranks))[-1]
-                if last[1] - last[0] < 6:
-                    raise SetupError("a PMC plus face along z needs a last z-slab of at least 6 planes (the wall's two image planes and "
-                                     f"the two they mirror inside its interior launch); it has {last[1] - last[0]}")
-            for a, w in enumerate(mp):
-                if w < 0 or (a == 2 and z1 != nz):
-                    continue
-                self._chk(d.fdtd_set_mirror_plus(h, a, int(w) - (z0 if a == 2 else 0)), "fdtd_set_mirror_plus")
-        # absorber layers (damping tables, slab-local along z)
+        if mp is None or not any(w >= 0 for w in mp):
+            return
+        # (z-slab ranks: x / y walls cross every slab; a z wall and its two image planes belong to the last one)
+        # (decided from the split alone, so that every rank raises — a lone rank giving up would leave the others waiting)
+        if mp[2] >= 0 and (self.n_ranks > 1 or (z0, z1) != (0, nz)):
+            last = (self._all_slabs or split_slabs(nz, self.n_ranks))[-1]
+            if last[1] - last[0] < 6:
+                raise SetupError("a PMC plus face along z needs a last z-slab of at least 6 planes (the wall's two image planes and "
+                                 f"the two they mirror inside its interior launch); it has {last[1] - last[0]}")
+        for a, w in enumerate(mp):
+            if w < 0 or (a == 2 and z1 != nz):
+                continue
+            self._chk(self.lib.dll.fdtd_set_mirror_plus(self.handle, a, int(w) - (z0 if a == 2 else 0)), "fdtd_set_mirror_plus")
+
+    def _set_absorbers(self, spec):
+        """absorber layers (damping tables, slab-local along z)"""
+        d, h, pad = self.lib.dll, self.handle, self.pad_x
+        nz, z0, z1, nzl = spec.shape[2], self.z0, self.z1, self.nzl
         dm = damping_tables(spec)
-        if dm is not None:
-            for a in range(3):
-                D = dm[a]
-                fb, fc, n_lo, n_hi = D.fb, D.fc, D.n_lo, D.n_hi
-                if a == 0 and pad:      # identity in the PEC padding; the hi layers grow to cover it
-                    fb, fc = np.append(fb, [1.0] * pad), np.append(fc, [1.0] * pad)
-                    n_hi = n_hi + pad if n_hi else 0
-                if a == 2:
-                    fb, fc = fb[z0:z1], fc[z0:z1]
-                    n_lo = int(np.clip(n_lo - z0, 0, nzl))
-                    n_hi = int(np.clip(z1 - (nz - n_hi), 0, nzl))
-                if n_lo + n_hi == 0:
-                    continue
-                fb32, fc32 = _f32(fb), _f32(fc)
-                self._chk(d.fdtd_set_absorber(h, a, n_lo, n_hi, _ptr(fb32), _ptr(fc32), len(fb32)),
-                          "fdtd_set_absorber")
-        # ADE groups
+        if dm is None:
+            return
+        for a in range(3):
+            D = dm[a]
+            fb, fc, n_lo, n_hi = D.fb, D.fc, D.n_lo, D.n_hi
+            if a == 0 and pad:      # identity in the PEC padding; the hi layers grow to cover it
+                fb, fc = np.append(fb, [1.0] * pad), np.append(fc, [1.0] * pad)
+                n_hi = n_hi + pad if n_hi else 0
+            if a == 2:
+                fb, fc = fb[z0:z1], fc[z0:z1]
+                n_lo = int(np.clip(n_lo - z0, 0, nzl))
+                n_hi = int(np.clip(z1 - (nz - n_hi), 0, nzl))
+            if n_lo + n_hi == 0:
+                continue
+            fb32, fc32 = _f32(fb), _f32(fc)
+            self._chk(d.fdtd_set_absorber(h, a, n_lo, n_hi, _ptr(fb32), _ptr(fc32), len(fb32)),
+                      "fdtd_set_absorber")
+
+    def _add_ade(self, spec):
+        """ADE groups: per E component and dispersive medium its nodes of the slab"""
+        d, h, mt = self.lib.dll, self.handle, self.mt
+        nx0, ny, _ = spec.shape
+        nx, sxy, z0, z1 = self.nxp, self.nxp * ny, self.z0, self.z1
         for c in range(3):
             for m in range(mt.n_media):
                 if not mt.is_dispersive(m):
@@ -577,7 +625,7 @@ class HipEngine:
                     kk, jj, ii = np.nonzero(spec.mat_idx[c, z0:z1] == m)
                     idx = (kk.astype(np.int64) * sxy + jj.astype(np.int64) * nx + ii).astype(np.uint32)
                 elif m == 1:
-                    kk, jj, ii = np.meshgrid(np.arange(nzl), np.arange(ny), np.arange(nx0), indexing="ij")
+                    kk, jj, ii = np.meshgrid(np.arange(self.nzl), np.arange(ny), np.arange(nx0), indexing="ij")
                     idx = (kk.astype(np.int64) * sxy + jj * nx + ii).reshape(-1).astype(np.uint32)
                 else:
                     continue
@@ -586,105 +634,107 @@ class HipEngine:
                 kap, bet = _cplx_f32(mt.kap[m]), _cplx_f32(mt.bet[m])
                 self._chk(d.fdtd_add_ade(h, c, idx.size, _ptr(idx), len(mt.kap[m]), _ptr(kap),
                                          _ptr(bet), float(mt.cc[m])), "fdtd_add_ade")
-        # fully anisotropic bodies: the off-diagonal coupling lists (spec.AnisoSet) with the weights folded with the material
-        # coefficients of the neighbour nodes — the curl the sweep applied at node j is (E^{n+1} - Ca E^n) / Cb there
+
+    def _add_aniso(self, spec):
+        """fully anisotropic bodies: the off-diagonal coupling lists (spec.AnisoSet) with the weights folded with the material
+        coefficients of the neighbour nodes — the curl the sweep applied at node j is (E^{n+1} - Ca E^n) / Cb there"""
+        d, h, mt = self.lib.dll, self.handle, self.mt
         aniso = getattr(spec, "aniso", None) or []
-        if aniso:
-            self._refuse_on_z_slabs("aniso")
-            # Bloch device layout: the lists are on the user grid — every node moves by the ghost offset, a neighbour across a
-            # periodic face is the real node on the far side (its own Ca / Cb), and the wrap codes carry the period crossed
-            bloch = spec.bloch is not None
-            off = np.asarray(self.ghost, np.int64)
-            for st_ in aniso:
-                n = len(st_.ijk)
-                ijk = st_.ijk + off[None, :]
-                cells = (ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32)
-                nbr = np.full((n, 8), 0xFFFFFFFF, np.uint32)
-                w_new = np.zeros((n, 8), np.float64)
-                w_old = np.zeros((n, 8), np.float64)
-                if bloch:
-                    if st_.nbr_wrap is None:
-                        raise SolverLibraryError("fully anisotropic lists without wrap signs cannot run with Bloch boundaries")
-                    s_ = np.asarray(st_.nbr_wrap, np.int64)
-                    wrap = ((s_ == 1) * 1 + (s_ == -1) * 2) @ np.array([1, 4, 16], np.int64)
-                    wrap = np.ascontiguousarray(wrap.astype(np.uint8).reshape(-1))
-                for slot in range(8):
-                    b = st_.nbr_comp[slot]
-                    j = st_.nbr_ijk[:, slot]
-                    ok = j[:, 0] >= 0
-                    j = j + off[None, :]
-                    if spec.mat_idx is not None:
-                        mi = spec.mat_idx[b][j[ok, 2], j[ok, 1], j[ok, 0]]
-                        ca_b, cb_b = np.asarray(mt.ca)[mi], np.asarray(mt.cb)[mi]
-                    else:
-                        ca_b, cb_b = np.full(int(ok.sum()), mt.ca[1]), np.full(int(ok.sum()), mt.cb[1])
-                    live = cb_b != 0
-                    wn = np.where(live, (spec.dt / EPSILON_0) * st_.g[ok, slot] / np.where(live, cb_b, 1.0), 0.0)
-                    idx = (j[ok, 2] * sxy + j[ok, 1] * nx + j[ok, 0]).astype(np.uint32)
-                    nbr[ok, slot] = np.where(wn != 0, idx, 0xFFFFFFFF)
-                    w_new[ok, slot] = wn
-                    w_old[ok, slot] = wn * ca_b
-                c32, n32 = np.ascontiguousarray(cells), np.ascontiguousarray(nbr.reshape(-1))
-                wn32, wo32 = _f32(w_new.reshape(-1)), _f32(w_old.reshape(-1))
-                if bloch:
-                    self._chk(d.fdtd_add_aniso_bloch(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32), _ptr(wrap)),
-                              "fdtd_add_aniso_bloch")
+        if not aniso:
+            return
+        self._refuse_on_z_slabs("aniso")
+        # Bloch device layout: the lists are on the user grid — every node moves by the ghost offset, a neighbour across a
+        # periodic face is the real node on the far side (its own Ca / Cb), and the wrap codes carry the period crossed
+        bloch = spec.bloch is not None
+        off = np.asarray(self.ghost, np.int64)
+        for st_ in aniso:
+            n = len(st_.ijk)
+            cells = self._flat(st_.ijk, off)
+            nbr = np.full((n, 8), 0xFFFFFFFF, np.uint32)        # [n][8], and no slot for a weight of 0: not the layout of _nbr_table
+            w_new = np.zeros((n, 8), np.float64)
+            w_old = np.zeros((n, 8), np.float64)
+            if bloch:
+                if st_.nbr_wrap is None:
+                    raise SolverLibraryError("fully anisotropic lists without wrap signs cannot run with Bloch boundaries")
+                s_ = np.asarray(st_.nbr_wrap, np.int64)
+                wrap = ((s_ == 1) * 1 + (s_ == -1) * 2) @ np.array([1, 4, 16], np.int64)
+                wrap = np.ascontiguousarray(wrap.astype(np.uint8).reshape(-1))
+            for slot in range(8):
+                b = st_.nbr_comp[slot]
+                j = st_.nbr_ijk[:, slot]
+                ok = j[:, 0] >= 0
+                j = j + off[None, :]
+                if spec.mat_idx is not None:
+                    mi = spec.mat_idx[b][j[ok, 2], j[ok, 1], j[ok, 0]]
+                    ca_b, cb_b = np.asarray(mt.ca)[mi], np.asarray(mt.cb)[mi]
                 else:
-                    self._chk(d.fdtd_add_aniso(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32)), "fdtd_add_aniso")
-        # time-modulated media (spec.ModulationSet): per node the table coefficient the sweep applies there and the static medium
-        # recovered from it — eps_bar = dt / (eps0 Cb) * 2 / (1 + Ca), s_bar = sigma_bar dt / (2 eps0) = eps_bar (1 - Ca) / (1 + Ca)
+                    ca_b, cb_b = np.full(int(ok.sum()), mt.ca[1]), np.full(int(ok.sum()), mt.cb[1])
+                live = cb_b != 0
+                wn = np.where(live, (spec.dt / EPSILON_0) * st_.g[ok, slot] / np.where(live, cb_b, 1.0), 0.0)
+                nbr[ok, slot] = np.where(wn != 0, self._flat(j[ok]), 0xFFFFFFFF)
+                w_new[ok, slot] = wn
+                w_old[ok, slot] = wn * ca_b
+            c32, n32 = np.ascontiguousarray(cells), np.ascontiguousarray(nbr.reshape(-1))
+            wn32, wo32 = _f32(w_new.reshape(-1)), _f32(w_old.reshape(-1))
+            if bloch:
+                self._chk(d.fdtd_add_aniso_bloch(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32), _ptr(wrap)),
+                          "fdtd_add_aniso_bloch")
+            else:
+                self._chk(d.fdtd_add_aniso(h, int(st_.comp), n, _ptr(c32), _ptr(n32), _ptr(wn32), _ptr(wo32)), "fdtd_add_aniso")
+
+    def _add_modulation(self, spec):
+        """time-modulated media (spec.ModulationSet): per node the table coefficient the sweep applies there and its static medium"""
+        d, h = self.lib.dll, self.handle
         modulation = getattr(spec, "modulation", None) or []
-        if modulation:
-            self._refuse_on_z_slabs("modulation")
-            if aniso:
-                refuse_together("modulation", "aniso")
-            off = np.asarray(self.ghost, np.int64)          # (Bloch device layout: every node moves by the ghost offset)
-            ca32, cb32 = np.asarray(ca, np.float64), np.asarray(cb, np.float64)     # the float32 table, as the sweep reads it
-            for ms in modulation:
-                n = len(ms.ijk)
-                if n == 0:
-                    continue
-                ijk = np.asarray(ms.ijk, np.int64) + off[None, :]
-                cells = np.ascontiguousarray((ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32))
-                mi = spec.mat_idx[int(ms.comp)][ijk[:, 2], ijk[:, 1], ijk[:, 0]] if spec.mat_idx is not None else np.ones(n, np.int64)
-                ca_n, cb_n = ca32[mi], cb32[mi]
-                if not (cb_n > 0).all():
-                    raise SolverLibraryError("a time-modulated node on a PEC cell")
-                eps_bar = spec.dt / (EPSILON_0 * cb_n) * 2.0 / (1.0 + ca_n)
-                s_bar = eps_bar * (1.0 - ca_n) / (1.0 + ca_n)
-                d_s = np.asarray(ms.d_sigma, np.complex128) * (spec.dt / (2.0 * EPSILON_0))
-                arrs = [_f32(ca_n), _f32(eps_bar), _f32(s_bar), _cplx_f32(np.asarray(ms.d_eps, np.complex128)), _cplx_f32(d_s)]
-                self._chk(d.fdtd_add_modulation(h, int(ms.comp), n, _ptr(cells), *[_ptr(a) for a in arrs],
-                                                2.0 * np.pi * float(ms.freq_eps) * spec.dt, 2.0 * np.pi * float(ms.freq_sigma) * spec.dt),
-                          "fdtd_add_modulation")
-        # PEC-conformal boundaries (spec.ConformalSet): the cut faces per H component, edges and weights as [4][n]
+        if not modulation:
+            return
+        self._refuse_on_z_slabs("modulation")
+        if getattr(spec, "aniso", None):
+            refuse_together("modulation", "aniso")
+        off = np.asarray(self.ghost, np.int64)          # (Bloch device layout: every node moves by the ghost offset)
+        for ms in modulation:
+            n = len(ms.ijk)
+            if n == 0:
+                continue
+            ijk = np.asarray(ms.ijk, np.int64) + off[None, :]
+            cells = self._flat(ijk)
+            ca_n, eps_bar, s_bar = self._static_medium(int(ms.comp), ijk, "time-modulated")
+            d_s = np.asarray(ms.d_sigma, np.complex128) * (spec.dt / (2.0 * EPSILON_0))
+            arrs = [_f32(ca_n), _f32(eps_bar), _f32(s_bar), _cplx_f32(np.asarray(ms.d_eps, np.complex128)), _cplx_f32(d_s)]
+            self._chk(d.fdtd_add_modulation(h, int(ms.comp), n, _ptr(cells), *[_ptr(a) for a in arrs],
+                                            2.0 * np.pi * float(ms.freq_eps) * spec.dt, 2.0 * np.pi * float(ms.freq_sigma) * spec.dt),
+                      "fdtd_add_modulation")
+
+    def _add_conformal(self, spec):
+        """PEC-conformal boundaries (spec.ConformalSet): the cut faces per H component, edges and weights as [4][n]"""
+        d, h = self.lib.dll, self.handle
         conformal = getattr(spec, "conformal", None) or []
-        if conformal:
-            self._refuse_on_z_slabs("conformal")
-            if spec.bloch is not None:
-                refuse_together("conformal", "Bloch boundaries")
-            for cs in conformal:
-                n = len(cs.ijk)
-                if n == 0:
-                    continue
-                ijk = np.asarray(cs.ijk, np.int64)
-                cells = np.ascontiguousarray((ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32))
-                j = np.asarray(cs.nbr_ijk, np.int64)
-                nbr = np.where(j[:, :, 0] >= 0, j[:, :, 2] * sxy + j[:, :, 1] * nx + j[:, :, 0], 0xFFFFFFFF).astype(np.uint32)
-                nbr32, d32 = np.ascontiguousarray(nbr.T), _f32(np.asarray(cs.d).T)
-                self._chk(d.fdtd_add_pec_conformal(h, int(cs.comp), n, _ptr(cells), _ptr(nbr32), _ptr(d32)), "fdtd_add_pec_conformal")
-            self.n_conformal_faces = sum(len(cs.ijk) for cs in conformal)
-        # Kerr media (spec.NonlinearSet)
-        self._table32 = (np.asarray(ca, np.float64), np.asarray(cb, np.float64))      # the float32 table, as the sweep reads it
+        if not conformal:
+            return
+        self._refuse_on_z_slabs("conformal")
+        if spec.bloch is not None:
+            refuse_together("conformal", "Bloch boundaries")
+        for cs in conformal:
+            n = len(cs.ijk)
+            if n == 0:
+                continue
+            cells, nbr32, d32 = self._flat(cs.ijk), self._nbr_table(cs.nbr_ijk), _f32(np.asarray(cs.d).T)
+            self._chk(d.fdtd_add_pec_conformal(h, int(cs.comp), n, _ptr(cells), _ptr(nbr32), _ptr(d32)), "fdtd_add_pec_conformal")
+        self.n_conformal_faces = sum(len(cs.ijk) for cs in conformal)
+
+    def _add_nonlinear(self, spec):
+        """Kerr media (spec.NonlinearSet) of the spec: beside no other list kind"""
         self.n_nonlinear_nodes = 0
         nonlinear = getattr(spec, "nonlinear", None) or []
-        if nonlinear:
-            for other, sets in (("aniso", aniso), ("modulation", modulation), ("conformal", conformal)):
-                if sets:
-                    refuse_together("nonlinear", other)
-            self.add_nonlinear(nonlinear)
-        # sources
-        from .spec import BC_PEC
+        if not nonlinear:
+            return
+        for other in ("aniso", "modulation", "conformal"):
+            if getattr(spec, other, None):
+                refuse_together("nonlinear", other)
+        self.add_nonlinear(nonlinear)
+
+    def _add_point_sources(self, spec):
+        d, h, z0, z1 = self.lib.dll, self.handle, self.z0, self.z1
         for s in spec.sources:
             k = s.ijk[:, 2]
             keep = (k >= z0) & (k < z1)
@@ -695,23 +745,23 @@ class HipEngine:
                     keep &= ~((s.ijk[:, a] == 0) & (s.comp < 3) & (s.comp != a))
             if not keep.any():
                 continue
-            ijk = s.ijk[keep]
-            cell = ((ijk[:, 2] - z0).astype(np.int64) * sxy + ijk[:, 1].astype(np.int64) * nx
-                    + ijk[:, 0]).astype(np.uint32)
+            cell = self._flat(s.ijk[keep], z0=z0)
             comp = np.ascontiguousarray(s.comp[keep], dtype=np.int32)
             wre, wim = _f32(s.w_re[keep]), _f32(s.w_im[keep])
             we, wh = _cplx_f32(s.wave_e), _cplx_f32(s.wave_h)
             self._chk(d.fdtd_add_point_source(h, len(cell), _ptr(comp), _ptr(cell), _ptr(wre),
                                               _ptr(wim), len(s.wave_e), _ptr(we), _ptr(wh)),
                       "fdtd_add_point_source")
+
+    def _add_tfsf(self, spec):
+        d, h, z0, z1 = self.lib.dll, self.handle, self.z0, self.z1
+
+        def loc(ijk, *arrs):
+            """the corrections of this slab: their slab-local cells, and ``arrs`` cut to them"""
+            k = ijk[:, 2]
+            keep = (k >= z0) & (k < z1)
+            return [self._flat(ijk[keep], z0=z0)] + [np.ascontiguousarray(a[keep]) for a in arrs]
         for t in spec.tfsf:
-            def loc(ijk, *arrs):
-                k = ijk[:, 2]
-                keep = (k >= z0) & (k < z1)
-                ij = ijk[keep]
-                cell = ((ij[:, 2] - z0).astype(np.int64) * sxy + ij[:, 1].astype(np.int64) * nx
-                        + ij[:, 0]).astype(np.uint32)
-                return [cell] + [np.ascontiguousarray(a[keep]) for a in arrs]
             ecell, ecomp, ew, eaux = loc(t.e_corr_ijk, t.e_corr_comp.astype(np.int32),
                                          t.e_corr_w.astype(np.float32), t.e_corr_aux.astype(np.int32))
             hcell, hcomp, hw, haux = loc(t.h_corr_ijk, t.h_corr_comp.astype(np.int32),
@@ -722,11 +772,6 @@ class HipEngine:
                                       _ptr(wave), len(ecell), _ptr(ecomp), _ptr(ecell), _ptr(ew),
                                       _ptr(eaux), len(hcell), _ptr(hcomp), _ptr(hcell), _ptr(hw),
                                       _ptr(haux)), "fdtd_add_tfsf")
-        # monitors (intersected with the slab)
-        self.mon_ids: List[Tuple[MonitorSpec, int, Tuple[int, int]]] = []
-        self.add_monitors(spec.monitors)
-        self._chk(d.fdtd_set_shutoff(h, int(spec.decay_every), float(spec.shutoff),
-                                     int(spec.decay_ref_step)), "fdtd_set_shutoff")
 
     def add_monitors(self, monitors):
         """Add ``monitors`` (MonitorSpecs on the device's axes and index layout, as ``self.spec.monitors`` are) to the handle — at
@@ -837,32 +882,20 @@ class HipEngine:
 
     def add_nonlinear(self, sets):
         """Upload Kerr lists (spec.NonlinearSet, in the axes of ``self.spec``; at most one per E component of the handle): per node the
-        table coefficient the sweep applies there, the static medium recovered from it as for the modulation lists — eps_bar = dt /
-        (eps0 Cb) * 2 / (1 + Ca), s_bar = eps_bar (1 - Ca) / (1 + Ca) — chi3, and the eight neighbour slots as [8][n].  May be called
-        between runs: the next step forms I^n from the fields it finds."""
+        table coefficient the sweep applies there, the static medium recovered from it as for the modulation lists
+        (``_static_medium``), chi3, and the eight neighbour slots as [8][n].  May be called between runs: the next step forms I^n
+        from the fields it finds."""
         spec, d, h = self.spec, self.lib.dll, self.handle
-        ny = spec.shape[1]
         self._refuse_on_z_slabs("nonlinear")
         if spec.bloch is not None:
             refuse_together("nonlinear", "Bloch boundaries")
-        nx = self.nxp                       # row length on the device
-        sxy = nx * ny
-        ca32, cb32 = self._table32
         for ns in sets:
             n = len(ns.ijk)
             if n == 0:
                 continue
             ijk = np.asarray(ns.ijk, np.int64)
-            cells = np.ascontiguousarray((ijk[:, 2] * sxy + ijk[:, 1] * nx + ijk[:, 0]).astype(np.uint32))
-            j = np.asarray(ns.nbr_ijk, np.int64)
-            nbr = np.where(j[:, :, 0] >= 0, j[:, :, 2] * sxy + j[:, :, 1] * nx + j[:, :, 0], 0xFFFFFFFF).astype(np.uint32)
-            nbr32 = np.ascontiguousarray(nbr.T)
-            mi = spec.mat_idx[int(ns.comp)][ijk[:, 2], ijk[:, 1], ijk[:, 0]] if spec.mat_idx is not None else np.ones(n, np.int64)
-            ca_n, cb_n = ca32[mi], cb32[mi]
-            if not (cb_n > 0).all():
-                raise SolverLibraryError("a nonlinear node on a PEC cell")
-            eps_bar = spec.dt / (EPSILON_0 * cb_n) * 2.0 / (1.0 + ca_n)
-            s_bar = eps_bar * (1.0 - ca_n) / (1.0 + ca_n)
+            cells, nbr32 = self._flat(ijk), self._nbr_table(ns.nbr_ijk)
+            ca_n, eps_bar, s_bar = self._static_medium(int(ns.comp), ijk, "nonlinear")
             arrs = [_f32(ca_n), _f32(eps_bar), _f32(s_bar), _f32(np.asarray(ns.chi3, np.float64))]
             self._chk(d.fdtd_add_nonlinear(h, int(ns.comp), n, _ptr(cells), _ptr(nbr32), *[_ptr(a) for a in arrs],
                                            int(ns.num_iters)), "fdtd_add_nonlinear")

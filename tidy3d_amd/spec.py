@@ -20,6 +20,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from .exceptions import Tidy3dNotImplementedError
+
 COMPONENTS = ("Ex", "Ey", "Ez", "Hx", "Hy", "Hz")
 COMP_ID = {c: i for i, c in enumerate(COMPONENTS)}
 
@@ -116,6 +118,17 @@ class NonlinearSet:
     nbr_ijk: np.ndarray               # [n, 8, 3], the layout of AnisoSet.nbr_ijk; -1 = no node (beyond a non-periodic wall): 0 in its mean
     chi3: np.ndarray                  # float64 [n], um^2 / V^2
     num_iters: int = 5                # the same in every set of a spec
+
+
+# The whole-grid node lists (csrc/fdtd_capi.hip kListKind) by their attribute on the SolverSpec: what the refusals call the kind, its verb
+LIST_KINDS = {"aniso": ("FullyAnisotropicMedium", "is"), "modulation": ("time-modulated (modulation_spec) media", "are"),
+              "conformal": ("PECConformal", "is"), "nonlinear": ("nonlinear (nonlinear_spec) media", "are")}
+
+
+def refuse_together(kind, other, hint=""):
+    """``kind`` (a key of LIST_KINDS) together with ``other`` (another key, or a phrase) is not supported"""
+    phrase, verb = LIST_KINDS[kind]
+    raise Tidy3dNotImplementedError(f"{phrase} together with {LIST_KINDS.get(other, (other,))[0]} {verb} not supported{hint}")
 
 
 @dataclass
