@@ -388,6 +388,19 @@ int fdtd_add_field_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps,
 int fdtd_add_lattice_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comps, const int32_t lo[3], const int32_t hi[3],
                                  int64_t n_rec, const int64_t* steps, const int32_t* n_targets, int n_taps /* 4 */,
                                  const int32_t* tap_index, const float* tap_weight, int nf, const float* phase_e, const float* phase_h);
+/* The power through a surface from its lattice accumulators, reduced on the device (ref monitor.py DirectivityMonitor: the radiated
+ * power a directivity is normalised by; csrc/fdtd_lattice_flux.hpp).  `monitor_id`: a lattice DFT monitor that holds the four
+ * components tangential to `axis`; a surface is one monitor here, a closed box is six calls.
+ * fdtd_set_lattice_flux_weights, once per monitor, with the plan: the orientation `sign` of the surface and the integration weights
+ * along the three axes — n[a] of them, as many as the monitor keeps nodes along a, one ([1]) along the normal.
+ * fdtd_lattice_flux, after a run:
+ *     out[k] = sign * sum over the lattice of w0 w1 w2 * 0.5 Re(E x conj H) . n_axis,   k < nf, double,
+ * from the accumulators as they stand (before any source normalisation), one workgroup of 256 per frequency, fp64, a fixed order
+ * of summation, no atomics.  Both refuse, with the handle's error string and without a launch: an id that is no lattice DFT
+ * monitor, z-slab handles, the handles of an fdtd_run_bloch pair; fdtd_lattice_flux a monitor without weights.  Return 0 or <0. */
+int fdtd_set_lattice_flux_weights(FdtdSolver* h, int monitor_id, int axis, double sign, const int32_t n[3], const double* w0,
+                                  const double* w1, const double* w2);
+int fdtd_lattice_flux(FdtdSolver* h, int monitor_id, double* out /* [nf] */);
 /* time: float [n_rec][n_comps][bz][by][bx];  dft: complex64 [nf][n_comps][bz][by][bx];  flux-time: float [n_rec];
  * sparse field-time: float [n_rec][sum over the components of their kept nodes];
  * sparse DFT, lattice DFT: complex64 [nf][sum over the components of their kept nodes] */

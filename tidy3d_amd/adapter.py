@@ -94,6 +94,12 @@ def to_tidy3d(sim_data: SimulationData, td_simulation=None):
                      for k, v in d.field_components.items()}
             out.append(getattr(td, type(d).__name__)(monitor=mon, projection_surfaces=mon.projection_surfaces,
                                                      medium=mon.medium or td_simulation.medium, **comps))
+        elif type(d).__name__ == "DirectivityData":
+            comps = {k: td.FieldProjectionAngleDataArray(v.values, coords={dim: v.coords[dim] for dim in v.dims})
+                     for k, v in d.field_components.items()}
+            out.append(td.DirectivityData(monitor=mon, projection_surfaces=mon.projection_surfaces,
+                                          medium=mon.medium or td_simulation.medium,
+                                          flux=td.FluxDataArray(d.flux.values, coords={"f": d.flux.coords["f"]}), **comps))
         elif type(d).__name__ == "ModeSolverData":
             comps = {k: td.ScalarModeFieldDataArray(v.values, coords={dim: v.coords[dim] for dim in v.dims})
                      for k, v in d.field_components.items()}

@@ -30,6 +30,7 @@
 #include "fdtd_field_time.hpp"
 #include "fdtd_field_dft.hpp"
 #include "fdtd_lattice_dft.hpp"
+#include "fdtd_lattice_flux.hpp"
 
 using namespace fdtd;
 
@@ -181,6 +182,8 @@ struct Monitor {
   FluxMonP fp{};                   // FluxRing: addresses and shapes of its tables
   FieldTimeP gp{};                 // SparseRing
   FieldDftP dp{};                  // SparseDft, LatticeDft
+  LatticeFluxP lp{};               // LatticeDft with integration weights (fdtd_set_lattice_flux_weights): what fdtd_lattice_flux reduces
+  bool has_flux = false;
   float* result() const { return form == MonForm::FluxRing ? fp.result : gp.out; }
   long long slot(size_t rec) const { return (long long)(ring ? rec % ring : rec); }
 };
@@ -396,6 +399,7 @@ struct FdtdSolver {
   int f2_dyn_reason = 0;              // the last reason a step of this run could not open a pair because of its sources (FDTD_F2_OFF_*)
   long long src_h_nodes = 0;          // H-side source nodes (need the table of all steps)
   bool src_e_in_damp = false;         // an E-side source node lies inside an absorber layer (its damping factor is not exactly 1)
+  bool bloch_pair = false;            // the handle has been one of the two of an fdtd_run_bloch
 };
 
 namespace {
@@ -4073,6 +4077,83 @@ int fdtd_add_lattice_dft_monitor(FdtdSolver* h, int n_comps, const int32_t* comp
   if (n_taps != kLatticeTaps) return fail(h, "fdtd_add_lattice_dft_monitor: n_taps must be %d, got %d", kLatticeTaps, n_taps);
   return add_sparse_dft(h, "fdtd_add_lattice_dft_monitor", MonForm::LatticeDft, kLatticeTaps, n_comps, comps, lo, hi, n_rec, steps, n_targets,
                         tap_index, tap_weight, nf, phase_e, phase_h);
+}
+
+}  // extern "C"
+namespace {
+// fdtd_set_lattice_flux_weights and fdtd_lattice_flux: the monitor `id` as a lattice DFT monitor on a handle that may reduce it
+Monitor* lattice_flux_monitor(FdtdSolver* h, const char* who, int id) {
+  if (h->comm || h->cfg.bc[4] == FDTD_BC_NEIGHBOR || h->cfg.bc[5] == FDTD_BC_NEIGHBOR) {
+    fail(h, "%s: not available on z-slab handles (the surface would be cut between ranks)", who);
+    return nullptr;
+  }
+  if (h->bloch_pair) { fail(h, "%s: not available on the handles of a Bloch pair (complex fields)", who); return nullptr; }
+  if (id < 0 || id >= (int)h->mons.size()) { fail(h, "%s: bad id %d", who, id); return nullptr; }
+  if (h->mons[id].form != MonForm::LatticeDft) {
+    fail(h, "%s: monitor %d has no lattice accumulators (it was not added by fdtd_add_lattice_dft_monitor)", who, id);
+    return nullptr;
+  }
+  return &h->mons[id];
+}
+}  // namespace
+extern "C" {
+
+int fdtd_set_lattice_flux_weights(FdtdSolver* h, int id, int axis, double sign, const int32_t n[3], const double* w0, const double* w1,
+                                  const double* w2) {
+  if (!h) return -1;
+  const char* who = "fdtd_set_lattice_flux_weights";
+  Monitor* m = lattice_flux_monitor(h, who, id);
+  if (!m) return -1;
+  if (axis < 0 || axis > 2 || !n || !w0 || !w1 || !w2) return fail(h, "%s: bad argument", who);
+  if (m->has_flux) return fail(h, "%s: monitor %d has its weights already", who, id);
+  // the four tangential components of the surface, in whatever order the monitor holds them; every one on the same lattice
+  const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
+  const int want[4] = {a1, a2, 3 + a1, 3 + a2};
+  const TapTables& T = m->dp.t;
+  LatticeFluxP p{};
+  if (m->comps.size() != 4) return fail(h, "%s: monitor %d holds %zu components, a surface holds its four tangential ones", who, id, m->comps.size());
+  for (int q = 0; q < 4; ++q) {
+    int slot = -1;
+    for (int c = 0; c < 4; ++c) if (m->comps[c] == want[q]) slot = c;
+    if (slot < 0) return fail(h, "%s: monitor %d does not hold component %d, tangential to a surface normal to axis %d", who, id, want[q], axis);
+    for (int a = 0; a < 3; ++a)
+      if (T.nt[slot][a] != n[a] || (a == axis && n[a] != 1))
+        return fail(h, "%s: %d weights along axis %d, component %d of monitor %d keeps %d nodes there", who, n[a], a, want[q], id, T.nt[slot][a]);
+    p.off[q] = T.out_off[slot];
+  }
+  const double* w[3] = {w0, w1, w2};
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; i < n[a]; ++i)
+      if (!(w[a][i] == w[a][i])) return fail(h, "%s: weight %d along axis %d is not a number", who, i, a);
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  m->mark = h->stats.device_bytes;
+  for (int a = 0; a < 3; ++a) {
+    double* dw = nullptr;
+    if (dev_upload(h, &dw, w[a], (size_t)n[a])) return -1;
+    p.w[a] = dw; p.n[a] = n[a];
+  }
+  if (dev_alloc(h, &p.out, (size_t)m->nf)) return -1;
+  took(h, *m, kBytesTables);
+  p.acc = m->dp.acc; p.nodes = T.nodes;
+  p.half_sign = 0.5 * sign;
+  m->lp = p;
+  m->has_flux = true;
+  return 0;
+}
+
+int fdtd_lattice_flux(FdtdSolver* h, int id, double* out) {
+  if (!h) return -1;
+  const char* who = "fdtd_lattice_flux";
+  Monitor* m = lattice_flux_monitor(h, who, id);
+  if (!m) return -1;
+  if (!out) return fail(h, "%s: bad argument", who);
+  if (!m->has_flux) return fail(h, "%s: monitor %d has no integration weights (fdtd_set_lattice_flux_weights)", who, id);
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(lattice_flux_kernel, dim3((unsigned)m->nf), dim3(kLatticeFluxThreads), 0, h->stream, m->lp);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(out, m->lp.out, (size_t)m->nf * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int fdtd_get_monitor_bytes(FdtdSolver* h, int id, int64_t out[4]) {

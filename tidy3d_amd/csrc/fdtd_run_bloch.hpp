@@ -60,6 +60,7 @@ struct BlochRun {
     st = hr->stream;
     HIPCHK(hr, hipStreamSynchronize(hi->stream));
     both[0] = hr, both[1] = hi;
+    hr->bloch_pair = hi->bloch_pair = true;
     if (run_begin({hr, hi}, st)) return -1;
     per_z = hr->cfg.bc[4] == FDTD_BC_PERIODIC;
     // (a wide material table keeps the two-pass kernels here, whatever the variant asked for: Run::setup lets FDTD_VARIANT_FUSED read it)

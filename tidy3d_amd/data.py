@@ -21,6 +21,7 @@ import numpy as np
 from . import schema as td
 from .discretize import Discretization, FieldPlan, MonitorPlan
 from .exceptions import DataError
+from .projection import FieldProjectionAngleData
 from .spec import BC_PERIODIC, COMP_ID, SolverSpec
 
 
@@ -224,6 +225,60 @@ class FluxData:
         s = np.abs(np.asarray(spectrum_fn(self.flux.coords["f"]))) ** 2
         return FluxData(monitor=self.monitor,
                         flux=DataArray((self.flux.values / s).astype(np.float32), self.flux.coords))
+
+
+AXIAL_RATIO_CAP = 100.0       # what the reference reports for a linear polarisation (its axial ratio is infinite)
+
+
+@dataclass
+class DirectivityData(FieldProjectionAngleData):
+    """Mirror of tidy3d DirectivityData (ref monitor_data.py DirectivityData): the far fields Er .. Hphi of a
+    ``FieldProjectionAngleData``, dims (r, theta, phi, f), and one more array,
+
+        flux[f]                            the power that leaves the monitor's box, in W: the sum over its surfaces (those of
+                                           ``exclude_surfaces`` left out) of sign * int 0.5 Re(E x conj H) . n dS, with the source
+                                           normalisation of ``FluxData`` (divided by |source spectrum|^2), never windowed.
+
+    From them (all with the dims of the fields):
+
+        radiation_intensity = r^2 * power                        power = 0.5 Re(E x conj H) . r_hat  (W / sr)
+        directivity         = 4 pi * radiation_intensity / flux
+        left_polarization   = (E_theta - 1j * E_phi) / sqrt(2)
+        right_polarization  = (E_theta + 1j * E_phi) / sqrt(2)
+        axial_ratio         = (|L| + |R|) / ||L| - |R||          clipped at ``AXIAL_RATIO_CAP`` = 100 (a linear polarisation)
+
+    Which circular component is "left".  The fields carry the time dependence exp(-i omega t), and (theta_hat, phi_hat, r_hat) is
+    right-handed.  E = L e_L + R e_R with e_L = (theta_hat + 1j phi_hat) / sqrt(2), e_R = (theta_hat - 1j phi_hat) / sqrt(2).  The
+    physical field of e_L is theta_hat cos(omega t) + phi_hat sin(omega t): it turns from theta_hat towards phi_hat, the
+    right-handed sense about the direction of propagation r_hat — counter-clockwise for an observer who faces the oncoming wave.
+    That is LEFT circular in the optics convention, the one these names follow, and right-hand circular in the IEEE antenna
+    convention; ``right_polarization`` is the other one."""
+    flux: object = None
+
+    @property
+    def radiation_intensity(self):
+        r = np.asarray(self.Etheta.coords["r"], float)
+        return DataArray(r[:, None, None, None] ** 2 * np.asarray(self.power.values), self.Etheta.coords)
+
+    @property
+    def directivity(self):
+        fl = np.asarray(self.flux.values, float)
+        return DataArray(4 * np.pi * np.asarray(self.radiation_intensity.values) / fl[None, None, None, :], self.Etheta.coords)
+
+    @property
+    def left_polarization(self):
+        return DataArray((np.asarray(self.Etheta.values) - 1j * np.asarray(self.Ephi.values)) / np.sqrt(2.0), self.Etheta.coords)
+
+    @property
+    def right_polarization(self):
+        return DataArray((np.asarray(self.Etheta.values) + 1j * np.asarray(self.Ephi.values)) / np.sqrt(2.0), self.Etheta.coords)
+
+    @property
+    def axial_ratio(self):
+        l, r = np.abs(self.left_polarization.values), np.abs(self.right_polarization.values)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ar = (l + r) / np.abs(l - r)
+        return DataArray(np.where(np.isnan(ar), AXIAL_RATIO_CAP, np.minimum(ar, AXIAL_RATIO_CAP)), self.Etheta.coords)
 
 
 @dataclass
@@ -673,8 +728,10 @@ def assemble(disc: Discretization, raw: Dict[str, np.ndarray], log: str = "", di
         elif plan.kind.startswith("projection_"):
             from . import projection
             fn = {"projection_angle": projection.project_angle, "projection_cartesian": projection.project_cartesian,
-                  "projection_kspace": projection.project_kspace}[plan.kind]
-            if plan.kind == "projection_kspace" or mon.far_field_approx:
+                  "projection_kspace": projection.project_kspace, "projection_directivity": projection.project_directivity}[plan.kind]
+            if plan.kind == "projection_directivity":
+                out.append(fn(disc, plan, raw, norm, lib=device_lib, device=device, notes=notes))
+            elif plan.kind == "projection_kspace" or mon.far_field_approx:
                 out.append(fn(disc, plan, raw, norm, lib=device_lib, device=device))
             else:
                 out.append(fn(disc, plan, raw, norm, lib=exact_lib or device_lib, device=device,

@@ -235,6 +235,9 @@ def permute_spec(spec: SolverSpec, s: int) -> SolverSpec:
                 for m in monitors]
     # sparse field-time and sparse DFT monitors: every component's per-axis tables (hence its kept-node counts) are renamed with the axes
     monitors = [m if m.kind not in SPARSE_KINDS else dataclasses.replace(m, taps=tuple(pick(t) for t in m.taps)) for m in monitors]
+    # ... and a lattice surface that carries integration weights (a DirectivityMonitor's): its normal and weights likewise
+    monitors = [m if m.kind != "dft_lattice" or m.weights is None else dataclasses.replace(m, axis=inv[m.axis], weights=pick(m.weights))
+                for m in monitors]
     def renamed(lists):
         """node lists with neighbour slots: nodes, slots and components are renamed with the axes; a cyclic renaming keeps the slot
         order (the PEC-conformal lists' a1, a2 follow c; the Kerr lists' b, c follow a)"""
@@ -814,6 +817,11 @@ class HipEngine:
                         args = args + taps + (_ptr(tidx), _ptr(tw), len(m.freqs), _ptr(pe), _ptr(ph))
                 mid = getattr(d, name)(h, *args)
                 self._chk(mid, name)
+                if m.kind == "dft_lattice" and m.weights is not None:      # a DirectivityMonitor's surface: uploaded once, with the plan
+                    w = [np.ascontiguousarray(m.weights[a], dtype=np.float64) for a in range(3)]
+                    n_w = np.asarray([len(v) for v in w], dtype=np.int32)
+                    self._chk(d.fdtd_set_lattice_flux_weights(h, mid, int(m.axis), float(m.sign), _ptr(n_w), *[_ptr(v) for v in w]),
+                              "fdtd_set_lattice_flux_weights")
                 self.mon_ids.append((m, mid, (lo2, hi2)))
                 continue
             if m.kind == "dft":
@@ -986,6 +994,20 @@ class HipEngine:
                     out[m.name] = (out[m.name][0] + 1j * im[m.name][0], out[m.name][1])
         if self.axis_shift:                 # back to the user's axes (single slab: the z range is the box's own)
             out = {k: (v[0] if v[0].ndim < 3 else unpermute_array(v[0], self.axis_shift), self.user_zrange[k]) for k, v in out.items()}
+        return out
+
+    def lattice_flux(self) -> Dict[str, np.ndarray]:
+        """name -> float64 [nf]: the power through every lattice surface that carries integration weights (the surfaces of a
+        DirectivityMonitor on the device path), reduced on the device from the accumulators as they stand
+        (``fdtd_lattice_flux``, csrc/fdtd_lattice_flux.hpp) — sign * sum w * 0.5 Re(E x conj H) . n, before the source
+        normalisation.  The planes are not downloaded."""
+        out = {}
+        for m, mid, _ in self.mon_ids:
+            if mid < 0 or m.kind != "dft_lattice" or m.weights is None:
+                continue
+            arr = np.empty(len(m.freqs), dtype=np.float64)
+            self._chk(self.lib.dll.fdtd_lattice_flux(self.handle, mid, _ptr(arr)), "fdtd_lattice_flux")
+            out[m.name] = arr
         return out
 
     def monitor_bytes(self, name: str, detail: bool = False):

@@ -446,7 +446,7 @@ def simulation_data_model(sim_data) -> Tuple[dict, Dict[str, Any]]:
             for name, arr in d.field_components.items():
                 entry[name] = "ScalarModeFieldDataArray"
                 arrays[f"{base}/{name}"] = arr
-        elif kind in ("FieldProjectionAngleData", "FieldProjectionCartesianData", "FieldProjectionKSpaceData"):
+        elif kind in ("FieldProjectionAngleData", "FieldProjectionCartesianData", "FieldProjectionKSpaceData", "DirectivityData"):
             from .discretize import flux_surfaces
             mon = d.monitor
             # ref monitor.py:874-889: the near-field surfaces as colocated FieldMonitors
@@ -458,9 +458,12 @@ def simulation_data_model(sim_data) -> Tuple[dict, Dict[str, Any]]:
                 for sname, box, axis, sign in flux_surfaces(mon)]
             entry["medium"] = (mon.medium if mon.medium is not None else sim.medium).dict()
             entry["is_2d_simulation"] = False
-            for name, arr in d.field_components.items():
-                entry[name] = kind.replace("Data", "DataArray")
+            for name, arr in d.field_components.items():      # (DirectivityData: the angle-data group plus a flux array)
+                entry[name] = "FieldProjectionAngleDataArray" if kind == "DirectivityData" else kind.replace("Data", "DataArray")
                 arrays[f"{base}/{name}"] = arr
+            if kind == "DirectivityData":
+                entry["flux"] = "FluxDataArray"
+                arrays[f"{base}/flux"] = d.flux
         elif kind == "DiffractionData":
             # ref monitor_data.py:2672-2751: six DiffractionDataArrays + sim_size, bloch_vecs, medium
             entry["sim_size"] = [float(v) for v in d.sim_size]
@@ -557,6 +560,9 @@ def load_simulation_data(path: str):
         elif kind in ("FieldProjectionAngleData", "FieldProjectionCartesianData", "FieldProjectionKSpaceData"):
             from . import projection
             out.append(getattr(projection, kind)(monitor=mon, **fields))
+        elif kind == "DirectivityData":
+            from .data import DirectivityData
+            out.append(DirectivityData(monitor=mon, **fields))
         elif kind == "DiffractionData":
             from . import projection
             out.append(projection.DiffractionData(monitor=mon, sim_size=tuple(e["sim_size"]),

@@ -43,6 +43,7 @@ SYMBOLS = (
     "fdtd_add_field_time_monitor", "fdtd_add_field_dft_monitor", "fdtd_add_lattice_dft_monitor", "fdtd_add_modulation",
     "fdtd_add_pec_conformal", "fdtd_add_nonlinear",
     "fdtd_near_field", "fdtd_near_field_chunks",
+    "fdtd_set_lattice_flux_weights", "fdtd_lattice_flux",
 )
 
 BC_PEC, BC_PMC, BC_PERIODIC, BC_NEIGHBOR = 0, 1, 2, 3
@@ -142,6 +143,8 @@ class FdtdLib:
         d.fdtd_add_field_time_monitor.argtypes = [vp, C.c_int, vp, vp, vp, i64, vp, vp, vp, vp, i64]
         d.fdtd_add_field_dft_monitor.argtypes = [vp, C.c_int, vp, vp, vp, i64, vp, vp, vp, vp, C.c_int, vp, vp]
         d.fdtd_add_lattice_dft_monitor.argtypes = [vp, C.c_int, vp, vp, vp, i64, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+        d.fdtd_set_lattice_flux_weights.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]
+        d.fdtd_lattice_flux.argtypes = [vp, C.c_int, vp]
         d.fdtd_get_monitor_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
         d.fdtd_set_field.argtypes = [vp, C.c_int, vp, C.c_size_t]
         d.fdtd_get_field.argtypes = [vp, C.c_int, vp, C.c_size_t]

@@ -82,10 +82,10 @@ def surface_lattice(sim, mon, box, axis: int, medium=None):
     return pts
 
 
-def _surface_currents(disc, plan, raw, norm, medium):
-    """Per surface of the monitor: (axis, u, v, sample points [3 arrays], J {axis: (u, v, f)}, M {...}):
-    equivalent currents J = n x H, M = -n x E (ref field_projection.py:231-278) on a regular lattice of
-    10 points per wavelength clipped to the simulation domain (ref :280-349).  A surface accumulated on the device (MonitorSpec
+def _surface_fields(disc, plan, raw, norm, medium):
+    """Per surface of the monitor: (axis, sign, u, v, sample points [3 arrays], F {"Ex" ..: (u, v, f)}): the four tangential
+    components, normalised by the source spectrum, in complex128 on a regular lattice of 10 points per wavelength clipped to the
+    simulation domain (ref field_projection.py:280-349).  A surface accumulated on the device (MonitorSpec
     kind "dft_lattice": a two-dimensional raw array) holds the values on the lattice of the plan already: nothing is colocated or
     resampled here, and a ``medium`` whose lattice differs from the recorded one is an error."""
     import dataclasses
@@ -118,12 +118,6 @@ def _surface_currents(disc, plan, raw, norm, medium):
             fp = dataclasses.replace(fp, target={f: list(rec) for f in fp.fields})      # the values lie on the lattice
         fd = _field_container(FieldData, m, spec, fp, raw[fp.spec_name], "f", freqs, sim.center,
                               np.complex128, full).normalize(norm)
-        # J = n x H, M = -n x E with the reference's sign table (ref :247-265)
-        signs = np.array([-1.0, 1.0])
-        if axis % 2 != 0:
-            signs = -signs
-        if sign < 0:
-            signs = -signs
         cu, cv = names[u], names[v]
 
         def sampled(comp):
@@ -133,8 +127,25 @@ def _surface_currents(disc, plan, raw, norm, medium):
             for a in (u, v):
                 arr = interp_axis(arr, np.asarray(fd[comp].coords[names[a]]), pts[a], axis=a)
             return np.take(arr, 0, axis=axis)                         # (u, v, f) in x, y, z order
-        J = {u: signs[0] * sampled("H" + cv), v: signs[1] * sampled("H" + cu)}
-        M = {v: signs[0] * sampled("E" + cu), u: signs[1] * sampled("E" + cv)}
+        yield axis, sign, u, v, pts, {c: sampled(c) for c in ("H" + cv, "H" + cu, "E" + cu, "E" + cv)}
+
+
+def _surface_currents(disc, plan, raw, norm, medium):
+    """Per surface of the monitor: (axis, u, v, sample points [3 arrays], J {axis: (u, v, f)}, M {...}):
+    equivalent currents J = n x H, M = -n x E (ref field_projection.py:231-278) of the fields ``_surface_fields`` samples, with the
+    monitor's ``window_size`` applied."""
+    mon = plan.monitor
+    names = "xyz"
+    for axis, sign, u, v, pts, F in _surface_fields(disc, plan, raw, norm, medium):
+        # J = n x H, M = -n x E with the reference's sign table (ref :247-265)
+        signs = np.array([-1.0, 1.0])
+        if axis % 2 != 0:
+            signs = -signs
+        if sign < 0:
+            signs = -signs
+        cu, cv = names[u], names[v]
+        J = {u: signs[0] * F["H" + cv], v: signs[1] * F["H" + cu]}
+        M = {v: signs[0] * F["E" + cu], u: signs[1] * F["E" + cv]}
         win = _window(mon, (u, v), pts)
         if win is not None:
             J = {a: arr * win for a, arr in J.items()}
@@ -362,6 +373,58 @@ def project_angle(disc, plan, raw, norm, lib=None, device: int = 0, exact_device
     e_t, e_p, k_f, eta_f = _far_fields(disc, plan, raw, norm, T.ravel(), P.ravel(), lib=lib, device=device)
     r = np.full(T.size, float(mon.proj_distance))
     return _package(FieldProjectionAngleData, mon, e_t, e_p, k_f, eta_f, r, (1, len(theta), len(phi), len(freqs)), coords)
+
+
+def surface_flux_terms(axis: int, pts, F) -> np.ndarray:
+    """The terms [n_u, n_v, n_f] (float64) whose sum is the power through one surface along +``axis``:
+
+        w_u w_v * 0.5 Re(E_a1 conj(H_a2) - E_a2 conj(H_a1)),        a1, a2 = axis + 1, axis + 2 (cyclic):  0.5 Re(E x conj H) . n
+
+    on the lattice ``pts`` = [x, y, z] with the fields ``F`` {"Ex" ..: (u, v, f)} (u < v the tangential axes), the trapezoid
+    weights w those of ``_trap_weights`` — the ones ``_far_fields`` / ``_trapz2`` integrate the currents with, so that far field and
+    flux see one surface.  What csrc/fdtd_lattice_flux.hpp sums on the device."""
+    a1, a2 = (axis + 1) % 3, (axis + 2) % 3
+    u, v = [a for a in range(3) if a != axis]
+    n = "xyz"
+    e1, e2, h1, h2 = (np.asarray(F[c + n[a]], np.complex128) for c, a in (("E", a1), ("E", a2), ("H", a1), ("H", a2)))
+    s = e1.real * h2.real + e1.imag * h2.imag - e2.real * h1.real - e2.imag * h1.imag
+    w = _trap_weights(pts[u])[:, None, None] * _trap_weights(pts[v])[None, :, None]
+    return w * (0.5 * s)
+
+
+FLUX_SUFFIX = "::flux"          # raw[spec_name + FLUX_SUFFIX]: float64 [n_f], the power through a surface as the device reduced it
+
+
+def project_directivity(disc, plan, raw, norm, lib=None, device: int = 0, notes: Optional[list] = None):
+    """DirectivityMonitor: the far fields of ``project_angle`` (the same ``_far_fields`` call: the same numbers) and the power that
+    leaves the monitor's box, ``flux[f]`` = the sum over its surfaces (``exclude_surfaces`` left out, as their currents are) of
+    sign * sum(``surface_flux_terms``), in float64, with the source normalisation of ``FluxData`` and never windowed.  Where the
+    run has reduced the surfaces on the device (``raw[spec_name + FLUX_SUFFIX]``: ``HipEngine.lattice_flux``, the accumulators
+    before the normalisation) those values are taken and divided by |source spectrum|^2; else the sums are taken here.  ``notes``
+    receives the line for SimulationData.log."""
+    from .data import DataArray, DirectivityData
+    mon = plan.monitor
+    freqs = np.asarray(mon.freqs, float)
+    theta, phi = np.asarray(mon.theta, float), np.asarray(mon.phi, float)
+    T, P = np.meshgrid(theta, phi, indexing="ij")
+    coords = {"r": np.atleast_1d(float(mon.proj_distance)), "theta": theta, "phi": phi, "f": freqs}
+    e_t, e_p, k_f, eta_f = _far_fields(disc, plan, raw, norm, T.ravel(), P.ravel(), lib=lib, device=device)
+    r = np.full(T.size, float(mon.proj_distance))
+    out = _package(DirectivityData, mon, e_t, e_p, k_f, eta_f, r, (1, len(theta), len(phi), len(freqs)), coords)
+    keys = [fp.spec_name + FLUX_SUFFIX for fp in plan.fields]
+    on_device = all(k in raw for k in keys)
+    flux = np.zeros(len(freqs), np.float64)
+    if on_device:
+        for k in keys:
+            flux += np.asarray(raw[k], np.float64)
+        flux = flux / np.abs(np.asarray(norm(freqs))) ** 2
+    else:
+        for axis, sign, u, v, pts, F in _surface_fields(disc, plan, raw, norm, None):
+            flux += sign * surface_flux_terms(axis, pts, F).sum(axis=(0, 1))
+    if notes is not None:
+        notes.append(f"Flux of DirectivityMonitor '{mon.name}': {'device' if on_device else 'host'}, {len(keys)} surfaces.")
+    out.flux = DataArray(flux, {"f": freqs})
+    return out
 
 
 @dataclass

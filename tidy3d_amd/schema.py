@@ -2712,6 +2712,26 @@ class FieldProjectionKSpaceMonitor(FieldProjectionAngleMonitor):
 
 @_register
 @dataclass
+class DirectivityMonitor(FieldProjectionAngleMonitor):
+    """Antenna directivity, radiated power and axial ratio on an angle grid (ref monitor.py DirectivityMonitor): the far fields of
+    a ``FieldProjectionAngleMonitor`` together with the power that leaves the monitor's own closed box (``DirectivityData.flux``,
+    tidy3d_amd/projection.py ``project_directivity``).  The same fields as the angle monitor; ``far_field_approx`` is fixed to
+    True, and the monitor must be a box: the flux through an open surface is not a radiated power."""
+
+    name: str = "directivity"
+
+    def __post_init__(self):
+        super().__post_init__()
+        if not self.far_field_approx:
+            raise SetupError(f"DirectivityMonitor '{self.name}': 'far_field_approx' is fixed to True (the directivity is a "
+                             "far-field quantity); far_field_approx=False is not supported.")
+        if any(float(_to_float(s)) == 0 for s in self.size):
+            raise SetupError(f"DirectivityMonitor '{self.name}' must be a box with a non-zero size along every axis, given "
+                             f"size={tuple(self.size)}: the flux through an open surface is not a radiated power.")
+
+
+@_register
+@dataclass
 class DiffractionMonitor(_Monitor):
     """Diffraction orders of a periodic structure through an infinite plane (ref monitor.py:1353-1407):
     the near fields of one period are recorded like a projection surface and decomposed into the

@@ -116,7 +116,7 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     ``FieldMonitor`` — accumulate its running DFT on the kept nodes only, on the device (True), over the whole box with colocation
     and ``interval_space`` on the host (False), or per monitor (None: on the device where the whole box's accumulators would
     exceed the threshold and fewer nodes are kept).  ``projection_device``: the same three values for the field projection monitors
-    (angle, Cartesian, k-space) — accumulate every surface on its sampling lattice of 10 points per wavelength only, on the device
+    (angle, Cartesian, k-space, and ``DirectivityMonitor``, whose flux is then reduced on the device too) — accumulate every surface on its sampling lattice of 10 points per wavelength only, on the device
     (True), over the whole padded surface boxes with colocation and resampling on the host (False), or per monitor (None: on the
     device where the whole-box accumulators of all its surfaces would exceed the threshold and the lattice holds fewer nodes).  The
     projected fields agree within a few fp32 roundings of the largest near field; coordinates, dtypes and files are the same.
@@ -185,6 +185,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         stats = eng.run(progress=progress if spec.decay_every else None)
         solve_s = time.perf_counter() - t0
         raw = eng.results()
+        from .projection import FLUX_SUFFIX
+        raw.update({name + FLUX_SUFFIX: fl for name, fl in eng.lattice_flux().items()})    # DirectivityMonitor surfaces on the device path
         steps_done = int(stats.steps_done)
         diverged = bool(stats.diverged)
         if stats.stopped_early:
