@@ -549,6 +549,41 @@ int fdtd_get_sweep_words(FdtdSolver* h, int64_t* out, int cap);
 /* Every instantiation the library holds, with W = 0: returns their number and fills min(number, cap) entries.  Needs no handle and no device. */
 int fdtd_sweep_table(int64_t* out, int cap);
 
+/* Staircase rasterisation of Box, Sphere and Cylinder structures on the device (ref simulation.py:1135-1241; the host form is
+ * tidy3d_amd/discretize.py rasterize, which the result equals bit for bit; csrc/fdtd_raster.hpp).  Needs no handle.
+ * The job: the grid shape; for each E component c its Yee coordinates along x, y, z (coords[3 c + a]: nx / ny / nz doubles); n records
+ * in the order of the structures.  A record paints, per component c, the nodes of the index box [lo[c], hi[c]) (x, y, z; an empty box
+ * paints nothing) that pass the primitive's inside test with medium[c]:
+ *   FDTD_RASTER_BOX       |p_a - center[a]| <= 0.5 size[a] on every axis a (size[a] may be inf)
+ *   FDTD_RASTER_SPHERE    (dx^2 + dy^2) + dz^2 <= size[0]                      size[0] = the squared radius as the caller evaluates it
+ *   FDTD_RASTER_CYLINDER  size[0] > 0, d0^2 + d1^2 <= size[0]^2 over the two axes other than `axis` (in x, y, z order) and
+ *                         |p_axis - center[axis]| <= 0.5 size[1]               size[0] = radius, size[1] = length (inf allowed)
+ * each operation in fp64, rounded once, in the order written.  out_host: uint16 [3][nz][ny][nx]; it starts as 1 (the background) and
+ * takes the records one after another on one stream — a later record overwrites an earlier one.  Refused with no launch: a null
+ * pointer, n == 0, an unknown kind, an index box outside the shape, a medium index that is no uint16, struct_bytes / record_bytes that
+ * are not this header's sizes.  Returns 0, or -1 with fdtd_last_error(NULL). */
+enum { FDTD_RASTER_BOX = 0, FDTD_RASTER_SPHERE = 1, FDTD_RASTER_CYLINDER = 2 };
+typedef struct FdtdRasterRecord {
+  int32_t kind;            /* FDTD_RASTER_*                                               */
+  int32_t axis;            /* cylinder: 0, 1, 2                                           */
+  int32_t medium[3];       /* table index per E component (0 = PEC)                       */
+  int32_t lo[3][3];        /* [component][x, y, z]                                        */
+  int32_t hi[3][3];
+  int32_t reserved;
+  double  center[3];
+  double  size[3];
+} FdtdRasterRecord;
+typedef struct FdtdRasterJob {
+  int32_t struct_bytes;    /* sizeof(FdtdRasterJob) of the caller                         */
+  int32_t record_bytes;    /* sizeof(FdtdRasterRecord) of the caller                      */
+  int32_t device;          /* HIP device ordinal                                          */
+  int32_t nx, ny, nz;
+  int64_t n;               /* records                                                     */
+  const double* coords[9];
+  const FdtdRasterRecord* records;
+} FdtdRasterJob;
+int fdtd_rasterize(const FdtdRasterJob* job, uint16_t* out_host);
+
 #ifdef __cplusplus
 }
 #endif

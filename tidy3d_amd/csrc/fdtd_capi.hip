@@ -31,6 +31,7 @@
 #include "fdtd_field_dft.hpp"
 #include "fdtd_lattice_dft.hpp"
 #include "fdtd_lattice_flux.hpp"
+#include "fdtd_raster.hpp"
 
 using namespace fdtd;
 
@@ -3258,6 +3259,90 @@ int fdtd_near_field(int device, int n_u, int n_v, const double* u, const double*
       rc = fail(nullptr, "fdtd_near_field: %s", hipGetErrorString(hipGetLastError()));
   }
   for (double* q : dev) if (q) hipFree(q);
+  return rc;
+}
+
+int fdtd_rasterize(const FdtdRasterJob* job, uint16_t* out_host) {
+  if (!job || !out_host) return fail(nullptr, "fdtd_rasterize: null argument");
+  if (job->struct_bytes != (int)sizeof(FdtdRasterJob) || job->record_bytes != (int)sizeof(FdtdRasterRecord))
+    return fail(nullptr, "fdtd_rasterize: job of %d bytes with records of %d: this library has %d and %d", job->struct_bytes,
+                job->record_bytes, (int)sizeof(FdtdRasterJob), (int)sizeof(FdtdRasterRecord));
+  if (!job->records) return fail(nullptr, "fdtd_rasterize: null argument");
+  for (int q = 0; q < 9; ++q)
+    if (!job->coords[q]) return fail(nullptr, "fdtd_rasterize: null argument");
+  if (job->n == 0) return fail(nullptr, "fdtd_rasterize: no records (n == 0)");
+  const int shape[3] = {job->nx, job->ny, job->nz};
+  if (job->n < 0 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1 || (long long)shape[0] * shape[1] * shape[2] >= (1LL << 32))
+    return fail(nullptr, "fdtd_rasterize: bad grid %d x %d x %d or record count %lld", shape[0], shape[1], shape[2], (long long)job->n);
+  long long launches = 0;
+  for (int64_t r = 0; r < job->n; ++r) {
+    const FdtdRasterRecord& rec = job->records[r];
+    if (rec.kind != FDTD_RASTER_BOX && rec.kind != FDTD_RASTER_SPHERE && rec.kind != FDTD_RASTER_CYLINDER)
+      return fail(nullptr, "fdtd_rasterize: record %lld: unknown kind %d", (long long)r, rec.kind);
+    if (rec.kind == FDTD_RASTER_CYLINDER && (rec.axis < 0 || rec.axis > 2))
+      return fail(nullptr, "fdtd_rasterize: record %lld: bad cylinder axis %d", (long long)r, rec.axis);
+    for (int c = 0; c < 3; ++c) {
+      if (rec.medium[c] < 0 || rec.medium[c] > 0xffff)
+        return fail(nullptr, "fdtd_rasterize: record %lld: medium index %d is no uint16", (long long)r, rec.medium[c]);
+      bool empty = false;
+      for (int a = 0; a < 3; ++a) {
+        if (rec.lo[c][a] < 0 || rec.hi[c][a] > shape[a])
+          return fail(nullptr, "fdtd_rasterize: record %lld, component %d: index box [%d, %d) along axis %d outside the shape (%d nodes)",
+                      (long long)r, c, rec.lo[c][a], rec.hi[c][a], a, shape[a]);
+        empty = empty || rec.lo[c][a] >= rec.hi[c][a];
+      }
+      if (!empty) ++launches;
+    }
+  }
+  // (grid.y = ceil(by / 4) and grid.z = bz of a launch are at most 65535: the node counts along y and z bound them)
+  if (shape[1] > 4 * 65535 || shape[2] > 65535)
+    return fail(nullptr, "fdtd_rasterize: %d x %d nodes along y, z exceed the launch grid", shape[1], shape[2]);
+  if (hipSetDevice(job->device) != hipSuccess) return fail(nullptr, "fdtd_rasterize: hipSetDevice(%d) failed", job->device);
+  const size_t cells = (size_t)shape[0] * shape[1] * shape[2], count = 3 * cells, n16 = (count + 7) / 8;
+  size_t off[10] = {0};
+  for (int q = 0; q < 9; ++q) off[q + 1] = off[q] + (size_t)shape[q % 3];
+  double* d_coords = nullptr;
+  uint4* d_out = nullptr;
+  hipStream_t st = nullptr;
+  int rc = 0;
+  if (hipMalloc((void**)&d_coords, off[9] * sizeof(double)) != hipSuccess || hipMalloc((void**)&d_out, n16 * sizeof(uint4)) != hipSuccess)
+    rc = fail(nullptr, "fdtd_rasterize: out of device memory (%zu bytes)", n16 * sizeof(uint4));
+  if (!rc && hipStreamCreate(&st) != hipSuccess) rc = fail(nullptr, "fdtd_rasterize: hipStreamCreate failed");
+  for (int q = 0; q < 9 && !rc; ++q)
+    if (hipMemcpyAsync(d_coords + off[q], job->coords[q], (size_t)shape[q % 3] * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+      rc = fail(nullptr, "fdtd_rasterize: upload failed");
+  if (!rc) {
+    const unsigned blocks = (unsigned)std::min<size_t>((n16 + 255) / 256, 1u << 16);
+    hipLaunchKernelGGL(raster_fill_kernel, dim3(blocks), dim3(256), 0, st, d_out, (long long)n16, 1u);
+    for (int64_t r = 0; r < job->n; ++r) {
+      const FdtdRasterRecord& rec = job->records[r];
+      for (int c = 0; c < 3; ++c) {
+        RasterP p;
+        p.xs = d_coords + off[3 * c]; p.ys = d_coords + off[3 * c + 1]; p.zs = d_coords + off[3 * c + 2];
+        p.out = reinterpret_cast<unsigned short*>(d_out) + (size_t)c * cells;
+        p.nx = shape[0]; p.ny = shape[1];
+        p.lo0 = rec.lo[c][0]; p.lo1 = rec.lo[c][1]; p.lo2 = rec.lo[c][2];
+        p.hi0 = rec.hi[c][0]; p.hi1 = rec.hi[c][1]; p.hi2 = rec.hi[c][2];
+        if (p.lo0 >= p.hi0 || p.lo1 >= p.hi1 || p.lo2 >= p.hi2) continue;
+        p.c0 = rec.center[0]; p.c1 = rec.center[1]; p.c2 = rec.center[2];
+        p.s0 = rec.size[0]; p.s1 = rec.size[1]; p.s2 = rec.size[2];
+        p.axis = rec.axis;
+        p.medium = (unsigned short)rec.medium[c];
+        const dim3 grid((unsigned)((p.hi0 - p.lo0 + kRasterLanes - 1) / kRasterLanes),
+                        (unsigned)((p.hi1 - p.lo1 + kRasterRows - 1) / kRasterRows), (unsigned)(p.hi2 - p.lo2));
+        const dim3 block(kRasterLanes, kRasterRows);
+        if (rec.kind == FDTD_RASTER_BOX) hipLaunchKernelGGL(raster_paint_kernel<kRasterBox>, grid, block, 0, st, p);
+        else if (rec.kind == FDTD_RASTER_SPHERE) hipLaunchKernelGGL(raster_paint_kernel<kRasterSphere>, grid, block, 0, st, p);
+        else hipLaunchKernelGGL(raster_paint_kernel<kRasterCylinder>, grid, block, 0, st, p);
+      }
+    }
+    if (hipMemcpyAsync(out_host, d_out, count * sizeof(uint16_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      rc = fail(nullptr, "fdtd_rasterize: %s", hipGetErrorString(hipGetLastError()));
+  }
+  if (st) hipStreamDestroy(st);
+  if (d_coords) hipFree(d_coords);
+  if (d_out) hipFree(d_out);
   return rc;
 }
 

@@ -43,7 +43,7 @@ SYMBOLS = (
     "fdtd_add_field_time_monitor", "fdtd_add_field_dft_monitor", "fdtd_add_lattice_dft_monitor", "fdtd_add_modulation",
     "fdtd_add_pec_conformal", "fdtd_add_nonlinear",
     "fdtd_near_field", "fdtd_near_field_chunks",
-    "fdtd_set_lattice_flux_weights", "fdtd_lattice_flux",
+    "fdtd_set_lattice_flux_weights", "fdtd_lattice_flux", "fdtd_rasterize",
 )
 
 BC_PEC, BC_PMC, BC_PERIODIC, BC_NEIGHBOR = 0, 1, 2, 3
@@ -89,6 +89,21 @@ class FdtdStats(C.Structure):
 class FdtdSeamStats(C.Structure):
     _fields_ = [("seam_deferred_pairs", C.c_int64), ("seam_flushes", C.c_int64), ("seam_pending", C.c_int32),
                 ("reserved", C.c_int32), ("seam_flush_ms", C.c_double)]
+
+
+RASTER_BOX, RASTER_SPHERE, RASTER_CYLINDER = 0, 1, 2
+
+
+class FdtdRasterRecord(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("axis", C.c_int32), ("medium", C.c_int32 * 3),
+                ("lo", (C.c_int32 * 3) * 3), ("hi", (C.c_int32 * 3) * 3), ("reserved", C.c_int32),
+                ("center", C.c_double * 3), ("size", C.c_double * 3)]
+
+
+class FdtdRasterJob(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("record_bytes", C.c_int32), ("device", C.c_int32),
+                ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("n", C.c_int64),
+                ("coords", C.c_void_p * 9), ("records", C.POINTER(FdtdRasterRecord))]
 
 
 def unpack_sweep_word(word: int):
@@ -160,6 +175,24 @@ class FdtdLib:
         d.fdtd_far_field.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, f64, f64, f64, C.c_int, vp, vp, vp, vp]
         d.fdtd_near_field.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, f64, f64, f64, C.c_int, vp, vp, vp, vp]
         d.fdtd_near_field_chunks.argtypes = [C.c_int, C.c_int, C.c_int]
+        d.fdtd_rasterize.argtypes = [C.POINTER(FdtdRasterJob), vp]
+
+    def rasterize(self, shape, coords, records, device: int = 0):
+        """``fdtd_rasterize``: the records (``FdtdRasterRecord``, in the order of the structures) painted over a background of 1 on the
+        device -> uint16 [3, nz, ny, nx].  ``coords``: per E component its (x, y, z) Yee coordinates."""
+        import numpy as np
+        nx, ny, nz = (int(v) for v in shape)
+        keep = [np.ascontiguousarray(coords[c][a], dtype=np.float64) for c in range(3) for a in range(3)]
+        assert all(keep[3 * c + a].size == (nx, ny, nz)[a] for c in range(3) for a in range(3))
+        job = FdtdRasterJob(struct_bytes=C.sizeof(FdtdRasterJob), record_bytes=C.sizeof(FdtdRasterRecord), device=int(device),
+                            nx=nx, ny=ny, nz=nz, n=len(records))
+        for q, a in enumerate(keep):
+            job.coords[q] = a.ctypes.data
+        recs = (FdtdRasterRecord * max(len(records), 1))(*records)
+        job.records = recs
+        out = np.empty((3, nz, ny, nx), dtype=np.uint16)
+        self.check(self.dll.fdtd_rasterize(C.byref(job), out.ctypes.data_as(C.c_void_p)), None, "fdtd_rasterize")
+        return out
 
     def far_field(self, u, v, wu, wv, currents, w0: float, k: complex, r_u, r_v, r_w, device: int = 0):
         """Surface integrals of the near -> far projection on the device (``fdtd_far_field``): ``currents`` [4, n_u, n_v]

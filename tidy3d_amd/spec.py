@@ -300,6 +300,7 @@ class SolverSpec:
     shutoff: float = 0.0                                # 0 disables the early stop
     decay_every: int = 0                                # 0 = never evaluate field decay
     decay_ref_step: int = 0                             # steps before this never shut off
+    raster_log: str = ""                                # what discretize.rasterize did, as SimulationData.log words it
 
     def __post_init__(self):
         if self.pml is None:

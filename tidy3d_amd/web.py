@@ -96,7 +96,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         return_tidy3d: Optional[bool] = None, devices=None, _dist_options: Optional[dict] = None,
         mode_grid_dispersion: Optional[bool] = None, flux_time_device: Optional[bool] = None,
         field_time_device: Optional[bool] = None, field_dft_device: Optional[bool] = None,
-        projection_device: Optional[bool] = None, exact_projection_device: Optional[bool] = None) -> SimulationData:
+        projection_device: Optional[bool] = None, exact_projection_device: Optional[bool] = None,
+        rasterize_device: Optional[bool] = None) -> SimulationData:
     """Solve ``simulation`` on the local MI355X and return its ``SimulationData``.
 
     Cloud-only arguments (``folder_name``, ``callback_url``, ``progress_callback_*``,
@@ -123,7 +124,11 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     ``exact_projection_device``: where angle and Cartesian projection monitors with ``far_field_approx=False`` take their surface
     integrals after the run — on the device in fp64 (True: ``fdtd_near_field``), in NumPy on the host (False), or per monitor (None: on
     the device from ``projection.EXACT_HOST_PAIRS`` point-node pairs on); ``SimulationData.log`` names the path per monitor.  With
-    more than one GPU in ``devices`` the first one integrates."""
+    more than one GPU in ``devices`` the first one integrates.  ``rasterize_device``: paint Box, Sphere and Cylinder structures into
+    the material volumes on the device during set-up (True; a scene with any other geometry, a Custom* medium, a Medium2D sheet or a
+    medium of the whole-grid node lists takes the host path as a whole), on the host (False), or by
+    ``discretize.RASTER_DEVICE_CELLS`` (None: the host); the volumes are the same bit for bit and ``SimulationData.log`` names the
+    path.  One-GPU runs: with more than one GPU in ``devices`` every rank rasterises on the host, and True is refused."""
     from .engine import HipEngine
 
     sim, was_tidy3d = _as_mirror(simulation)
@@ -132,6 +137,9 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     paths = DevicePaths(flux_time_device, field_time_device, field_dft_device, projection_device)
     if devices is not None and len(devices) > 1:
         _device_refusals(sim, paths, "devices= with more than one GPU")
+        if rasterize_device:
+            raise Tidy3dNotImplementedError("rasterize_device=True (structures rasterised on the device) together with devices= with "
+                                            "more than one GPU is not supported; rasterize_device=None or False keeps the host path")
         from .conformal import pec_conformal_of
         from .engine import refuse_together
         media = [m for m in sim.mediums if isinstance(m, td.Medium)]
@@ -155,7 +163,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
     t_setup = time.perf_counter()
-    disc = discretize(sim, n_steps=n_steps, mode_grid_dispersion=mode_grid_dispersion, device_paths=paths)
+    disc = discretize(sim, n_steps=n_steps, mode_grid_dispersion=mode_grid_dispersion, device_paths=paths,
+                      rasterize_device=rasterize_device, lib=lib, gpu=device)
     spec = disc.spec
     lines = [f"Simulation domain Nx, Ny, Nz: {list(spec.shape)}",
              f"Applied symmetries: {tuple(sim.symmetry)}",
@@ -163,6 +172,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
              f"Number of time steps: {spec.n_steps:.4e}",
              f"Time step size (dt): {spec.dt:.4e}s", "",
              "Running solver for %d time steps..." % spec.n_steps]
+    if spec.raster_log:
+        lines[-2:-2] = spec.raster_log.splitlines()
     if spec.conformal:
         lines.insert(-2, "PEC-conformal boundaries (Dey-Mittra): %d cut faces listed; single time steps."
                      % sum(len(cs.ijk) for cs in spec.conformal))
