@@ -165,14 +165,26 @@ def bloch_xy():
     return spec
 
 
+def small_at_wall():
+    """12 x 12 x 12 PEC box with a PMC wall at x- (8^3 leaves over 10 % of its nodes pinned: list_case.SHARE_CAP), a modulated body of 2 x 2 x 2 cells
+    against the x+ wall: lists shorter than a wavefront"""
+    body = td.Structure(geometry=td.Box(center=(5 * DL, 0.0, 0.0), size=(2 * DL,) * 3), medium=eps_modulated(eps=3.0, amp=0.8))
+    walls = td.BoundarySpec(x=td.Boundary(minus=td.PMCBoundary(), plus=td.PECBoundary()), y=_pec(), z=_pec())
+    spec = _spec(_box_sim((12, 12, 12), walls, [body]))
+    assert spec.shape == (12, 12, 12) and max(len(m.ijk) for m in spec.modulation) < 64
+    return spec
+
+
 SCENARIOS = {"pec_box_blocks": pec_box_blocks, "seam_bar": seam_bar, "pml_slab": pml_slab, "graded_travelling_wave": graded_travelling_wave,
              "bloch_xy": bloch_xy}
+EXTRA = {"small_at_wall": small_at_wall}          # (not in the emulator's committed record)
 PATHS = lc.PATHS
 GOLDEN = lc.golden("modulation")
 
 
 class Scenario(lc.Scenario):
     ATTR, TAG, ORACLE, SCENARIOS, BAR, GOLDEN = "modulation", "modulation", ModulatedOracle, SCENARIOS, BAR, GOLDEN
+    EXTRA = EXTRA
 
 
 def scenario(label):
@@ -197,6 +209,7 @@ def check_scenario(lib, label, K, what=""):
         err = sc.errors(got[p].fields, K)
         print(f"[modulation] {label} K={K} {what}{p}: rel-L2 per field " + " ".join(f"{e:.2e}" for e in err) + f" | off-reason {got[p].why}")
         worst = max(worst, max(err))
+        sc.check_nodes(got[p].fields, K, what + p)          # the same run, node by node: its message says where
         assert max(err) <= BAR, (label, K, p, err)
     lin = {p: sc.run(lib, K, p, plain=True) for p in PATHS}
     if all(np.array_equal(lin["fused"].fields[c], lin["twopass"].fields[c]) for c in range(6)):

@@ -168,8 +168,21 @@ def graded_two_media():
     return spec
 
 
+def small_at_wall():
+    """12 x 12 x 12 PEC box with a PMC wall at x- (8^3 leaves over 10 % of its nodes pinned: list_case.SHARE_CAP; across a PMC wall the
+    nodes a slot beyond the x+ wall would wrap to are live, behind a PEC wall they are pinned and a wrongly filled slot reads 0), a Kerr body of 3 x 3 x 3 cells against the
+    x+ wall: lists shorter than a wavefront, E_x nodes whose slots reach beyond the wall.  (Where the body lies decides whether the
+    state keeps |chi3| I / eps_bar inside RANGE for seven steps; a body of 2 x 2 x 2 cells on the axis falls to 0.02.)"""
+    body = _bx((4.5 * mc.DL, 0.5 * mc.DL, -0.5 * mc.DL), (3 * mc.DL,) * 3, kerr(eps=3.0))
+    walls = td.BoundarySpec(x=td.Boundary(minus=td.PMCBoundary(), plus=td.PECBoundary()), y=mc._pec(), z=mc._pec())
+    spec = mc._spec(mc._box_sim((12, 12, 12), walls, [body], sources=(DIPOLE,)))
+    assert spec.shape == (12, 12, 12) and max(len(s.ijk) for s in spec.nonlinear) < 64
+    return spec
+
+
 SCENARIOS = {"pec_box_blocks": pec_box_blocks, "seam_bar": seam_bar, "periodic_xy": periodic_xy, "pml_slab": pml_slab,
              "graded_two_media": graded_two_media}
+EXTRA = {"small_at_wall": small_at_wall}          # (not in the emulator's committed record)
 PATHS = lc.PATHS
 GOLDEN = lc.golden("nonlinear")
 
@@ -191,6 +204,7 @@ def with_lists(spec, scale=1.0, num_iters=None, reverse=False):
 class Scenario(lc.Scenario):
     """chi3 scaled to the state; the fp64 references per (K, num_iters)"""
     ATTR, TAG, ORACLE, SCENARIOS, BAR, GOLDEN = "nonlinear", "nonlinear", NonlinearOracle, SCENARIOS, BAR, GOLDEN
+    EXTRA = EXTRA
 
     def __init__(self, label):
         super().__init__(label)
@@ -215,6 +229,18 @@ class Scenario(lc.Scenario):
 
     def errors(self, fields, K, num_iters=5):
         return super().errors(fields, K, num_iters)
+
+    def measure(self, fields, K, num_iters=5, ref=None):
+        return super().measure(fields, K, num_iters, ref=ref)
+
+    def floor(self, K, num_iters=5):
+        return super().floor(K, num_iters)
+
+    def bar_nodes(self, K, num_iters=5):
+        return super().bar_nodes(K, num_iters)
+
+    def check_nodes(self, fields, K, what, num_iters=5):
+        return super().check_nodes(fields, K, what, num_iters)
 
     def run(self, lib, K, path, num_iters=5, plain=False, **kw):
         spec = self.plain if plain else with_lists(self.spec, num_iters=num_iters, **kw)
@@ -247,6 +273,7 @@ def check_scenario(lib, label, K, num_iters, what=""):
         print(f"[nonlinear] {label} K={K} iters={num_iters} {what}{p}: rel-L2 per field " + " ".join(f"{e:.2e}" for e in err)
               + f" | off-reason {got[p].why}")
         worst = max(worst, max(err))
+        sc.check_nodes(got[p].fields, K, what + p, num_iters)          # the same run, node by node: its message says where
         assert max(err) <= BAR, (label, K, num_iters, p, err)
     for c in range(6):
         assert np.array_equal(got["fused"].fields[c], got["twopass"].fields[c]), (label, K, num_iters, ds.COMP[c])

@@ -265,16 +265,29 @@ def periodic_sphere():
     return spec
 
 
+def small_at_wall():
+    """12 x 12 x 12 PEC box with a PMC wall at x- (8^3 leaves over 10 % of its nodes pinned: list_case.SHARE_CAP; across a PMC wall the
+    edges a slot beyond the x+ wall would wrap to are live), a PEC sphere of radius 1.4 cells through the
+    x+ wall: lists shorter than a wavefront, faces whose edges lie beyond the wall"""
+    body = td.Structure(geometry=td.Sphere(center=(4.9 * DL, 0.1 * DL, -0.2 * DL), radius=1.4 * DL), medium=td.PEC)
+    walls = td.BoundarySpec(x=td.Boundary(minus=td.PMCBoundary(), plus=td.PECBoundary()), y=_pec(), z=_pec())
+    spec = _spec(_box_sim((12, 12, 12), walls, [body]))
+    assert spec.shape == (12, 12, 12) and max(len(c.ijk) for c in spec.conformal) < 64
+    return spec
+
+
 SCENARIOS = {"sphere_blocks": sphere_blocks, "seam_cylinder": seam_cylinder, "pml_tilted_slab": pml_tilted_slab,
              "graded_sphere": graded_sphere, "periodic_sphere": periodic_sphere}
+EXTRA = {"small_at_wall": small_at_wall}          # (not in the emulator's committed record)
 # label -> (scenario, axis_shift): the first scenario under the other two axis renamings as well
-RUNS = {**{k: (k, 0) for k in SCENARIOS}, "sphere_blocks_shift1": ("sphere_blocks", 1), "sphere_blocks_shift2": ("sphere_blocks", 2)}
+RUNS = {**{k: (k, 0) for k in (*SCENARIOS, *EXTRA)}, "sphere_blocks_shift1": ("sphere_blocks", 1), "sphere_blocks_shift2": ("sphere_blocks", 2)}
 PATHS = lc.PATHS
 GOLDEN = lc.golden("pec_conformal")
 
 
 class Scenario(lc.Scenario):
     ATTR, TAG, ORACLE, SCENARIOS, BAR, GOLDEN = "conformal", "pec-conformal", ConformalOracle, SCENARIOS, BAR, GOLDEN
+    EXTRA = EXTRA
 
 
 def scenario(label):
@@ -300,6 +313,7 @@ def check_run(lib, run_label, K, what=""):
         err = sc.errors(got[p].fields, K)
         print(f"[pec-conformal] {run_label} K={K} {what}{p}: rel-L2 per field " + " ".join(f"{e:.2e}" for e in err) + f" | off-reason {got[p].why}")
         worst = max(worst, max(err))
+        sc.check_nodes(got[p].fields, K, what + p + (f" shift {shift}" if shift else ""))          # the same run, node by node: its message says where
         assert max(err) <= BAR, (run_label, K, p, err)
     lin = {p: sc.run(lib, K, p, plain=True, axis_shift=shift) for p in PATHS}
     if all(np.array_equal(lin["fused"].fields[c], lin["twopass"].fields[c]) for c in range(6)):

@@ -169,7 +169,7 @@ def test_scenario_can_see_the_feature(label):
 
 
 @pytest.mark.parametrize("K", mc.KS)
-@pytest.mark.parametrize("label", list(mc.SCENARIOS))
+@pytest.mark.parametrize("label", mc.Scenario.all_labels())
 def test_scenario_matches_the_modulated_oracle(label, K, emu_lib):
     mc.check_scenario(emu_lib, label, K)
 

@@ -204,7 +204,7 @@ def test_iterations_are_counted():
 
 @pytest.mark.parametrize("num_iters", nc.ITERS)
 @pytest.mark.parametrize("K", nc.KS)
-@pytest.mark.parametrize("label", list(nc.SCENARIOS))
+@pytest.mark.parametrize("label", nc.Scenario.all_labels())
 def test_scenario_matches_the_nonlinear_oracle(label, K, num_iters, emu_lib):
     nc.check_scenario(emu_lib, label, K, num_iters)
 
@@ -235,6 +235,9 @@ def test_axis_renamings(shift, emu_lib):
         assert t.comp == (s.comp - shift) % 3 and t.nbr_comp == ((t.comp + 1) % 3,) * 4 + ((t.comp + 2) % 3,) * 4
     got = ds.run_engine(sc.spec, emu_lib, sc.state, 7, "fused", axis_shift=shift)
     assert max(sc.errors(got.fields, 7)) <= nc.BAR
+    sc.check_nodes(got.fields, 7, f"fused shift {shift}")
+    for K in nc.KS[:-1]:                                     # node by node at the other step counts as well
+        sc.check_nodes(ds.run_engine(sc.spec, emu_lib, sc.state, K, "fused", axis_shift=shift).fields, K, f"fused shift {shift}")
 
 
 def test_the_emulator_record_is_current(emu_lib):

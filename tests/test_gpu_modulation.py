@@ -19,12 +19,12 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("K", mc.KS)
-@pytest.mark.parametrize("label", list(mc.SCENARIOS))
+@pytest.mark.parametrize("label", mc.Scenario.all_labels())
 def test_scenario_matches_the_modulated_oracle(label, K, hip_lib):
     sc = mc.scenario(label)
     assert sc.visibility(K) >= 100 * mc.BAR
     _, got = mc.check_scenario(hip_lib, label, K, what="device ")
-    if K == 7:
+    if K == 7 and label in mc.SCENARIOS:
         mc.check_against_emulator_record(label, got["fused"].fields)
 
 

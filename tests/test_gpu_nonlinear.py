@@ -17,12 +17,12 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("num_iters", nc.ITERS)
 @pytest.mark.parametrize("K", nc.KS)
-@pytest.mark.parametrize("label", list(nc.SCENARIOS))
+@pytest.mark.parametrize("label", nc.Scenario.all_labels())
 def test_scenario_matches_the_nonlinear_oracle(label, K, num_iters, hip_lib):
     sc = nc.scenario(label)
     assert sc.visibility(K) >= 100 * nc.BAR
     _, got = nc.check_scenario(hip_lib, label, K, num_iters, what="device ")
-    if K == 7 and num_iters == 5:
+    if K == 7 and num_iters == 5 and label in nc.SCENARIOS:
         nc.check_against_emulator_record(label, got["fused"].fields)
 
 
