@@ -10,6 +10,7 @@ import tidy3d_amd.schema as td
 from tidy3d_amd import lib as L
 from tidy3d_amd.discretize import discretize
 from tidy3d_amd.engine import HipEngine
+from tidy3d_amd.spec import PointSourceSet
 
 DL = 0.05
 PULSE = td.GaussianPulse(freq0=3e14, fwidth=1.5e14)
@@ -104,6 +105,50 @@ def test_current_sheets_through_the_cpml_layers(N, w, zc, axis, emu_lib):
     disc = discretize(sim(N, PML, srcs, [BALL], MON), n_steps=40)
     disc.spec.decay_every = 0
     check(disc.spec, emu_lib, w + 64 * zc, (11, 16, 13), shell2=1, seed=4)
+
+
+def one_list(spec, a, b):
+    """the point lists a and b of the spec (one pulse) as ONE list: E nodes and H nodes arrive in one fdtd_add_point_source call, as the
+    electric and magnetic currents of a mode source do"""
+    sa, sb = spec.sources[a], spec.sources[b]
+    assert np.array_equal(sa.wave_e, sb.wave_e) and np.array_equal(sa.wave_h, sb.wave_h)
+    assert (sa.comp < 3).any() and (sb.comp >= 3).any()
+    both = PointSourceSet(comp=np.concatenate([sa.comp, sb.comp]), ijk=np.concatenate([sa.ijk, sb.ijk]), w_re=np.concatenate([sa.w_re, sb.w_re]),
+                          w_im=np.concatenate([sa.w_im, sb.w_im]), wave_e=sa.wave_e, wave_h=sa.wave_h, name="both")
+    spec.sources = [s for q, s in enumerate(spec.sources) if q not in (a, b)] + [both]
+
+
+@pytest.mark.parametrize("N,w,zc,axis", [((40, 30, 28), 5, 3, 1), ((300, 26, 24), 6, 4, 2)])
+def test_one_list_with_electric_and_magnetic_sheets(N, w, zc, axis, emu_lib):
+    """ONE list that holds an electric and a magnetic current sheet through the CPML layers (hundreds of E nodes and of H nodes): both
+    sides of a point list take slots, layers and paged terms (the H side those of step n + 1), and with FDTD_OPT_SRC_PAGED = 0 both
+    sides' planes are z holes.  The wide grid puts E_x and H_y nodes of the sheets on both sides of the seam at column 256."""
+    size, centre_e, centre_h = [td.inf] * 3, [0.0] * 3, [0.0] * 3
+    size[axis] = 0
+    centre_e[axis], centre_h[axis] = 0.23, -0.17
+    pol = ("Ez", "Hz") if axis != 2 else ("Ex", "Hy")
+    srcs = [td.UniformCurrentSource(center=tuple(centre_e), size=tuple(size), source_time=PULSE, polarization=pol[0]),
+            td.UniformCurrentSource(center=tuple(centre_h), size=tuple(size), source_time=PULSE, polarization=pol[1])]
+    disc = discretize(sim(N, PML, srcs, [BALL], MON), n_steps=40)
+    disc.spec.decay_every = 0
+    one_list(disc.spec, 0, 1)
+    assert len(disc.spec.sources) == 1
+    check(disc.spec, emu_lib, w + 64 * zc, (11, 16, 13), shell2=1, seed=4)
+
+
+def test_one_list_with_electric_and_magnetic_dipoles_in_the_node_table(emu_lib):
+    """ONE list of a few E nodes and H nodes, small enough for the sweep's node table (no paging): the table lists the E nodes, then the H
+    nodes (codes 3 - 5, their terms of step n + 1) of the list, at the offsets the table of all steps gives them"""
+    srcs = [td.PointDipole(center=(0.02, 0.01, 0.03), source_time=PULSE, polarization="Ey"),
+            td.PointDipole(center=(-0.1, 0.05, -0.04), source_time=PULSE, polarization="Hx")]
+    disc = discretize(sim((40, 30, 28), PEC, srcs, [BALL], MON), n_steps=40)
+    disc.spec.decay_every = 0
+    one_list(disc.spec, 0, 1)
+    ref = run(disc.spec, emu_lib, 0, (11, 16, 13))
+    got = run(disc.spec, emu_lib, 5 + 64 * 3, (11, 16, 13))
+    assert ref[2] == 0 and got[2] >= 5 + 8 + 6 and got[3] == 0, got[2:]
+    assert max(float(np.abs(f).max()) for f in ref[0]) > 0
+    same(ref, got)
 
 
 def test_tfsf_box_and_dispersive_sphere_in_cpml(emu_lib):

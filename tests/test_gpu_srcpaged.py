@@ -101,6 +101,75 @@ def _run(spec, lib, runs, twostep=-1, paged=-1):
         return [e.get_field(c) for c in range(6)], e.results(), pairs, sp, dp
 
 
+def _small(spec, lib, twostep, runs, paged=-1, shell2=None):
+    with HipEngine(spec, lib=lib, variant=L.VARIANT_FUSED, axis_shift=0) as e:
+        e.set_option(L.OPT_PLACEMENT_TRIES, 0)
+        e.set_option(L.OPT_TWOSTEP, twostep)
+        if paged >= 0:
+            e.set_option(L.OPT_SRC_PAGED, paged)
+        if shell2 is not None:
+            e.set_option(L.OPT_SHELL_PAIRS, 1)
+            e.set_option(L.OPT_SHELL2, shell2)
+        rng = np.random.default_rng(4)
+        for c in range(6):
+            f = e.get_field(c)
+            e.set_field(c, ((1e-3 if c < 3 else 1e-3 / 376.73) * rng.uniform(-1, 1, size=f.shape)).astype(np.float32))
+        pairs = sp = 0
+        for r in runs:
+            st = e.run(r)
+            pairs += int(st.fused2_pairs)
+            sp += int(st.src_paged_pairs)
+        return [e.get_field(c) for c in range(6)], e.results(), pairs, sp
+
+
+def _same(ref, got):
+    for c in range(6):
+        assert np.array_equal(got[0][c], ref[0][c]), (c, float(np.abs(got[0][c] - ref[0][c]).max()))
+    for k in ref[1]:
+        assert np.array_equal(np.asarray(got[1][k]), np.asarray(ref[1][k])), k
+
+
+@pytest.mark.parametrize("N,w,zc,axis", [((40, 30, 28), 6, 5, 1), ((300, 26, 24), 8, 8, 2)])
+def test_one_list_with_electric_and_magnetic_sheets(N, w, zc, axis, hip_lib):
+    """the device twin of tests/test_emu_srcpaged.py's case of the same name: ONE point list with an electric and a magnetic current
+    sheet through the CPML layers, pairs == single steps == the schedule without paging, bit for bit"""
+    import test_emu_srcpaged as emu
+    size, centre_e, centre_h = [td.inf] * 3, [0.0] * 3, [0.0] * 3
+    size[axis] = 0
+    centre_e[axis], centre_h[axis] = 0.23, -0.17
+    pol = ("Ez", "Hz") if axis != 2 else ("Ex", "Hy")
+    srcs = [td.UniformCurrentSource(center=tuple(centre_e), size=tuple(size), source_time=emu.PULSE, polarization=pol[0]),
+            td.UniformCurrentSource(center=tuple(centre_h), size=tuple(size), source_time=emu.PULSE, polarization=pol[1])]
+    disc = discretize(emu.sim(N, emu.PML, srcs, [emu.BALL], emu.MON), n_steps=40)
+    disc.spec.decay_every = 0
+    emu.one_list(disc.spec, 0, 1)
+    runs = (11, 16, 13)
+    ref = _small(disc.spec, hip_lib, 0, runs, shell2=1)
+    got = _small(disc.spec, hip_lib, w + 64 * zc, runs, shell2=1)
+    off = _small(disc.spec, hip_lib, w + 64 * zc, runs, paged=0, shell2=1)
+    assert ref[2] == 0 and got[3] > 0 and got[2] >= sum(r // 2 for r in runs), got[2:]
+    assert off[3] == 0 and off[2] < got[2], (off[2:], got[2:])
+    assert max(float(np.abs(f).max()) for f in ref[0]) > 0
+    _same(ref, got)
+    _same(ref, off)
+
+
+def test_one_list_with_electric_and_magnetic_dipoles_in_the_node_table(hip_lib):
+    """the device twin of the emulator's case: E nodes and H nodes of ONE small list through the sweep's node table (no paging)"""
+    import test_emu_srcpaged as emu
+    srcs = [td.PointDipole(center=(0.02, 0.01, 0.03), source_time=emu.PULSE, polarization="Ey"),
+            td.PointDipole(center=(-0.1, 0.05, -0.04), source_time=emu.PULSE, polarization="Hx")]
+    disc = discretize(emu.sim((40, 30, 28), emu.PEC, srcs, [emu.BALL], emu.MON), n_steps=40)
+    disc.spec.decay_every = 0
+    emu.one_list(disc.spec, 0, 1)
+    runs = (11, 16, 13)
+    ref = _small(disc.spec, hip_lib, 0, runs)
+    got = _small(disc.spec, hip_lib, 8 + 64 * 8, runs)
+    assert ref[2] == 0 and got[2] >= sum(r // 2 for r in runs) and got[3] == 0, got[2:]
+    assert max(float(np.abs(f).max()) for f in ref[0]) > 0
+    _same(ref, got)
+
+
 @pytest.mark.parametrize("kind,n", [("mie", 320), ("mie_lorentz", 320), ("sheet_x", 344), ("sheet_y", 344)])
 def test_pairs_while_lists_inject_bit_identical_to_single_steps(kind, n, hip_lib):
     runs = (7, 30, 9)

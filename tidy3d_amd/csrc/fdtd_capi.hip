@@ -75,16 +75,32 @@ struct AdeGroup {
   uint32_t* qoff = nullptr;        // slot of entry t in the paged arrays (Disp)
 };
 
+// Which block of paged storage a row segment (256 cells of one row) owns: the map both pagings (Disp, SrcPaged) address their
+// arrays by, on the device for the kernels and on the host for the tile classes and the shell's boxes.  seg_map_build lays it out.
+struct SegMap {
+  int* dev = nullptr;              // [nz][ny][nbx]: block of the row segment, -1 = none
+  std::vector<int> host;           // the same (empty: not built)
+  int n_blocks = 0;
+  // does a row segment of planes k0 .. k1, rows j0 .. j1, x-tiles t0 .. t1 (inclusive; clamped to the grid here) own a block?
+  bool any(const GridP& g, int k0, int k1, int j0, int j1, int t0, int t1) const {
+    const int nbx = (g.nx + 255) / 256;
+    if (host.empty()) return false;
+    for (int k = std::max(k0, 0); k <= std::min(k1, g.nz - 1); ++k)
+      for (int j = std::max(j0, 0); j <= std::min(j1, g.ny - 1); ++j)
+        for (int t = std::max(t0, 0); t <= std::min(t1, nbx - 1); ++t)
+          if (host[((size_t)k * g.ny + j) * nbx + t] >= 0) return true;
+    return false;
+  }
+};
+
 // Dispersive cells in step pairs (round 6; fdtd_fused2.hpp DispP).  What a two-step sweep needs of the ADE update of its first step is
 // the memory term cc S(Q^n) at the dispersive cells — known before the sweep starts.  Once a run may take such pairs it is kept in
 // paged storage (`cs`: one block per row segment that holds a dispersive cell) by every ADE kernel of this handle; the sweep subtracts
 // it and leaves E^{n+1} in `e1`; ade2_kernel behind the sweep advances the pole states two steps.  The lists stay what they were.
 struct Disp {
   int state = 0;                   // 0 = not tried, 1 = ready, -1 = this problem cannot
-  int n_blocks = 0;
-  int* dseg = nullptr;             // [nz][ny][nbx]
-  std::vector<int> dseg_host;
-  float* cs = nullptr;             // [n_blocks][3][256]
+  SegMap seg;                      // the row segments that hold a dispersive cell (DispP::dseg)
+  float* cs = nullptr;             // [seg.n_blocks][3][256]
   float* e1 = nullptr;
   int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};     // bounding box of the dispersive cells [lo, hi)
   long long pairs = 0;             // pairs of the last run whose sweep carried the ADE update of its first step
@@ -123,24 +139,33 @@ constexpr struct { const char* noun; int f2_off; bool early; const char* bloch_l
     {"PEC-conformal boundaries", FDTD_F2_OFF_CONFORMAL, true, "PEC-conformal lists"},
     {"nonlinear media", FDTD_F2_OFF_NONLINEAR, true, nullptr}};
 
+// The points of one side (E or H components) of a point-source list (point_source_kernel).  PointSide and TfsfList name what the paged
+// source terms need of a side alike: n, cell, comp, soff, layer (for_each_source_side).
+struct PointSide {
+  long long n = 0;
+  int k0 = 0, k1 = 0;              // planes [k0, k1) that hold its points
+  int32_t* comp = nullptr;
+  uint32_t* cell = nullptr;
+  float *wre = nullptr, *wim = nullptr;
+  float2* wave = nullptr;
+  uint32_t* soff = nullptr;        // slots of the nodes in the paged source terms (SrcPaged)
+  int layer = 0;                   // their layer
+  std::vector<int32_t> host_comp;  // host copies of the nodes (the two-step sweep applies them in-kernel)
+  std::vector<uint32_t> host_cell;
+};
 struct PointSrc {
-  long long n_e = 0, n_h = 0;      // points split by E / H components
-  int32_t *comp_e = nullptr, *comp_h = nullptr;
-  uint32_t *cell_e = nullptr, *cell_h = nullptr;
-  float *wre_e = nullptr, *wim_e = nullptr, *wre_h = nullptr, *wim_h = nullptr;
-  float2 *wave_e = nullptr, *wave_h = nullptr;
   long long n_steps = 0;
-  int ke0 = 0, ke1 = 0, kh0 = 0, kh1 = 0;   // planes [k0, k1) that hold its E / H points
-  uint32_t *soff_e = nullptr, *soff_h = nullptr;   // slots of the nodes in the paged source terms (SrcPaged)
-  int layer_e = 0, layer_h = 0;                    // their layers
-  std::vector<int32_t> host_comp_e, host_comp_h;   // host copies of the nodes (the two-step sweep applies them in-kernel)
-  std::vector<uint32_t> host_cell_e, host_cell_h;
+  PointSide e, h;
+  const PointSide& side(bool e_side) const { return e_side ? e : h; }
+  bool has_nodes() const { return e.n || h.n; }
+  bool alive(long long n) const { return has_nodes() && n < n_steps; }       // the list injects at step n
+  bool e_due(long long n) const { return e.n && n < n_steps; }               // its E side injects at step n
 };
 
 // correction list of one side (E or H) of a TFSF box, grouped by target node (tfsf_corr_kernel)
 struct TfsfList {
   int k0 = 0, k1 = 0;              // planes [k0, k1) that hold its target nodes
-  long long n_targets = 0;
+  long long n = 0;                 // target nodes
   int32_t *comp = nullptr, *start = nullptr, *aux = nullptr;
   uint32_t* cell = nullptr;
   float* w = nullptr;
@@ -223,13 +248,11 @@ struct F2Plan {                    // one step pair: the monitors that record at
 // n (E side), n + 1 (H side) and n + 1 (E side) in three paged arrays; the sweep, the seam kernel and the shell's boxes add them.
 struct SrcPaged {
   int state = 0;                   // 0 = not tried, 1 = ready, -1 = this problem cannot (two lists meet on a node, ...)
-  int n_blocks = 0;
-  int* sseg = nullptr;             // [nz][ny][nbx]
-  float *e1 = nullptr, *h2 = nullptr, *e2 = nullptr;     // [n_blocks][3][256]: layer 0
+  SegMap seg;                      // the row segments that hold a source node (SrcP::sseg)
+  float *e1 = nullptr, *h2 = nullptr, *e2 = nullptr;     // [seg.n_blocks][3][256]: layer 0
   float *e1b = nullptr, *h2b = nullptr, *e2b = nullptr;  // layer 1: lists that meet an earlier list on a node (nullptr: none does)
   bool any_h = false;              // a list has H-side nodes
   long long pairs = 0;
-  std::vector<int> sseg_host;
   SrcT* tab = nullptr;             // the arrays' addresses, in device memory (SrcP::t)
   size_t n_psrc = 0, n_tfsf = 0;   // the list counts spg_setup saw: lists added since then make the tables stale (spg_release)
 };
@@ -592,6 +615,53 @@ inline void plane_range(const uint32_t* cell, long long n, long long sxy, int* k
   *k1 = (int)(hi / (uint64_t)sxy) + 1;
 }
 inline bool planes_meet(int k0, int k1, int kbeg, int kend) { return k0 < kend && kbeg < k1; }
+
+// Every non-empty side of every source list, in the order launch_sources adds them at a step: TFSF boxes first, then point lists, in
+// the order they were added; within each the E side before the H side.  fn(side, is the H side) with a TfsfList& or a PointSide&:
+// both name n, cell, comp, soff and layer alike.  The paged source terms take their layers in this order (spg_setup), and spg_fill
+// and launch_sources walk one side at a time in the same order of lists.
+template <typename Solver, typename Fn>
+void for_each_source_side(Solver* h, Fn fn) {
+  for (auto& t : h->tfsf) {
+    if (t.e.n) fn(t.e, false);
+    if (t.h.n) fn(t.h, true);
+  }
+  for (auto& s : h->psrc) {
+    if (s.e.n) fn(s.e, false);
+    if (s.h.n) fn(s.h, true);
+  }
+}
+// a point list's E side injects at step n: something is still to be added to E behind a sweep that did not add it itself
+bool e_sources_due(const FdtdSolver* h, long long n) {
+  for (const PointSrc& s : h->psrc) if (s.e_due(n)) return true;
+  return false;
+}
+
+// Lays out the segment map of a paging: `mark(M.dev)` launches disp_mark_kernel on h->stream for every list; the marked segments are
+// numbered 0 .. n_blocks - 1 in map order, the others become -1, on the host and on the device.  0 = built; 1 = the caller gives up
+// (no memory, no marked segment, or more floats in [n_blocks][3][256] than a 32-bit slot addresses); -1 = a HIP error.
+template <typename Mark>
+int seg_map_build(FdtdSolver* h, SegMap& M, Mark mark) {
+  const size_t nseg = (size_t)h->g.nz * h->g.ny * ((h->g.nx + 255) / 256);
+  hipStream_t st = h->stream;
+  if (dev_alloc(h, &M.dev, nseg)) return 1;
+  mark(M.dev);
+  M.host.assign(nseg, 0);
+  HIPCHK(h, hipMemcpyAsync(M.host.data(), M.dev, nseg * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  long long nb = 0;
+  for (size_t q = 0; q < nseg; ++q) M.host[q] = M.host[q] ? (int)nb++ : -1;
+  if (nb == 0 || nb * 3 * 256 >= (1LL << 32)) return 1;
+  HIPCHK(h, hipMemcpyAsync(M.dev, M.host.data(), nseg * sizeof(int), hipMemcpyHostToDevice, st));
+  M.n_blocks = (int)nb;
+  return 0;
+}
+// the empty bounding box {lo, hi} per axis that the slot kernels of a paging (disp_qoff_kernel, src_soff_kernel) widen
+int box_seed_upload(FdtdSolver* h, int** box) {
+  const int big = 1 << 30;
+  const int box0[6] = {big, -1, big, -1, big, -1};
+  return dev_upload(h, box, box0, 6);
+}
 
 long long plane_cells(const FdtdSolver* h) { return (long long)h->cfg.nx * h->cfg.ny; }
 long long n_cells(const FdtdSolver* h) { return plane_cells(h) * h->cfg.nz; }
@@ -1096,10 +1166,8 @@ bool fused2_eligible(const FdtdSolver* h) { return !any_pml(h) && fused2_why_not
 // keeps single steps for the length of its pulse, the rest of the run goes out in pairs).  `*alive`: the lists inject at step n.
 int fused2_sources_why_not(const FdtdSolver* h, long long n, bool* alive = nullptr) {
   bool any_alive = false, any_spent = false;
-  for (const PointSrc& s : h->psrc) {
-    if (!s.n_e && !s.n_h) continue;
-    if (n < s.n_steps) any_alive = true; else any_spent = true;
-  }
+  for (const PointSrc& s : h->psrc)
+    if (s.has_nodes()) (s.alive(n) ? any_alive : any_spent) = true;
   if (alive) *alive = any_alive;
   for (const Tfsf& t : h->tfsf) if (n < t.n_steps) return FDTD_F2_OFF_TFSF;
   if (any_alive && any_spent) return FDTD_F2_OFF_SOURCES;
@@ -1172,20 +1240,20 @@ int fused2_sources(FdtdSolver* h) {
     long long nodes = 0, steps = 0;
     h->src_h_nodes = 0;
     for (const PointSrc& s : h->psrc) {
-      nodes += s.n_e + s.n_h;
-      h->src_h_nodes += s.n_h;
-      if (s.n_e || s.n_h) steps = std::max(steps, s.n_steps);
-      for (long long t = 0; t < s.n_e; ++t) {
-        const int i = (int)(s.host_cell_e[(size_t)t] % g.nx);
+      nodes += s.e.n + s.h.n;
+      h->src_h_nodes += s.h.n;
+      if (s.has_nodes()) steps = std::max(steps, s.n_steps);
+      for (long long t = 0; t < s.e.n; ++t) {
+        const int i = (int)(s.e.host_cell[(size_t)t] % g.nx);
         h->src_on_seam = h->src_on_seam || (i % 256 == 255 && i + 1 < g.nx) || (i % 256 == 0 && i > 0);
         if (h->has_damp) {
-          const long long cell = s.host_cell_e[(size_t)t];
+          const long long cell = s.e.host_cell[(size_t)t];
           const int c3[3] = {i, (int)((cell % g.sxy) / g.nx), (int)(cell / g.sxy)};
           for (int a = 0; a < 3; ++a) h->src_e_in_damp = h->src_e_in_damp || c3[a] < h->damp_lo[a] || c3[a] >= h->damp_hi[a];
         }
       }
-      for (long long t = 0; t < s.n_h; ++t) {
-        const int i = (int)(s.host_cell_h[(size_t)t] % g.nx), c = s.host_comp_h[(size_t)t];
+      for (long long t = 0; t < s.h.n; ++t) {
+        const int i = (int)(s.h.host_cell[(size_t)t] % g.nx), c = s.h.host_comp[(size_t)t];
         h->src_h_on_seam = h->src_h_on_seam || (c != 3 && i % 256 == 255 && i + 1 < g.nx);
       }
     }
@@ -1193,12 +1261,11 @@ int fused2_sources(FdtdSolver* h) {
     if (nodes > 0 && nodes * steps <= (1LL << 24)) {
       if (dev_alloc(h, &h->src_tab, (size_t)(nodes * steps))) return -1;
       long long off = 0;
-      for (const PointSrc& s : h->psrc) {          // node order: E nodes then H nodes of each list (as the node table below)
-        if (s.n_e) launch_inject_table(h->stream, h->src_tab, nodes, off, s.wre_e, s.wim_e, s.wave_e, s.n_steps, (int)s.n_e);
-        off += s.n_e;
-        if (s.n_h) launch_inject_table(h->stream, h->src_tab, nodes, off, s.wre_h, s.wim_h, s.wave_h, s.n_steps, (int)s.n_h);
-        off += s.n_h;
-      }
+      for (const PointSrc& s : h->psrc)            // node order: E nodes then H nodes of each list (as the node table below)
+        for (const PointSide* p : {&s.e, &s.h}) {
+          if (p->n) launch_inject_table(h->stream, h->src_tab, nodes, off, p->wre, p->wim, p->wave, s.n_steps, (int)p->n);
+          off += p->n;
+        }
       h->src_tab_steps = steps; h->src_tab_nodes = nodes;
     }
   }
@@ -1216,14 +1283,11 @@ const F2Table* fused2_table(FdtdSolver* h, const F2Plan& plan, bool with_sources
   int off = 0;
   for (const PointSrc& s : h->psrc) {
     if (!with_sources) break;          // (spent lists: nothing is injected, and a mode plane's 10^5 nodes would be walked per plane for nothing)
-    for (long long t = 0; t < s.n_e; ++t, ++off) {
-      const long long cell = s.host_cell_e[(size_t)t];
-      ent.push_back({(int)(cell / g.sxy), (int)(cell % g.nx), (int)((cell % g.sxy) / g.nx), s.host_comp_e[(size_t)t] % 3, off});
-    }
-    for (long long t = 0; t < s.n_h; ++t, ++off) {      // H-side nodes: codes 3 - 5, terms of step n+1 only (those of step n go out
-      const long long cell = s.host_cell_h[(size_t)t];  // in front of the sweep, launch_sources)
-      ent.push_back({(int)(cell / g.sxy), (int)(cell % g.nx), (int)((cell % g.sxy) / g.nx), 3 + s.host_comp_h[(size_t)t] % 3, off});
-    }
+    for (const PointSide* p : {&s.e, &s.h})             // H-side nodes: codes 3 - 5, terms of step n+1 only (those of step n go out
+      for (long long t = 0; t < p->n; ++t, ++off) {     // in front of the sweep, launch_sources)
+        const long long cell = p->host_cell[(size_t)t];
+        ent.push_back({(int)(cell / g.sxy), (int)(cell % g.nx), (int)((cell % g.sxy) / g.nx), (p == &s.h ? 3 : 0) + p->host_comp[(size_t)t] % 3, off});
+      }
   }
   F2Table tb;
   tb.with_sources = with_sources;
@@ -1311,18 +1375,9 @@ const FdtdSolver::TileClasses* tile_classes(FdtdSolver* h, int W, int zc, const 
         for (int k = std::max(k0 - 1, 0); mats && k <= std::min(k1, g.nz - 1) && !c; ++k)
           for (int j = std::max(j0 - 2, 0); j <= std::min(j0 + R, g.ny - 1); ++j)
             if (h->roww_host[((size_t)k * g.ny + j) * nbx_all + tx] != kBgWord) { c = 1; break; }
-        if (disp && c)
-          for (int k = std::max(k0 - 1, 0); k <= std::min(k1, g.nz - 1) && c < 2; ++k)
-            for (int j = std::max(j0 - 2, 0); j <= std::min(j0 + R, g.ny - 1); ++j)
-              if (h->disp.dseg_host[((size_t)k * g.ny + j) * nbx_all + tx] >= 0) { c = 2; break; }
+        if (disp && c && h->disp.seg.any(g, k0 - 1, k1, j0 - 2, j0 + R, tx, tx)) c = 2;
         n_bg += !c;
-        if (src) {
-          bool found = false;
-          for (int k = std::max(k0 - 1, 0); k <= std::min(k1, g.nz - 1) && !found; ++k)
-            for (int j = std::max(j0 - 2, 0); j <= std::min(j0 + R, g.ny - 1); ++j)
-              if (h->spg.sseg_host[((size_t)k * g.ny + j) * nbx_all + tx] >= 0) { found = true; break; }
-          if (found) c |= 4;
-        }
+        if (src && h->spg.seg.any(g, k0 - 1, k1, j0 - 2, j0 + R, tx, tx)) c |= 4;
         cls[((size_t)tz * nbx + tx) * nby + ty] = c;
       }
   FdtdSolver::TileClasses e{W, zc, box, nbx, nby, nbz, nullptr, n_bg, (long long)cls.size(), disp, src};
@@ -1374,7 +1429,7 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   {
     bool alive = false, alive2 = true;
     for (const PointSrc& s : h->psrc)
-      if (inject && (s.n_e || s.n_h)) { alive = alive || n < s.n_steps; alive2 = alive2 && n + 1 < s.n_steps; }
+      if (inject && s.has_nodes()) { alive = alive || s.alive(n); alive2 = alive2 && s.alive(n + 1); }
     // (all lists alive or all spent: fused2_sources_uniform.  Spent lists add nothing — not + 0 — so their table is only
     //  walked when there are none or when they are alive: pairs with monitor samples AND spent sources are not taken, fdtd_run)
     if (alive && h->src_tab && n + 1 < h->src_tab_steps) {
@@ -1387,8 +1442,8 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
     } else if (alive) {
       int off = 0;
       for (const PointSrc& s : h->psrc) {
-        if (s.n_e) launch_inject_values(st, h->inj_val + off, s.wre_e, s.wim_e, s.wave_e, n, (int)s.n_e);
-        off += (int)(s.n_e + s.n_h);
+        if (s.e.n) launch_inject_values(st, h->inj_val + off, s.e.wre, s.e.wim, s.e.wave, n, (int)s.e.n);
+        off += (int)(s.e.n + s.h.n);
       }
       inj.val = h->inj_val;
     }
@@ -1408,8 +1463,7 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   DampT dmp{};
   if (h->has_damp) {
     for (int a = 0; a < 3; ++a) { dmp.fb[a] = h->damp_fb[a]; dmp.fc[a] = h->damp_fc[a]; }
-    bool post_sources = false;
-    for (const PointSrc& s : h->psrc) post_sources = post_sources || (s.n_e && n + 1 < s.n_steps);
+    const bool post_sources = e_sources_due(h, n + 1);
     // (... unless every E-side source node lies outside the layers: there the factor is exactly 1 — damp (E + s) == damp (E) + s bit
     //  for bit — and the sweep damps E^{n+2} itself.  The bench's dipole sits on the seam column 256 of a 512-cell row, which sent
     //  six damping launches over 40 % of the grid behind every pair: 20 % of the `va` step)
@@ -1424,7 +1478,7 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   time_begin(h, 2, st);
   const MatP mp = mat_params(h);
   DispP dp{nullptr, nullptr, nullptr};
-  if (use_disp) dp = DispP{h->disp.dseg, h->disp.cs, h->disp.e1};
+  if (use_disp) dp = DispP{h->disp.seg.dev, h->disp.cs, h->disp.e1};
   const bool damp = !clip && h->has_damp;
   SrcP sr_used = sr;
   if (h->whatif == 9 && !sr.sseg && !damp && (!use_disp || clip)) {
@@ -1432,12 +1486,12 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
     // every tile dispatches to the bodies the plain launch runs: what the larger kernel costs by itself (results unchanged)
     SrcPaged& S = h->spg;
     const size_t nseg = (size_t)g.nz * g.ny * ((g.nx + 255) / 256);
-    if (!S.sseg && S.state != 1) {
-      S.sseg_host.assign(nseg, -1);
+    if (!S.seg.dev && S.state != 1) {
+      S.seg.host.assign(nseg, -1);
       SrcT tab{};
-      if (dev_upload(h, &S.sseg, (const int*)S.sseg_host.data(), nseg) || dev_upload(h, &S.tab, &tab, 1)) return -1;
+      if (dev_upload(h, &S.seg.dev, (const int*)S.seg.host.data(), nseg) || dev_upload(h, &S.tab, &tab, 1)) return -1;
     }
-    if (S.sseg && S.state != 1) { sr_used.sseg = S.sseg; sr_used.t = S.tab; }
+    if (S.seg.dev && S.state != 1) { sr_used.sseg = S.seg.dev; sr_used.t = S.tab; }
   }
   // the word of the launch (fdtd_fused2.hpp).  What-if variants: measuring aids, the vacuum sweep with part of its work skipped (19: the
   // sweep without its stores into the seam scratch, variant 9 of the kernel; option 9 itself is the map above)
@@ -1458,9 +1512,7 @@ int launch_fused2(FdtdSolver* h, long long n, hipStream_t st, const F2Table* tb,
   h->seam_pending = false;
   bool defer = defer_ok && rep_capable && h->seam_defer != 0 && h->whatif == 0;
   if (defer) {        // nothing may touch the set behind the seam kernel: E-side sources of step n + 1 and the damping of E^{n+2} are in the sweep, or absent
-    bool e_post = false;
-    for (const PointSrc& s : h->psrc) e_post = e_post || (s.n_e && n + 1 < s.n_steps);
-    if ((e_post && !*sources2_done) || (h->has_damp && !dmp.e2)) defer = false;
+    if ((e_sources_due(h, n + 1) && !*sources2_done) || (h->has_damp && !dmp.e2)) defer = false;
   }
   const int blocks = remap ? ((total + 7) / 8) * 8 : total;
   // background-only tiles take the plain sweep inside the materials launch (fdtd_kernels2.hpp, tile classes)
@@ -1573,16 +1625,7 @@ struct ZPlan {
 bool zplan_build(const FdtdSolver* h, const ShellGeom& G, bool source_holes, ZPlan* P) {
   std::vector<std::pair<int, int>> holes;
   for (const AdeGroup& a : h->ade) if (a.n > 0) holes.push_back({a.k0 - 2, a.k1 + 2});
-  if (source_holes) {
-    for (const PointSrc& s : h->psrc) {
-      if (s.n_e) holes.push_back({s.ke0 - 2, s.ke1 + 2});
-      if (s.n_h) holes.push_back({s.kh0 - 2, s.kh1 + 2});
-    }
-    for (const Tfsf& t : h->tfsf) {
-      if (t.e.n_targets) holes.push_back({t.e.k0 - 2, t.e.k1 + 2});
-      if (t.h.n_targets) holes.push_back({t.h.k0 - 2, t.h.k1 + 2});
-    }
-  }
+  if (source_holes) for_each_source_side(h, [&](const auto& L, bool) { holes.push_back({L.k0 - 2, L.k1 + 2}); });
   std::sort(holes.begin(), holes.end());
   P->n = 0;
   int lo = G.o0[2];
@@ -1820,7 +1863,7 @@ void shell2_shape(const FdtdSolver* h, const Shell2Box& bx, int W, int zc_cap, S
 int shell2_box_paged(FdtdSolver* h, const Shell2Box& bx);
 void launch_shell2_boxes(FdtdSolver* h, const Shell2Box* bx, int n, const PmlP* pm, hipStream_t st, const F2Table* tb, bool use_disp = false,
                          const SrcP& sr = SrcP{}) {
-  const DispP dp = use_disp ? DispP{h->disp.dseg, h->disp.cs, h->disp.e1} : DispP{nullptr, nullptr, nullptr};
+  const DispP dp = use_disp ? DispP{h->disp.seg.dev, h->disp.cs, h->disp.e1} : DispP{nullptr, nullptr, nullptr};
   // (the DFT monitors of the pair's plan that reach into the shell: the boxes copy the middle step out over them; the dump buffer was sized by launch_fused2)
   Shell2Dump dmp{};
   if (tb && tb->dstart && h->dump_buf) { dmp.dstart = tb->dstart; dmp.dlist = tb->dlist; dmp.dboxes = tb->dboxes; dmp.dump = h->dump_buf; }
@@ -1871,10 +1914,9 @@ bool shell2_sources_deep(const FdtdSolver* h, const ShellGeom& G) {
     }
     return true;
   };
-  for (const PointSrc& s : h->psrc) {
-    for (long long t = 0; t < s.n_e; ++t) if (!deep(s.host_cell_e[(size_t)t])) return false;
-    for (long long t = 0; t < s.n_h; ++t) if (!deep(s.host_cell_h[(size_t)t])) return false;
-  }
+  for (const PointSrc& s : h->psrc)
+    for (const PointSide* p : {&s.e, &s.h})
+      for (uint32_t cell : p->host_cell) if (!deep(cell)) return false;
   return true;
 }
 int shell2_why_not(const FdtdSolver* h, ShellGeom* G) {
@@ -1988,7 +2030,7 @@ void launch_field_dft(FdtdSolver* h, const Monitor& m, const FieldDftSrc& r, con
 // case in 200, scripts/fuzz_round6.py seed 11 case 47).
 bool h_terms_in_front(const FdtdSolver* h) {
   if (h->src_h_nodes > 0) return true;
-  for (const Tfsf& t : h->tfsf) if (t.h.n_targets) return true;
+  for (const Tfsf& t : h->tfsf) if (t.h.n) return true;
   return false;
 }
 // behind the sweep of the pair (n, n + 1) (the sets are swapped: h->f2 = what it read, h->f = what it wrote): everything the
@@ -2478,6 +2520,7 @@ void launch_damp(FdtdSolver* h, bool e_side, int kbeg, int kend, hipStream_t st)
     }
 }
 
+// the lists of one side that inject at step n, in the order of for_each_source_side
 void launch_sources(FdtdSolver* h, bool e_side, long long n, int kbeg, int kend, hipStream_t st, bool replica = false,
                     const FieldP* fs = nullptr) {
   dbg_sync(h);
@@ -2491,22 +2534,18 @@ void launch_sources(FdtdSolver* h, bool e_side, long long n, int kbeg, int kend,
     const TfsfList& L = e_side ? t.e : t.h;
     // E-side corrections read the incident H (h1), H-side ones the incident E (e1)
     const float* aux = e_side ? (replica ? t.h1c : t.h1) : (replica ? t.e1c : t.e1);
-    if (L.n_targets && planes_meet(L.k0, L.k1, kbeg, kend))
-      hipLaunchKernelGGL(tfsf_corr_kernel, dim3(nblk(L.n_targets)), dim3(256), 0, st, f0, f1, f2,
+    if (L.n && planes_meet(L.k0, L.k1, kbeg, kend))
+      hipLaunchKernelGGL(tfsf_corr_kernel, dim3(nblk(L.n)), dim3(256), 0, st, f0, f1, f2,
                          (const int32_t*)L.comp, (const uint32_t*)L.cell, (const int32_t*)L.start, (const float*)L.w,
-                         (const int32_t*)L.aux, aux, L.n_targets, zlo, zhi);
+                         (const int32_t*)L.aux, aux, L.n, zlo, zhi);
   }
   for (PointSrc& s : h->psrc) {
     if (n >= s.n_steps) continue;
-    if (e_side && s.n_e && planes_meet(s.ke0, s.ke1, kbeg, kend))
-      hipLaunchKernelGGL(point_source_kernel, dim3(nblk(s.n_e)), dim3(256), 0, st, f0, f1, f2,
-                         (const int32_t*)s.comp_e, (const uint32_t*)s.cell_e, (const float*)s.wre_e,
-                         (const float*)s.wim_e, (const float2*)s.wave_e, h->step_dev_mode ? h->step_dev_off : n, s.n_e, zlo, zhi,
-                         (const long long*)(h->step_dev_mode ? h->step_dev : nullptr));
-    if (!e_side && s.n_h && planes_meet(s.kh0, s.kh1, kbeg, kend))
-      hipLaunchKernelGGL(point_source_kernel, dim3(nblk(s.n_h)), dim3(256), 0, st, f0, f1, f2,
-                         (const int32_t*)s.comp_h, (const uint32_t*)s.cell_h, (const float*)s.wre_h,
-                         (const float*)s.wim_h, (const float2*)s.wave_h, h->step_dev_mode ? h->step_dev_off : n, s.n_h, zlo, zhi,
+    const PointSide& P = s.side(e_side);
+    if (P.n && planes_meet(P.k0, P.k1, kbeg, kend))
+      hipLaunchKernelGGL(point_source_kernel, dim3(nblk(P.n)), dim3(256), 0, st, f0, f1, f2,
+                         (const int32_t*)P.comp, (const uint32_t*)P.cell, (const float*)P.wre,
+                         (const float*)P.wim, (const float2*)P.wave, h->step_dev_mode ? h->step_dev_off : n, P.n, zlo, zhi,
                          (const long long*)(h->step_dev_mode ? h->step_dev : nullptr));
   }
 }
@@ -2736,33 +2775,24 @@ int disp_setup(FdtdSolver* h) {
   if (h->ade.empty() || h->disp_on == 0 || !h->mat4 || h->mat4b || h->comm || !h->aniso.empty() || !h->modulation.empty() || !h->nonlinear.empty() || g.nx % 4 != 0) return 0;
   for (const AdeGroup& a : h->ade) if (!a.strict) return 0;
   const int nbx = (g.nx + 255) / 256;
-  const size_t nseg = (size_t)g.nz * g.ny * nbx;
   hipStream_t st = h->stream;
   auto give_up = [&]() { (void)hipGetLastError(); h->err.clear(); for (AdeGroup& a : h->ade) a.qoff = nullptr; return 0; };
-  if (dev_alloc(h, &D.dseg, nseg)) return give_up();
-  for (const AdeGroup& a : h->ade)
-    hipLaunchKernelGGL(disp_mark_kernel, dim3(nblk(a.n)), dim3(256), 0, st, (const uint32_t*)a.cell, a.n, g.nx, nbx, D.dseg);
-  D.dseg_host.assign(nseg, 0);
-  HIPCHK(h, hipMemcpyAsync(D.dseg_host.data(), D.dseg, nseg * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  long long nb = 0;
-  for (size_t q = 0; q < nseg; ++q) D.dseg_host[q] = D.dseg_host[q] ? (int)nb++ : -1;
-  const long long floats = nb * 3 * 256;
-  if (nb == 0 || floats >= (1LL << 32)) return give_up();             // (qoff is 32 bits wide)
-  HIPCHK(h, hipMemcpyAsync(D.dseg, D.dseg_host.data(), nseg * sizeof(int), hipMemcpyHostToDevice, st));
-  const int big = 1 << 30;
-  const int box0[6] = {big, -1, big, -1, big, -1};
+  const int rc = seg_map_build(h, D.seg, [&](int* seg) {
+    for (const AdeGroup& a : h->ade)
+      hipLaunchKernelGGL(disp_mark_kernel, dim3(nblk(a.n)), dim3(256), 0, st, (const uint32_t*)a.cell, a.n, g.nx, nbx, seg);
+  });
+  if (rc) return rc < 0 ? -1 : give_up();             // (gives up past 2^32 floats: qoff is 32 bits wide)
+  const size_t floats = (size_t)D.seg.n_blocks * 3 * 256;
   int* box = nullptr;
-  if (dev_alloc(h, &D.cs, (size_t)floats) || dev_alloc(h, &D.e1, (size_t)floats) || dev_upload(h, &box, box0, 6)) return give_up();
+  if (dev_alloc(h, &D.cs, floats) || dev_alloc(h, &D.e1, floats) || box_seed_upload(h, &box)) return give_up();
   for (AdeGroup& a : h->ade) {
     if (dev_alloc(h, &a.qoff, (size_t)a.n, false)) return give_up();
     hipLaunchKernelGGL(disp_qoff_kernel, dim3(nblk(a.n)), dim3(256), 0, st, (const uint32_t*)a.cell, a.n, g.nx, g.ny, nbx,
-                       (const int*)D.dseg, a.comp, (const float2*)a.q, a.p, a.qoff, D.cs, box);
+                       (const int*)D.seg.dev, a.comp, (const float2*)a.q, a.p, a.qoff, D.cs, box);
   }
   int boxh[6];
   HIPCHK(h, hipMemcpyAsync(boxh, box, sizeof(boxh), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
-  D.n_blocks = (int)nb;
   for (int a = 0; a < 3; ++a) { D.lo[a] = boxh[2 * a]; D.hi[a] = boxh[2 * a + 1] + 1; }
   h->tile_cls.clear();
   h->box_paged.clear();
@@ -2792,56 +2822,36 @@ int spg_setup(FdtdSolver* h) {
   const GridP& g = h->g;
   if (h->spg_on == 0 || h->comm || g.nx % 4 != 0) return 0;
   long long total = 0;
-  for (const PointSrc& s : h->psrc) total += s.n_e + s.n_h;
-  for (const Tfsf& t : h->tfsf) total += t.e.n_targets + t.h.n_targets;
+  for_each_source_side(h, [&](const auto& L, bool) { total += L.n; });
   if (total == 0) return 0;
   const int nbx = (g.nx + 255) / 256;
-  const size_t nseg = (size_t)g.nz * g.ny * nbx;
   hipStream_t st = h->stream;
   auto give_up = [&]() { (void)hipGetLastError(); h->err.clear(); return 0; };
-  if (dev_alloc(h, &S.sseg, nseg)) return give_up();
-  // every (cells, comps, n, soff, layer, H side?) of every list, in the order launch_sources adds them: TFSF boxes, then point lists
-  auto each = [&](auto fn) {
-    for (Tfsf& t : h->tfsf) {
-      if (t.e.n_targets) fn((const uint32_t*)t.e.cell, (const int32_t*)t.e.comp, t.e.n_targets, &t.e.soff, &t.e.layer, false);
-      if (t.h.n_targets) fn((const uint32_t*)t.h.cell, (const int32_t*)t.h.comp, t.h.n_targets, &t.h.soff, &t.h.layer, true);
-    }
-    for (PointSrc& s : h->psrc) {
-      if (s.n_e) fn((const uint32_t*)s.cell_e, (const int32_t*)s.comp_e, s.n_e, &s.soff_e, &s.layer_e, false);
-      if (s.n_h) fn((const uint32_t*)s.cell_h, (const int32_t*)s.comp_h, s.n_h, &s.soff_h, &s.layer_h, true);
-    }
-  };
-  each([&](const uint32_t* cell, const int32_t*, long long n, uint32_t**, int*, bool) {
-    hipLaunchKernelGGL(disp_mark_kernel, dim3(nblk(n)), dim3(256), 0, st, cell, n, g.nx, nbx, S.sseg);
+  const int rc = seg_map_build(h, S.seg, [&](int* seg) {
+    for_each_source_side(h, [&](const auto& L, bool) {
+      hipLaunchKernelGGL(disp_mark_kernel, dim3(nblk(L.n)), dim3(256), 0, st, (const uint32_t*)L.cell, L.n, g.nx, nbx, seg);
+    });
   });
-  std::vector<int>& seg = S.sseg_host;
-  seg.assign(nseg, 0);
-  HIPCHK(h, hipMemcpyAsync(seg.data(), S.sseg, nseg * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  long long nb = 0;
-  for (size_t q = 0; q < nseg; ++q) seg[q] = seg[q] ? (int)nb++ : -1;
-  const long long floats = nb * 3 * 256;
-  if (nb == 0 || floats >= (1LL << 32)) return give_up();
-  HIPCHK(h, hipMemcpyAsync(S.sseg, seg.data(), nseg * sizeof(int), hipMemcpyHostToDevice, st));
+  if (rc) return rc < 0 ? -1 : give_up();
+  const size_t floats = (size_t)S.seg.n_blocks * 3 * 256;
   int *occ[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *box = nullptr, *hit = nullptr;       // [side][layer]
-  const int big = 1 << 30;
-  const int box0[6] = {big, -1, big, -1, big, -1};
-  if (dev_alloc(h, &S.e1, (size_t)floats) || dev_alloc(h, &S.h2, (size_t)floats) || dev_alloc(h, &S.e2, (size_t)floats) ||
-      dev_upload(h, &box, box0, 6) || dev_alloc(h, &hit, 2)) return give_up();
-  for (int sd = 0; sd < 2; ++sd) for (int ly = 0; ly < 2; ++ly) if (dev_alloc(h, &occ[sd][ly], (size_t)floats)) return give_up();
+  if (dev_alloc(h, &S.e1, floats) || dev_alloc(h, &S.h2, floats) || dev_alloc(h, &S.e2, floats) || box_seed_upload(h, &box) ||
+      dev_alloc(h, &hit, 2)) return give_up();
+  for (int sd = 0; sd < 2; ++sd) for (int ly = 0; ly < 2; ++ly) if (dev_alloc(h, &occ[sd][ly], floats)) return give_up();
   bool failed = false, hip_failed = false;
   int layers = 1;
   S.any_h = false;
-  each([&](const uint32_t* cell, const int32_t* comp, long long n, uint32_t** soff, int* layer, bool h_side) {
+  for_each_source_side(h, [&](auto& L, bool h_side) {      // (in this order a list meets the lists added to the fields before it)
     if (failed || hip_failed) return;
-    if (dev_alloc(h, soff, (size_t)n, false)) { failed = true; return; }
+    if (dev_alloc(h, &L.soff, (size_t)L.n, false)) { failed = true; return; }
     S.any_h = S.any_h || h_side;
-    hipLaunchKernelGGL(src_soff_kernel, dim3(nblk(n)), dim3(256), 0, st, cell, comp, n, g.nx, g.ny, nbx, (const int*)S.sseg, *soff, box);
+    hipLaunchKernelGGL(src_soff_kernel, dim3(nblk(L.n)), dim3(256), 0, st, (const uint32_t*)L.cell, (const int32_t*)L.comp, L.n, g.nx, g.ny,
+                       nbx, (const int*)S.seg.dev, L.soff, box);
     // the layer: above every earlier list of this side it meets
     int hh[2] = {0, 0};
     auto probe = [&](int ly, int mark) {
       if (hipMemsetAsync(hit, 0, 2 * sizeof(int), st) != hipSuccess) { hip_failed = true; return; }
-      hipLaunchKernelGGL(src_layer_kernel, dim3(nblk(n)), dim3(256), 0, st, (const uint32_t*)*soff, n, occ[h_side ? 1 : 0][ly], hit, mark);
+      hipLaunchKernelGGL(src_layer_kernel, dim3(nblk(L.n)), dim3(256), 0, st, (const uint32_t*)L.soff, L.n, occ[h_side ? 1 : 0][ly], hit, mark);
       if (hipMemcpyAsync(hh, hit, sizeof(hh), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) hip_failed = true;
     };
     probe(1, 0);
@@ -2849,20 +2859,19 @@ int spg_setup(FdtdSolver* h) {
     if (hh[0] > 0) { failed = true; return; }            // it would need a third layer
     probe(0, 0);
     if (hip_failed) return;
-    *layer = hh[0] > 0 ? 1 : 0;
-    layers = std::max(layers, *layer + 1);
-    probe(*layer, 1);
+    L.layer = hh[0] > 0 ? 1 : 0;
+    layers = std::max(layers, L.layer + 1);
+    probe(L.layer, 1);
     if (!hip_failed && hh[1] > 0) failed = true;         // a node listed twice
   });
   for (int sd = 0; sd < 2; ++sd) for (int ly = 0; ly < 2; ++ly) release_buf(h, occ[sd][ly]);
   if (hip_failed) return fail(h, "spg_setup: a HIP call failed");
   if (failed) return give_up();
-  if (layers > 1 && (dev_alloc(h, &S.e1b, (size_t)floats) || dev_alloc(h, &S.h2b, (size_t)floats) || dev_alloc(h, &S.e2b, (size_t)floats)))
+  if (layers > 1 && (dev_alloc(h, &S.e1b, floats) || dev_alloc(h, &S.h2b, floats) || dev_alloc(h, &S.e2b, floats)))
     return give_up();
   HIPCHK(h, hipStreamSynchronize(st));
   const SrcT tab{S.e1, S.h2, S.e2, S.any_h ? 1 : 0, 1, S.e1b, S.h2b, S.e2b};
   if (dev_upload(h, &S.tab, &tab, 1)) return give_up();
-  S.n_blocks = (int)nb;
   S.state = 1;
   h->box_paged.clear();
   return 0;
@@ -2874,11 +2883,10 @@ void spg_release(FdtdSolver* h) {
   SrcPaged& S = h->spg;
   (void)hipStreamSynchronize(h->stream);
   auto drop = [&](auto*& p) { if (p) release_buf(h, p); p = nullptr; };
-  drop(S.sseg); drop(S.e1); drop(S.h2); drop(S.e2); drop(S.e1b); drop(S.h2b); drop(S.e2b); drop(S.tab);
-  for (Tfsf& t : h->tfsf) { drop(t.e.soff); drop(t.h.soff); t.e.layer = t.h.layer = 0; }
-  for (PointSrc& s : h->psrc) { drop(s.soff_e); drop(s.soff_h); s.layer_e = s.layer_h = 0; }
-  S.sseg_host.clear();
-  S.n_blocks = 0; S.any_h = false;
+  drop(S.seg.dev); drop(S.e1); drop(S.h2); drop(S.e2); drop(S.e1b); drop(S.h2b); drop(S.e2b); drop(S.tab);
+  for_each_source_side(h, [&](auto& L, bool) { drop(L.soff); L.layer = 0; });
+  S.seg.host.clear();
+  S.seg.n_blocks = 0; S.any_h = false;
   S.state = 0;
   h->tile_cls.clear();
   h->box_paged.clear();
@@ -2894,39 +2902,29 @@ int shell2_box_paged(FdtdSolver* h, const Shell2Box& bx) {
   const bool per_x = h->cfg.bc[0] == FDTD_BC_PERIODIC;
   const int t0 = per_x ? 0 : std::max(0, bx.i0 - 8) / 256, t1 = per_x ? nbx - 1 : std::min(g.nx - 1, bx.i1 + 7) / 256;
   int flags = 0;
-  const std::vector<int>* maps[2] = {h->spg.state == 1 ? &h->spg.sseg_host : nullptr, h->disp.state == 1 ? &h->disp.dseg_host : nullptr};
-  for (int m = 0; m < 2; ++m) {
-    if (!maps[m] || maps[m]->empty()) continue;
-    bool found = false;
-    for (int k = std::max(0, bx.k0 - 1); k <= std::min(g.nz - 1, bx.k1) && !found; ++k)
-      for (int j = std::max(0, bx.j0 - 2); j <= std::min(g.ny - 1, bx.j1) && !found; ++j)
-        for (int t = t0; t <= t1; ++t)
-          if ((*maps[m])[((size_t)k * g.ny + j) * nbx + t] >= 0) { found = true; break; }
-    if (found) flags |= 1 << m;
-  }
+  if (h->spg.state == 1 && h->spg.seg.any(g, bx.k0 - 1, bx.k1, bx.j0 - 2, bx.j1, t0, t1)) flags |= 1;
+  if (h->disp.state == 1 && h->disp.seg.any(g, bx.k0 - 1, bx.k1, bx.j0 - 2, bx.j1, t0, t1)) flags |= 2;
   h->box_paged[key] = flags;
   return flags;
 }
-// the three arrays (per layer) of the pair (n, n + 1), and the incident grids of the TFSF boxes advanced through both steps — in the
-// order of two single steps (the H-side terms of step n were added to H^{n-1/2} in place just before, launch_sources):
+// the three arrays (per layer) of the pair (n, n + 1), and the incident grids of the TFSF boxes advanced through both steps: a side's lists
+// as for_each_source_side orders them, the sides as two single steps do (the H-side terms of step n went into H^{n-1/2} just before, launch_sources):
 //   incident H(n) | E-side terms of n | incident E(n) | H-side terms of n+1 | incident H(n+1) | E-side terms of n+1 | incident E(n+1)
 void spg_fill(FdtdSolver* h, long long n, hipStream_t st) {
   SrcPaged& S = h->spg;
   auto fill = [&](float* val0, float* val1, bool e_side, long long step) {
     for (Tfsf& t : h->tfsf) {
       const TfsfList& L = e_side ? t.e : t.h;
-      if (!L.n_targets) continue;
-      hipLaunchKernelGGL(src_fill_tfsf_kernel, dim3(nblk(L.n_targets)), dim3(256), 0, st, L.layer ? val1 : val0, (const uint32_t*)L.soff,
-                         (const int32_t*)L.start, (const float*)L.w, (const int32_t*)L.aux, (const float*)(e_side ? t.h1 : t.e1), L.n_targets,
+      if (!L.n) continue;
+      hipLaunchKernelGGL(src_fill_tfsf_kernel, dim3(nblk(L.n)), dim3(256), 0, st, L.layer ? val1 : val0, (const uint32_t*)L.soff,
+                         (const int32_t*)L.start, (const float*)L.w, (const int32_t*)L.aux, (const float*)(e_side ? t.h1 : t.e1), L.n,
                          step >= t.n_steps ? 1 : 0);
     }
     for (PointSrc& s : h->psrc) {
-      const long long nn = e_side ? s.n_e : s.n_h;
-      if (!nn) continue;
-      hipLaunchKernelGGL(src_fill_points_kernel, dim3(nblk(nn)), dim3(256), 0, st, (e_side ? s.layer_e : s.layer_h) ? val1 : val0,
-                         (const uint32_t*)(e_side ? s.soff_e : s.soff_h), (const float*)(e_side ? s.wre_e : s.wre_h),
-                         (const float*)(e_side ? s.wim_e : s.wim_h), (const float2*)(e_side ? s.wave_e : s.wave_h), step, nn,
-                         step >= s.n_steps ? 1 : 0);
+      const PointSide& P = s.side(e_side);
+      if (!P.n) continue;
+      hipLaunchKernelGGL(src_fill_points_kernel, dim3(nblk(P.n)), dim3(256), 0, st, P.layer ? val1 : val0, (const uint32_t*)P.soff,
+                         (const float*)P.wre, (const float*)P.wim, (const float2*)P.wave, step, P.n, step >= s.n_steps ? 1 : 0);
     }
   };
   advance_tfsf_aux(h, false, n, st, false);
@@ -2940,7 +2938,7 @@ void spg_fill(FdtdSolver* h, long long n, hipStream_t st) {
 SrcP spg_params(const FdtdSolver* h) {
   const SrcPaged& S = h->spg;
   SrcP p;
-  p.sseg = S.sseg; p.t = S.tab;
+  p.sseg = S.seg.dev; p.t = S.tab;
   return p;
 }
 
@@ -3824,32 +3822,24 @@ int fdtd_add_point_source(FdtdSolver* h, int64_t n, const int32_t* comp, const u
     acc.first += (double)w_re[i];
     acc.second += (double)w_im[i];
   }
-  std::vector<int32_t> ce, chh;
-  std::vector<uint32_t> le, lh;
-  std::vector<float> re_e, im_e, re_h, im_h;
-  for (const auto& kv : merged) {
-    const int32_t c = kv.first.first;
-    if (c < 3) { ce.push_back(c); le.push_back(kv.first.second); re_e.push_back((float)kv.second.first); im_e.push_back((float)kv.second.second); }
-    else { chh.push_back(c); lh.push_back(kv.first.second); re_h.push_back((float)kv.second.first); im_h.push_back((float)kv.second.second); }
-  }
   PointSrc s{};
-  s.n_e = (long long)ce.size(); s.n_h = (long long)chh.size(); s.n_steps = n_steps;
-  plane_range(le.data(), s.n_e, h->g.sxy, &s.ke0, &s.ke1);
-  plane_range(lh.data(), s.n_h, h->g.sxy, &s.kh0, &s.kh1);
-  if (s.n_e) {
-    if (dev_upload(h, &s.comp_e, (const int32_t*)ce.data(), ce.size()) || dev_upload(h, &s.cell_e, (const uint32_t*)le.data(), le.size()) ||
-        dev_upload(h, &s.wre_e, (const float*)re_e.data(), re_e.size()) || dev_upload(h, &s.wim_e, (const float*)im_e.data(), im_e.size()) ||
-        dev_upload(h, &s.wave_e, reinterpret_cast<const float2*>(wave_e), (size_t)n_steps))
-      return -1;
+  s.n_steps = n_steps;
+  std::vector<float> re[2], im[2];      // [H side?]
+  for (const auto& kv : merged) {       // each side keeps the map's order: by component, then by cell
+    const int hs = kv.first.first < 3 ? 0 : 1;
+    PointSide& P = hs ? s.h : s.e;
+    P.host_comp.push_back(kv.first.first); P.host_cell.push_back(kv.first.second);
+    re[hs].push_back((float)kv.second.first); im[hs].push_back((float)kv.second.second);
   }
-  if (s.n_h) {
-    if (dev_upload(h, &s.comp_h, (const int32_t*)chh.data(), chh.size()) || dev_upload(h, &s.cell_h, (const uint32_t*)lh.data(), lh.size()) ||
-        dev_upload(h, &s.wre_h, (const float*)re_h.data(), re_h.size()) || dev_upload(h, &s.wim_h, (const float*)im_h.data(), im_h.size()) ||
-        dev_upload(h, &s.wave_h, reinterpret_cast<const float2*>(wave_h), (size_t)n_steps))
-      return -1;
-  }
-  s.host_comp_e = ce; s.host_comp_h = chh;
-  s.host_cell_e = le; s.host_cell_h = lh;
+  auto upload = [&](PointSide& P, const std::vector<float>& wre, const std::vector<float>& wim, const float* wave) {
+    P.n = (long long)P.host_comp.size();
+    plane_range(P.host_cell.data(), P.n, h->g.sxy, &P.k0, &P.k1);
+    return P.n && (dev_upload(h, &P.comp, (const int32_t*)P.host_comp.data(), P.host_comp.size()) ||
+                   dev_upload(h, &P.cell, (const uint32_t*)P.host_cell.data(), P.host_cell.size()) ||
+                   dev_upload(h, &P.wre, (const float*)wre.data(), wre.size()) || dev_upload(h, &P.wim, (const float*)wim.data(), wim.size()) ||
+                   dev_upload(h, &P.wave, reinterpret_cast<const float2*>(wave), (size_t)n_steps));
+  };
+  if (upload(s.e, re[0], im[0], wave_e) || upload(s.h, re[1], im[1], wave_h)) return -1;
   h->psrc.push_back(s);
   return 0;
 }
@@ -3880,8 +3870,8 @@ int build_tfsf_list(FdtdSolver* h, TfsfList& L, int64_t n, const int32_t* comp, 
     ax[(size_t)e] = aux[i];
   }
   st.push_back((int32_t)n);
-  L.n_targets = (long long)tc.size();
-  plane_range(tl.data(), L.n_targets, h->g.sxy, &L.k0, &L.k1);
+  L.n = (long long)tc.size();
+  plane_range(tl.data(), L.n, h->g.sxy, &L.k0, &L.k1);
   if (dev_upload(h, &L.comp, (const int32_t*)tc.data(), tc.size()) || dev_upload(h, &L.cell, (const uint32_t*)tl.data(), tl.size()) ||
       dev_upload(h, &L.start, (const int32_t*)st.data(), st.size()) || dev_upload(h, &L.w, (const float*)ww.data(), ww.size()) ||
       dev_upload(h, &L.aux, (const int32_t*)ax.data(), ax.size()))
@@ -4359,7 +4349,7 @@ int fdtd_reset(FdtdSolver* h) {
     HIPCHK(h, hipMemset(a.e_old, 0, (size_t)a.n * 4));
     HIPCHK(h, hipMemset(a.q, 0, (size_t)a.n * a.p.n_poles * 8));
   }
-  if (h->disp.state == 1) HIPCHK(h, hipMemset(h->disp.cs, 0, (size_t)h->disp.n_blocks * 3 * 256 * sizeof(float)));
+  if (h->disp.state == 1) HIPCHK(h, hipMemset(h->disp.cs, 0, (size_t)h->disp.seg.n_blocks * 3 * 256 * sizeof(float)));
   for (Tfsf& t : h->tfsf) {
     HIPCHK(h, hipMemset(t.e1, 0, ((size_t)t.n_aux + 1) * 4));
     HIPCHK(h, hipMemset(t.h1, 0, (size_t)t.n_aux * 4));

@@ -499,7 +499,7 @@ struct Run {
       bool needs = !h->tfsf.empty() || h->src_nodes > kMaxInj || h->src_h_on_seam || (h->src_h_nodes > 0 && !h->src_tab);
       if (!needs) {                                // lists of different lengths: mixed alive / spent pairs
         long long len = -1;
-        for (const PointSrc& s : h->psrc) if (s.n_e || s.n_h) { if (len >= 0 && s.n_steps != len) needs = true; len = s.n_steps; }
+        for (const PointSrc& s : h->psrc) if (s.has_nodes()) { if (len >= 0 && s.n_steps != len) needs = true; len = s.n_steps; }
       }
       if (h->spg.state != 0 && (h->spg.n_psrc != h->psrc.size() || h->spg.n_tfsf != h->tfsf.size())) spg_release(h);      // (lists added since)
       if (needs && spg_setup(h)) return -1;
@@ -677,8 +677,7 @@ struct Run {
     }
     // dispersive cells (all deep inside the bulk): both steps of their pole states and the correction of E^{n+2} behind the bulk,
     // beside the shell's boxes, once nothing else is due on E^{n+2} there — else at the end, behind the sources of step n + 1
-    bool src_due = false;
-    for (const PointSrc& sr : h->psrc) src_due = src_due || (sr.n_e && n + 1 < sr.n_steps);
+    const bool src_due = e_sources_due(h, n + 1);
     // (clear of the bulk's faces by what the boxes read beyond their own cells — a plane, two rows, a halo lane: ade2_kernel REWRITES the
     //  paged memory terms, and a box that has not yet read those of its halo plane would subtract the next pair's.  Found on the device by
     //  scripts/fuzz_round6.py in the round's last hour (seed 31, case 124: a Lorentz body whose lowest plane is the bulk's first one — one run
