@@ -60,6 +60,11 @@ struct PmlAxisDev {
   float* psi_et[2] = {nullptr, nullptr};   // still read the old values), lazily allocated
   size_t psi_count = 0;                    // entries per psi array
   size_t psi_plane = 0;                    // entries of one z-plane of it (x, y axes: the H-side arrays carry one more, the ghost slot)
+  // the six sets by number, in the order they are allocated (the first two by fdtd_set_pml, the others lazily: ensure_psi_sets),
+  // and the entries each array of a set holds
+  enum Set { kE, kH, kH2, kE2, kHt, kEt, kSets };
+  float** set(int s) { float** const v[kSets] = {psi_e, psi_h, psi_h2, psi_e2, psi_ht, psi_et}; return v[s]; }
+  size_t set_count(int s) const { return psi_count + (s == kH || s == kH2 || s == kHt ? psi_plane : 0); }
 };
 
 struct AdeGroup {
@@ -770,71 +775,95 @@ bool any_pml(const FdtdSolver* h) {
   return false;
 }
 
-// Device parameter blocks of the in-sweep CPML: block [hp][ep] reads psi_h (hp = 0) or psi_h2 (hp = 1) and
-// writes the other set; the sweep alternates between them.  The E side is updated in place, in the set that is current
-// ([ep]: a shell2 pair leaves it in the other one).  Built on first use.
-void fill_pml_axis(const FdtdSolver* h, int a, bool in, bool flip_h, bool flip_e, bool e_in_place, PmlAxisP& A) {
+// ---- device parameter blocks of the in-sweep CPML (PmlP), built on first use ----------------------------------------------------
+// the lazily allocated psi sets named in `which` (bits 1 << PmlAxisDev::kH2 ...) of every axis with members; *e2_fresh: the second
+// E-side set was allocated by this call
+int ensure_psi_sets(FdtdSolver* h, int which, bool* e2_fresh = nullptr) {
+  for (int a = 0; a < 3; ++a) {
+    PmlAxisDev& P = h->pml[a];
+    if (P.ns == 0) continue;
+    for (int q = 0; q < 2; ++q)
+      for (int s = PmlAxisDev::kH2; s < PmlAxisDev::kSets; ++s) {
+        if (!((which >> s) & 1) || P.set(s)[q]) continue;
+        if (dev_alloc(h, &P.set(s)[q], P.set_count(s))) return -1;
+        if (s == PmlAxisDev::kE2 && e2_fresh) *e2_fresh = true;
+      }
+  }
+  return 0;
+}
+// every parameter block is rebuilt on its next use
+void invalidate_pml_blocks(FdtdSolver* h) {
+  for (bool& ok : h->pml_blk_ok) ok = false;
+  h->pml_blk2_ok = false; h->pml_blk_hole_ok = false;
+}
+
+// which sets of an axis a block reads and writes.  "Current" is what the host calls psi_h / psi_e at the time of the launch,
+// "other" what it calls psi_h2 / psi_e2.
+enum PsiRoute {
+  kPsiEInPlace,     // sweeps of single steps: the H side reads the current set and writes the other one, the E side stays in place
+  kPsiPingPong,     // shell2_step_kernel: both sides read the current sets and write the other ones
+  kPsiToTemp,       // z hole of a shell2 pair, step one: both sides current -> temporary sets
+  kPsiFromTemp,     // z hole, step two: both sides temporary -> other sets
+};
+// flip_h / flip_e: the block is for the parity opposite to the one the host's names have now (upload_pml_block)
+void fill_pml_axis(const FdtdSolver* h, int a, bool in, bool flip_h, bool flip_e, PsiRoute route, PmlAxisP& A) {
   const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
   const PmlAxisDev& P = h->pml[a];
   A.ce4 = P.ce4; A.ch4 = P.ch4;
   A.kv_e = P.kv_e; A.b_e = P.b_e; A.c_e = P.c_e;
   A.kv_h = P.kv_h; A.b_h = P.b_h; A.c_h = P.c_h;
-  float* const e_cur[2] = {flip_e && P.psi_e2[0] ? P.psi_e2[0] : P.psi_e[0], flip_e && P.psi_e2[1] ? P.psi_e2[1] : P.psi_e[1]};
-  float* const e_oth[2] = {flip_e || !P.psi_e2[0] ? P.psi_e[0] : P.psi_e2[0], flip_e || !P.psi_e2[1] ? P.psi_e[1] : P.psi_e2[1]};
-  A.pe0 = e_cur[0]; A.pe1 = e_cur[1];
-  A.pe0n = e_in_place ? e_cur[0] : e_oth[0]; A.pe1n = e_in_place ? e_cur[1] : e_oth[1];
-  A.ph0 = flip_h ? P.psi_h2[0] : P.psi_h[0]; A.ph1 = flip_h ? P.psi_h2[1] : P.psi_h[1];
-  A.ph0n = flip_h ? P.psi_h[0] : P.psi_h2[0]; A.ph1n = flip_h ? P.psi_h[1] : P.psi_h2[1];
+  float *rd_e[2], *wr_e[2], *rd_h[2], *wr_h[2];
+  for (int q = 0; q < 2; ++q) {
+    // (without a second E-side set both parities name the one set there is)
+    float* const e_cur = flip_e && P.psi_e2[q] ? P.psi_e2[q] : P.psi_e[q];
+    float* const e_oth = flip_e || !P.psi_e2[q] ? P.psi_e[q] : P.psi_e2[q];
+    float* const h_cur = flip_h ? P.psi_h2[q] : P.psi_h[q];
+    float* const h_oth = flip_h ? P.psi_h[q] : P.psi_h2[q];
+    rd_e[q] = route == kPsiFromTemp ? P.psi_et[q] : e_cur;
+    rd_h[q] = route == kPsiFromTemp ? P.psi_ht[q] : h_cur;
+    wr_e[q] = route == kPsiEInPlace ? e_cur : (route == kPsiToTemp ? P.psi_et[q] : e_oth);
+    wr_h[q] = route == kPsiToTemp ? P.psi_ht[q] : h_oth;
+  }
+  A.pe0 = rd_e[0]; A.pe1 = rd_e[1]; A.pe0n = wr_e[0]; A.pe1n = wr_e[1];
+  A.ph0 = rd_h[0]; A.ph1 = rd_h[1]; A.ph0n = wr_h[0]; A.ph1n = wr_h[1];
   // an axis without CPML, or one whose recursions stay in the slab kernels, has no members
   A.lo = in ? P.lo : 0; A.hi0 = in ? P.hi0 : N[a]; A.ns = P.ns; A.n = N[a];
 }
+// One block into one slot: the axes of `mask` with their recursions inside the kernel, for H-side parity `par` and E-side parity `ep`.
+// The two sets of an axis keep their identity: `psi_h` / `psi_h2` (`psi_e` / `psi_e2`) swap NAMES on the host after every sweep that
+// carried the axis (swap_psi_h: the axes of its mask only — launch_pml reads the un-swapped names of the others) or shell2 pair
+// (swap_psi_e), and pml_parity / pml_e_parity count the swaps.  A block is indexed by the parities at the time of its launch, but
+// filled from the names as they are NOW: block [par][ep] must read what the host will call psi_h (psi_e) when pml_parity == par
+// (pml_e_parity == ep) — today's psi_h2 (psi_e2) when that parity differs from today's.
+int upload_pml_block(FdtdSolver* h, PmlP** slot, int mask, int par, int ep, PsiRoute route) {
+  PmlP pm{};
+  for (int a = 0; a < 3; ++a)
+    fill_pml_axis(h, a, h->pml[a].ns > 0 && ((mask >> a) & 1), par != h->pml_parity, ep != h->pml_e_parity, route, pm.ax[a]);
+  if (!*slot && dev_alloc(h, slot, 1, false)) return -1;
+  if (hipMemcpy(*slot, &pm, sizeof(PmlP), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(h, "upload of the CPML parameter block failed");
+  return 0;
+}
+// the blocks of the sweeps of single steps: [axes inside the sweep][par][ep]
 int ensure_pml_blocks(FdtdSolver* h, int mask) {
   if (h->pml_blk_ok[mask]) return 0;
-  for (int a = 0; a < 3; ++a) {
-    PmlAxisDev& P = h->pml[a];
-    if (P.ns == 0) continue;
-    for (int q = 0; q < 2; ++q)
-      if (!P.psi_h2[q] && dev_alloc(h, &P.psi_h2[q], P.psi_count + P.psi_plane)) return -1;
-  }
-  // The two sets of an axis keep their identity: `psi_h` / `psi_h2` (`psi_e` / `psi_e2`) swap names on the host after every
-  // sweep (shell2 pair), so block [hp][ep] must read what the host calls psi_h (psi_e) when pml_parity == hp (pml_e_parity == ep).
-  for (int par = 0; par < 2; ++par) {
-    for (int ep = 0; ep < 2; ++ep) {
-      PmlP pm{};
-      for (int a = 0; a < 3; ++a)
-        fill_pml_axis(h, a, h->pml[a].ns > 0 && ((mask >> a) & 1), par != h->pml_parity, ep != h->pml_e_parity, true, pm.ax[a]);
-      if (!h->pml_blk[mask][par][ep] && dev_alloc(h, &h->pml_blk[mask][par][ep], 1, false)) return -1;
-      if (hipMemcpy(h->pml_blk[mask][par][ep], &pm, sizeof(PmlP), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(h, "upload of the CPML parameter block failed");
-    }
-  }
+  if (ensure_psi_sets(h, 1 << PmlAxisDev::kH2)) return -1;
+  for (int par = 0; par < 2; ++par)
+    for (int ep = 0; ep < 2; ++ep)
+      if (upload_pml_block(h, &h->pml_blk[mask][par][ep], mask, par, ep, kPsiEInPlace)) return -1;
   h->pml_blk_ok[mask] = true;
   return 0;
 }
-// the blocks of shell2_step_kernel: all axes with layers, both sides read the current sets and write the other ones; the second
-// E-side set is allocated here (and the in-place blocks, which name it for the other parity, are rebuilt on their next use)
+// the blocks of shell2_step_kernel: all axes with layers.  The second E-side set is allocated here; the in-place blocks name it for
+// the other parity, so a fresh one sends them to be rebuilt (no hole block can be valid without it)
 int ensure_pml_blocks2(FdtdSolver* h) {
   if (h->pml_blk2_ok) return 0;
   bool fresh = false;
-  for (int a = 0; a < 3; ++a) {
-    PmlAxisDev& P = h->pml[a];
-    if (P.ns == 0) continue;
-    for (int q = 0; q < 2; ++q) {
-      if (!P.psi_h2[q] && dev_alloc(h, &P.psi_h2[q], P.psi_count + P.psi_plane)) return -1;
-      if (!P.psi_e2[q]) { if (dev_alloc(h, &P.psi_e2[q], P.psi_count)) return -1; fresh = true; }
-    }
-  }
-  if (fresh) for (bool& ok : h->pml_blk_ok) ok = false;
-  for (int par = 0; par < 2; ++par) {
-    for (int ep = 0; ep < 2; ++ep) {
-      PmlP pm{};
-      for (int a = 0; a < 3; ++a)
-        fill_pml_axis(h, a, h->pml[a].ns > 0, par != h->pml_parity, ep != h->pml_e_parity, false, pm.ax[a]);
-      if (!h->pml_blk2[par][ep] && dev_alloc(h, &h->pml_blk2[par][ep], 1, false)) return -1;
-      if (hipMemcpy(h->pml_blk2[par][ep], &pm, sizeof(PmlP), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(h, "upload of the CPML parameter block failed");
-    }
-  }
+  if (ensure_psi_sets(h, 1 << PmlAxisDev::kH2 | 1 << PmlAxisDev::kE2, &fresh)) return -1;
+  if (fresh) invalidate_pml_blocks(h);
+  for (int par = 0; par < 2; ++par)
+    for (int ep = 0; ep < 2; ++ep)
+      if (upload_pml_block(h, &h->pml_blk2[par][ep], 7, par, ep, kPsiPingPong)) return -1;
   h->pml_blk2_ok = true;
   return 0;
 }
@@ -846,40 +875,11 @@ int ensure_pml_blocks2(FdtdSolver* h) {
 int ensure_pml_blocks_hole(FdtdSolver* h) {
   if (h->pml_blk_hole_ok) return 0;
   if (ensure_pml_blocks2(h)) return -1;
-  const int N[3] = {h->g.nx, h->g.ny, h->g.nz};
-  for (int a = 0; a < 3; ++a) {
-    PmlAxisDev& P = h->pml[a];
-    if (P.ns == 0) continue;
-    for (int q = 0; q < 2; ++q) {
-      if (!P.psi_ht[q] && dev_alloc(h, &P.psi_ht[q], P.psi_count + P.psi_plane)) return -1;
-      if (!P.psi_et[q] && dev_alloc(h, &P.psi_et[q], P.psi_count)) return -1;
-    }
-  }
+  if (ensure_psi_sets(h, 1 << PmlAxisDev::kHt | 1 << PmlAxisDev::kEt)) return -1;
   for (int step = 0; step < 2; ++step)
     for (int par = 0; par < 2; ++par)
-      for (int ep = 0; ep < 2; ++ep) {
-        PmlP pm{};
-        for (int a = 0; a < 3; ++a) {
-          const PmlAxisDev& P = h->pml[a];
-          PmlAxisP& A = pm.ax[a];
-          fill_pml_axis(h, a, P.ns > 0, par != h->pml_parity, ep != h->pml_e_parity, false, A);     // (coefficients, membership; pointers below)
-          float* const h_cur[2] = {const_cast<float*>(A.ph0), const_cast<float*>(A.ph1)};
-          float* const h_oth[2] = {A.ph0n, A.ph1n};
-          float* const e_cur[2] = {A.pe0, A.pe1};
-          float* const e_oth[2] = {A.pe0n, A.pe1n};
-          if (step == 0) {
-            A.ph0 = h_cur[0]; A.ph1 = h_cur[1]; A.ph0n = P.psi_ht[0]; A.ph1n = P.psi_ht[1];
-            A.pe0 = e_cur[0]; A.pe1 = e_cur[1]; A.pe0n = P.psi_et[0]; A.pe1n = P.psi_et[1];
-          } else {
-            A.ph0 = P.psi_ht[0]; A.ph1 = P.psi_ht[1]; A.ph0n = h_oth[0]; A.ph1n = h_oth[1];
-            A.pe0 = P.psi_et[0]; A.pe1 = P.psi_et[1]; A.pe0n = e_oth[0]; A.pe1n = e_oth[1];
-          }
-          (void)N;
-        }
-        if (!h->pml_blk_hole[step][par][ep] && dev_alloc(h, &h->pml_blk_hole[step][par][ep], 1, false)) return -1;
-        if (hipMemcpy(h->pml_blk_hole[step][par][ep], &pm, sizeof(PmlP), hipMemcpyHostToDevice) != hipSuccess)
-          return fail(h, "upload of the CPML parameter block failed");
-      }
+      for (int ep = 0; ep < 2; ++ep)
+        if (upload_pml_block(h, &h->pml_blk_hole[step][par][ep], 7, par, ep, step == 0 ? kPsiToTemp : kPsiFromTemp)) return -1;
   h->pml_blk_hole_ok = true;
   return 0;
 }
@@ -2468,24 +2468,17 @@ void launch_pml(FdtdSolver* h, bool e_side, int kbeg, int kend, hipStream_t st, 
     const bool vec4 = (a != 0) && (g.nx % 4 == 0);      // y / z slabs: float4 along x
     const long long most = std::max(cells[0], cells[1]);
     const dim3 grid(nblk(vec4 ? most / 4 : most), n_sl);
-    if (vec4 && e_side)
-      hipLaunchKernelGGL(pml_e4_kernel, grid, dim3(256), 0, st, g, sl[0], sl[1], field_ptr(h, c1),
-                         field_ptr(h, c2), (const float*)field_ptr(h, 3 + c1), (const float*)field_ptr(h, 3 + c2),
-                         P.psi_e[0], P.psi_e[1], (const float4*)P.ce4, (const float*)h->idl[a], (const uint32_t*)h->mat4,
-                         (const float2*)h->lut, h->cb1, (const uint32_t*)h->mat4b);
-    else if (vec4)
-      hipLaunchKernelGGL(pml_h4_kernel, grid, dim3(256), 0, st, g, sl[0], sl[1], field_ptr(h, 3 + c1),
-                         field_ptr(h, 3 + c2), (const float*)field_ptr(h, c1), (const float*)field_ptr(h, c2),
-                         P.psi_h[0], P.psi_h[1], (const float4*)P.ch4, (const float*)h->ip[a]);
-    else if (e_side)
-      hipLaunchKernelGGL(pml_e_kernel, grid, dim3(256), 0, st, g, sl[0], sl[1], field_ptr(h, c1),
-                         field_ptr(h, c2), (const float*)field_ptr(h, 3 + c1), (const float*)field_ptr(h, 3 + c2),
-                         P.psi_e[0], P.psi_e[1], (const float4*)P.ce4, (const float*)h->idl[a], (const uint32_t*)h->mat4,
-                         (const float2*)h->lut, h->cb1, (const uint32_t*)h->mat4b);
-    else
-      hipLaunchKernelGGL(pml_h_kernel, grid, dim3(256), 0, st, g, sl[0], sl[1], field_ptr(h, 3 + c1),
-                         field_ptr(h, 3 + c2), (const float*)field_ptr(h, c1), (const float*)field_ptr(h, c2),
-                         P.psi_h[0], P.psi_h[1], (const float4*)P.ch4, (const float*)h->ip[a]);
+    if (e_side) {
+      const auto kern = vec4 ? pml_slab_kernel<true, 4> : pml_slab_kernel<true, 1>;
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, g, sl[0], sl[1],
+                         field_ptr(h, c1), field_ptr(h, c2), (const float*)field_ptr(h, 3 + c1), (const float*)field_ptr(h, 3 + c2),
+                         P.psi_e[0], P.psi_e[1], (const float4*)P.ce4, SlabEP{h->idl[a], h->mat4, h->lut, h->cb1, h->mat4b});
+    } else {
+      const auto kern = vec4 ? pml_slab_kernel<false, 4> : pml_slab_kernel<false, 1>;
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, g, sl[0], sl[1],
+                         field_ptr(h, 3 + c1), field_ptr(h, 3 + c2), (const float*)field_ptr(h, c1), (const float*)field_ptr(h, c2),
+                         P.psi_h[0], P.psi_h[1], (const float4*)P.ch4, SlabHP{h->ip[a]});
+    }
   }
 }
 
@@ -2511,12 +2504,10 @@ void launch_damp(FdtdSolver* h, bool e_side, int kbeg, int kend, hipStream_t st)
       if (s_hi <= s_lo) continue;
       const long long bx = (a == 0) ? (s_hi - s_lo) : g.nx, by = (a == 1) ? (s_hi - s_lo) : g.ny;
       const long long bz = (a == 2) ? (s_hi - s_lo) : (kend - kbeg);
-      if (a != 0 && g.nx % 4 == 0)
-        hipLaunchKernelGGL(damp4_kernel, dim3(nblk(bx / 4 * by * bz)), dim3(256), 0, st, g, d, f0, f1, f2,
-                           e_side ? 0 : 1, a, s_lo, s_hi - s_lo, kbeg, kend);
-      else
-        hipLaunchKernelGGL(damp_kernel, dim3(nblk(bx * by * bz)), dim3(256), 0, st, g, d, f0, f1, f2,
-                           e_side ? 0 : 1, a, s_lo, s_hi - s_lo, kbeg, kend);
+      const bool vec4 = a != 0 && g.nx % 4 == 0;        // y / z layers: float4 along x
+      const auto kern = vec4 ? damp_kernel<4> : damp_kernel<1>;
+      hipLaunchKernelGGL(kern, dim3(nblk((vec4 ? bx / 4 : bx) * by * bz)), dim3(256), 0, st,
+                         g, d, f0, f1, f2, e_side ? 0 : 1, a, s_lo, s_hi - s_lo, kbeg, kend);
     }
 }
 
@@ -3067,7 +3058,7 @@ int exchange_fused_all(FdtdSolver* h, hipStream_t st, bool pml_with_sweep = fals
   // H-side psi of that plane — my top plane, CURRENT set (what the next sweep reads): into slot nz of its arrays.
   // Decided by the configuration alone (both sides must post the same messages), not by what a rank's sweep ends up doing.
   const bool psi_too = pml_with_sweep && h->pml_fused > 0;
-  auto psi_of = [&](int a, int q) { const PmlAxisDev& P = h->pml[a]; return psi_set == 1 ? P.psi_ht[q] : (psi_set == 2 ? P.psi_h2[q] : P.psi_h[q]); };
+  auto psi_of = [&](int a, int q) { return h->pml[a].set(psi_set == 1 ? PmlAxisDev::kHt : (psi_set == 2 ? PmlAxisDev::kH2 : PmlAxisDev::kH))[q]; };
   // posting order mirrors the peer's (see exchange_fused_e): [to-hi][to-lo] <-> [from-lo][from-hi]
   NCCLCHK(h, ncclGroupStart());
   if (has_hi) {
@@ -3593,14 +3584,12 @@ int fdtd_set_pml(FdtdSolver* h, int axis, int n_lo, int n_hi, const float* kinv_
   // (x, y axes: one more plane behind the H-side arrays — the ghost slot a z-slab rank receives its lower neighbour's
   //  top-plane psi into, fdtd_kernels.hpp GridP::psi_ghost)
   P.psi_plane = axis < 2 ? P.psi_count / (size_t)h->cfg.nz : 0;
-  for (int q = 0; q < 2; ++q) {
-    if (P.ns > 0 && dev_alloc(h, &P.psi_e[q], P.psi_count)) return -1;
-    if (P.ns > 0 && dev_alloc(h, &P.psi_h[q], P.psi_count + P.psi_plane)) return -1;
-    P.psi_h2[q] = nullptr;
-    P.psi_e2[q] = nullptr; P.psi_ht[q] = nullptr; P.psi_et[q] = nullptr;
-  }
-  for (bool& ok : h->pml_blk_ok) ok = false;          // parameter blocks are rebuilt on next use
-  h->pml_blk2_ok = false; h->pml_blk_hole_ok = false;
+  for (int q = 0; q < 2; ++q)
+    for (int s = 0; s < PmlAxisDev::kSets; ++s) {
+      if (s >= PmlAxisDev::kH2) P.set(s)[q] = nullptr;            // the lazily allocated sets: on their next use
+      else if (P.ns > 0 && dev_alloc(h, &P.set(s)[q], P.set_count(s))) return -1;
+    }
+  invalidate_pml_blocks(h);
   return 0;
 }
 
@@ -4336,14 +4325,9 @@ int fdtd_reset(FdtdSolver* h) {
   for (int a = 0; a < 3; ++a) {
     PmlAxisDev& P = h->pml[a];
     if (P.n == 0) continue;
-    for (int s = 0; s < 2; ++s) {
-      if (P.psi_e[s]) HIPCHK(h, hipMemset(P.psi_e[s], 0, P.psi_count * 4));
-      if (P.psi_h[s]) HIPCHK(h, hipMemset(P.psi_h[s], 0, (P.psi_count + P.psi_plane) * 4));
-      if (P.psi_h2[s]) HIPCHK(h, hipMemset(P.psi_h2[s], 0, (P.psi_count + P.psi_plane) * 4));
-      if (P.psi_e2[s]) HIPCHK(h, hipMemset(P.psi_e2[s], 0, P.psi_count * 4));
-      if (P.psi_et[s]) HIPCHK(h, hipMemset(P.psi_et[s], 0, P.psi_count * 4));
-      if (P.psi_ht[s]) HIPCHK(h, hipMemset(P.psi_ht[s], 0, (P.psi_count + P.psi_plane) * 4));
-    }
+    for (int q = 0; q < 2; ++q)
+      for (int s = 0; s < PmlAxisDev::kSets; ++s)
+        if (P.set(s)[q]) HIPCHK(h, hipMemset(P.set(s)[q], 0, P.set_count(s) * 4));
   }
   for (AdeGroup& a : h->ade) {
     HIPCHK(h, hipMemset(a.e_old, 0, (size_t)a.n * 4));
@@ -4399,7 +4383,7 @@ int fdtd_set_option(FdtdSolver* h, int key, int value) {
     case FDTD_OPT_ZCHUNK: if (value < 1) break; h->zchunk = value; h->zchunk_f = value; h->user_geometry = true; return 0;
     case FDTD_OPT_ROWS: if (value < 1 || value > 15) break; h->rows = value > 8 ? 8 : value; h->rows_f = value; h->user_geometry = true; return 0;
     case FDTD_OPT_XCD_REMAP: if (value > 1024) break; h->xcd_remap = value < 0 ? -1 : value; return 0;
-    case FDTD_OPT_PML_FUSED: h->pml_fused = value < 0 ? -1 : (value & 7); for (bool& ok : h->pml_blk_ok) ok = false; h->pml_blk2_ok = false; h->pml_blk_hole_ok = false; return 0;
+    case FDTD_OPT_PML_FUSED: h->pml_fused = value < 0 ? -1 : (value & 7); invalidate_pml_blocks(h); return 0;
     case FDTD_OPT_BND_PLANES: h->bnd_planes = value > 0 ? value : 0; return 0;
     case FDTD_OPT_AUTOTUNE: h->autotune = value < 0 ? 0 : (value > 2 ? 1 : value); if (value) h->tuned = false; return 0;
     case FDTD_OPT_MEM_HINTS: h->mem_hints = value != 0; return 0;

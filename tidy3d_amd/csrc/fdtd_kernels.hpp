@@ -372,8 +372,8 @@ __global__ __launch_bounds__(512) void e_update_kernel(GridP g, FieldP f, StepP 
 }
 
 // ---- CPML inside the fused sweep ------------------------------------------------------------
-// Same recursion and the same operation order as the slab kernels pml_h_kernel / pml_e_kernel
-// (K3 below), applied to registers: H-side corrections to H^{n-1/2} before upd_h, E-side ones to
+// Same recursion and the same operation order as the slab kernel pml_slab_kernel (both sides;
+// K3 below), applied to registers: H-side corrections to H^{n-1/2} before upd_h, E-side ones to
 // E^{n+1} after upd_e.  Halo rows / columns / prologue planes recompute the corrected value from
 // psi without storing it, so psi is updated exactly once per cell.
 //
@@ -1147,236 +1147,109 @@ __device__ __forceinline__ long long psi_index(const GridP& g, const SlabP& sl, 
   return ((long long)si * g.ny + j) * g.nx + i;
 }
 
-// E-side:  E_{a+1} -= Cb * ((kinv-1) d(H_{a+2})/da + psi1),  E_{a+2} += Cb * ((kinv-1) d(H_{a+1})/da + psi2)
-__global__ __launch_bounds__(256) void pml_e_kernel(GridP g, SlabP sl_lo, SlabP sl_hi, float* e1, float* e2, const float* h1,
-                                                     const float* h2, float* psi1, float* psi2,
-                                                     const float4* cf4,
-                                                     const float* idl, const uint32_t* m4,
-                                                     const float2* lut, float cb_uniform, const uint32_t* m4b) {
+// One slab kernel for both sides and both widths (V cells of a row per thread).  With (c1, c2) = (a+1, a+2) mod 3:
+//   E side:  E_c1 -= Cb * ((kinv-1) d(H_c2)/da + psi1),  E_c2 += Cb * ((kinv-1) d(H_c1)/da + psi2)      (f = E, o = H)
+//   H side:  H_c1 += ch * ((kinv-1) d(E_c2)/da + psi1),  H_c2 -= ch * ((kinv-1) d(E_c1)/da + psi2)      (f = H, o = E)
+// The derivative along a is (up - dn) * w: on the E side `up` is the cell's own H and `dn` its lower neighbour (w = idl), on the
+// H side `dn` is the cell's own E and `up` its upper neighbour (w = ipl).  The library is built with -ffp-contract=off: the
+// expressions below, in the order written, are the arithmetic of every instantiation — and of the in-sweep forms held to them.
+struct SlabEP { const float* idl; const uint32_t* m4; const float2* lut; float cb_uniform; const uint32_t* m4b; };
+struct SlabHP { const float* ipl; };
+template <bool E_SIDE> struct SlabSide { using P = SlabEP; };
+template <> struct SlabSide<false> { using P = SlabHP; };
+
+template <bool E_SIDE, int V>
+__global__ __launch_bounds__(256) void pml_slab_kernel(GridP g, SlabP sl_lo, SlabP sl_hi, float* f1, float* f2, const float* o1,
+                                                        const float* o2, float* psi1, float* psi2, const float4* cf4,
+                                                        typename SlabSide<E_SIDE>::P sp) {
+  static_assert(V == 1 || V == 4, "one cell per thread, or four cells of a row (y / z slabs of float4-aligned rows)");
   const SlabP sl = blockIdx.y ? sl_hi : sl_lo;   // both faces of an axis in one launch (disjoint cells)
-  const int bx = (sl.a == 0) ? sl.s_n : g.nx;
+  bool ax = false;                               // an x slab: V = 4 is never launched for a == 0 (launch_pml)
+  if constexpr (V == 1) ax = sl.a == 0;
+  const int bx = ax ? sl.s_n : g.nx / V;
   const int by = (sl.a == 1) ? sl.s_n : g.ny;
   const int bz = sl.kend - sl.kbeg;
   const long long total = (long long)bx * by * bz;
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
-  const int lx = (int)(t % bx);
-  const int ly = (int)((t / bx) % by);
-  const int lz = (int)(t / ((long long)bx * by));
-  const int i = (sl.a == 0) ? sl.s_lo + lx : lx;
-  const int j = (sl.a == 1) ? sl.s_lo + ly : ly;
-  const int k = sl.kbeg + lz;
-  const int ia = (sl.a == 0) ? i : (sl.a == 1 ? j : k);
-  const int c1 = (sl.a + 1) % 3, c2 = (sl.a + 2) % 3;
-  const int idx3[3] = {i, j, k};
-  const int bc0[3] = {g.bcx0, g.bcy0, g.pec_z0 ? BC_PEC : BC_NEIGHBOR};
-  const long long stride = (sl.a == 0) ? 1 : (sl.a == 1 ? (long long)g.nx : g.sxy);
+  const int i = (int)(t % bx) * V + (ax ? sl.s_lo : 0);
+  const int j = (int)((t / bx) % by) + (sl.a == 1 ? sl.s_lo : 0);
+  const int k = sl.kbeg + (int)(t / ((long long)bx * by));
+  const int ia = ax ? i : (sl.a == 1 ? j : k);
+  const int na = ax ? g.nx : (sl.a == 1 ? g.ny : g.nz);
+  const long long stride = ax ? 1 : (sl.a == 1 ? (long long)g.nx : g.sxy);
+  const long long wrap = (long long)(na - 1) * stride;     // to the cell one period away (x / y walls)
   const long long p = (long long)k * g.sxy + (long long)j * g.nx + i;
-  float d1, d2;   // d/da of H_{a+1}, H_{a+2}
-  if (ia == 0 && sl.a != 2) {
-    if (bc0[sl.a] == BC_PEC) return;                  // both components are wall-tangential: stay 0
-    if (bc0[sl.a] == BC_PMC) { d1 = 2.f * h1[p] * idl[ia]; d2 = 2.f * h2[p] * idl[ia]; }
-    else { const long long w = (long long)((sl.a == 0 ? g.nx : g.ny) - 1) * stride;
-           d1 = (h1[p] - h1[p + w]) * idl[ia]; d2 = (h2[p] - h2[p + w]) * idl[ia]; }
+  float up1[V], up2[V], dn1[V], dn2[V];
+  bool pmc = false;                              // E side, lower PMC wall: H is odd about it, d = 2 H w
+  if constexpr (E_SIDE) {
+    ldv<V>(up1, o1 + p);
+    ldv<V>(up2, o2 + p);
+    if (ia == 0 && sl.a != 2) {
+      const int bc0 = ax ? g.bcx0 : g.bcy0;
+      if (bc0 == BC_PEC) return;                 // both components are wall-tangential: stay 0
+      if (bc0 == BC_PMC) { pmc = true; zero<V>(dn1); zero<V>(dn2); }
+      else { ldv<V>(dn1, o1 + p + wrap); ldv<V>(dn2, o2 + p + wrap); }
+    } else {
+      if (ia == 0 && g.pec_z0) return;           // z wall (ghost plane otherwise)
+      ldv<V>(dn1, o1 + p - stride);
+      ldv<V>(dn2, o2 + p - stride);
+    }
   } else {
-    if (ia == 0 && g.pec_z0) return;                  // z wall (ghost plane otherwise)
-    d1 = (h1[p] - h1[p - stride]) * idl[ia];
-    d2 = (h2[p] - h2[p - stride]) * idl[ia];
+    if (ia == na - 1 && sl.a != 2) {
+      if ((ax ? g.bcx1 : g.bcy1) == BC_PERIODIC) { ldv<V>(up1, o1 + p - wrap); ldv<V>(up2, o2 + p - wrap); }
+      else { zero<V>(up1); zero<V>(up2); }
+    } else {
+      ldv<V>(up1, o1 + p + stride);              // for a == 2 the ghost plane holds the boundary value
+      ldv<V>(up2, o2 + p + stride);
+    }
+    ldv<V>(dn1, o1 + p);
+    ldv<V>(dn2, o2 + p);
   }
   const int si = sl.psi_base + (ia - sl.s_lo);
   const long long q = psi_index(g, sl, i, j, k, si);
   const float4 cf = cf4[ia];
   const float kv = cf.x, b = cf.y, c = cf.z;
-  const float p1 = b * psi1[q] + c * d2;     // psi of E_{a+1} follows d(H_{a+2})/da
-  const float p2 = b * psi2[q] + c * d1;     // psi of E_{a+2} follows d(H_{a+1})/da
-  psi1[q] = p1;
-  psi2[q] = p2;
-  const uint32_t mw = m4 ? m4[p] : 0u;
-  const float cb1 = m4 ? lut[medium_of(mw, m4b, p, c1)].y : cb_uniform;
-  const float cb2 = m4 ? lut[medium_of(mw, m4b, p, c2)].y : cb_uniform;
-  // PEC walls of the other transverse axis
-  const bool w1 = (idx3[c2] == 0) && (bc0[c2] == BC_PEC);   // E_{c1} is tangential to the c2-wall
-  const bool w2 = (idx3[c1] == 0) && (bc0[c1] == BC_PEC);
-  if (!w1) e1[p] -= cb1 * (kv * d2 + p1);
-  if (!w2) e2[p] += cb2 * (kv * d1 + p2);
-}
-
-// H-side:  H_{a+1} += ch * ((kinv-1) d(E_{a+2})/da + psi1),  H_{a+2} -= ch * ((kinv-1) d(E_{a+1})/da + psi2)
-__global__ __launch_bounds__(256) void pml_h_kernel(GridP g, SlabP sl_lo, SlabP sl_hi, float* h1, float* h2, const float* e1,
-                                                     const float* e2, float* psi1, float* psi2,
-                                                     const float4* cf4,
-                                                     const float* ipl) {
-  const SlabP sl = blockIdx.y ? sl_hi : sl_lo;   // both faces of an axis in one launch (disjoint cells)
-  const int bx = (sl.a == 0) ? sl.s_n : g.nx;
-  const int by = (sl.a == 1) ? sl.s_n : g.ny;
-  const int bz = sl.kend - sl.kbeg;
-  const long long total = (long long)bx * by * bz;
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int lx = (int)(t % bx);
-  const int ly = (int)((t / bx) % by);
-  const int lz = (int)(t / ((long long)bx * by));
-  const int i = (sl.a == 0) ? sl.s_lo + lx : lx;
-  const int j = (sl.a == 1) ? sl.s_lo + ly : ly;
-  const int k = sl.kbeg + lz;
-  const int ia = (sl.a == 0) ? i : (sl.a == 1 ? j : k);
-  const int na = (sl.a == 0) ? g.nx : (sl.a == 1 ? g.ny : g.nz);
-  const int bc1 = (sl.a == 0) ? g.bcx1 : (sl.a == 1 ? g.bcy1 : BC_NEIGHBOR);
-  const long long stride = (sl.a == 0) ? 1 : (sl.a == 1 ? (long long)g.nx : g.sxy);
-  const long long p = (long long)k * g.sxy + (long long)j * g.nx + i;
-  float n1, n2;   // E_{a+1}, E_{a+2} at ia + 1
-  if (ia == na - 1 && sl.a != 2) {
-    if (bc1 == BC_PERIODIC) { n1 = e1[p - (long long)(na - 1) * stride]; n2 = e2[p - (long long)(na - 1) * stride]; }
-    else { n1 = 0.f; n2 = 0.f; }
-  } else {
-    n1 = e1[p + stride];      // for a == 2 the ghost plane holds the boundary value
-    n2 = e2[p + stride];
-  }
-  const float d1 = (n1 - e1[p]) * ipl[ia];
-  const float d2 = (n2 - e2[p]) * ipl[ia];
-  const int si = sl.psi_base + (ia - sl.s_lo);
-  const long long q = psi_index(g, sl, i, j, k, si);
-  const float4 cf = cf4[ia];
-  const float kv = cf.x, b = cf.y, c = cf.z;
-  const float p1 = b * psi1[q] + c * d2;
-  const float p2 = b * psi2[q] + c * d1;
-  psi1[q] = p1;
-  psi2[q] = p2;
-  h1[p] += g.ch * (kv * d2 + p1);
-  h2[p] -= g.ch * (kv * d1 + p2);
-}
-
-// float4 versions for the y and z slabs (rows are contiguous along x): one thread = 4 cells, same
-// per-element arithmetic as the scalar kernels above.
-__global__ __launch_bounds__(256) void pml_e4_kernel(GridP g, SlabP sl_lo, SlabP sl_hi, float* e1, float* e2, const float* h1,
-                                                      const float* h2, float* psi1, float* psi2,
-                                                      const float4* cf4,
-                                                      const float* idl, const uint32_t* m4,
-                                                      const float2* lut, float cb_uniform, const uint32_t* m4b) {
-  const SlabP sl = blockIdx.y ? sl_hi : sl_lo;   // both faces of an axis in one launch (disjoint cells)
-  constexpr int V = 4;
-  const int bx = g.nx / V;
-  const int by = (sl.a == 1) ? sl.s_n : g.ny;
-  const int bz = sl.kend - sl.kbeg;
-  const long long total = (long long)bx * by * bz;
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int i0 = (int)(t % bx) * V;
-  const int ly = (int)((t / bx) % by);
-  const int lz = (int)(t / ((long long)bx * by));
-  const int j = (sl.a == 1) ? sl.s_lo + ly : ly;
-  const int k = sl.kbeg + lz;
-  const int ia = (sl.a == 1) ? j : k;
-  const int c1 = (sl.a + 1) % 3, c2 = (sl.a + 2) % 3;
-  const int bcz0 = g.pec_z0 ? BC_PEC : BC_NEIGHBOR;
-  const long long stride = (sl.a == 1) ? (long long)g.nx : g.sxy;
-  const long long p = (long long)k * g.sxy + (long long)j * g.nx + i0;
-  float a1[V], a2[V], b1[V], b2[V];
-  ldv<V>(a1, h1 + p);
-  ldv<V>(a2, h2 + p);
-  float s1 = 1.f;          // derivative = (a - s * b) * idl  with b the lower neighbour
-  if (ia == 0 && sl.a == 1) {
-    if (g.bcy0 == BC_PEC) return;
-    if (g.bcy0 == BC_PMC) { for (int e = 0; e < V; ++e) { b1[e] = a1[e]; b2[e] = a2[e]; } s1 = -1.f; }
-    else { ldv<V>(b1, h1 + p + (long long)(g.ny - 1) * stride); ldv<V>(b2, h2 + p + (long long)(g.ny - 1) * stride); }
-  } else {
-    if (ia == 0 && g.pec_z0) return;
-    ldv<V>(b1, h1 + p - stride);
-    ldv<V>(b2, h2 + p - stride);
-  }
-  const int si = sl.psi_base + (ia - sl.s_lo);
-  const long long q = psi_index(g, sl, i0, j, k, si);
-  const float4 cf = cf4[ia];
-  const float kv = cf.x, b = cf.y, c = cf.z, w = idl[ia];
+  float w;
+  if constexpr (E_SIDE) w = sp.idl[ia]; else w = sp.ipl[ia];
   float q1[V], q2[V], x1[V], x2[V];
   ldv<V>(q1, psi1 + q);
   ldv<V>(q2, psi2 + q);
-  ldv<V>(x1, e1 + p);
-  ldv<V>(x2, e2 + p);
-  uint32_t mw[V] = {0u, 0u, 0u, 0u};
-  if (m4) ldm<V>(mw, m4 + p);
-  // E_{c1} is tangential to the c2-wall, E_{c2} to the c1-wall; along x only element i == 0 can sit on it
-  const int jk[3] = {0, j, k};
-  const int bc0[3] = {g.bcx0, g.bcy0, bcz0};
+  ldv<V>(x1, f1 + p);
+  ldv<V>(x2, f2 + p);
+  uint32_t mw[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) mw[e] = 0u;
+  if constexpr (E_SIDE) { if (sp.m4) ldm<V>(mw, sp.m4 + p); }
 #pragma unroll
   for (int e = 0; e < V; ++e) {
-    const float d1 = (s1 > 0.f) ? (a1[e] - b1[e]) * w : 2.f * a1[e] * w;
-    const float d2 = (s1 > 0.f) ? (a2[e] - b2[e]) * w : 2.f * a2[e] * w;
-    const float p1 = b * q1[e] + c * d2;
-    const float p2 = b * q2[e] + c * d1;
+    const float d1 = pmc ? 2.f * up1[e] * w : (up1[e] - dn1[e]) * w;     // d/da of the c1 component of o
+    const float d2 = pmc ? 2.f * up2[e] * w : (up2[e] - dn2[e]) * w;
+    const float p1 = b * q1[e] + c * d2;         // psi of f_c1 follows d(o_c2)/da
+    const float p2 = b * q2[e] + c * d1;         // psi of f_c2 follows d(o_c1)/da
     q1[e] = p1;
     q2[e] = p2;
-    const float cb1 = m4 ? lut[medium_of(mw[e], m4b, p + e, c1)].y : cb_uniform;
-    const float cb2 = m4 ? lut[medium_of(mw[e], m4b, p + e, c2)].y : cb_uniform;
-    const int i3c2 = (c2 == 0) ? i0 + e : jk[c2];
-    const int i3c1 = (c1 == 0) ? i0 + e : jk[c1];
-    const bool w1 = (i3c2 == 0) && (bc0[c2] == BC_PEC);
-    const bool w2 = (i3c1 == 0) && (bc0[c1] == BC_PEC);
-    if (!w1) x1[e] -= cb1 * (kv * d2 + p1);
-    if (!w2) x2[e] += cb2 * (kv * d1 + p2);
+    if constexpr (E_SIDE) {
+      const int c1 = (sl.a + 1) % 3, c2 = (sl.a + 2) % 3;
+      const float cb1 = sp.m4 ? sp.lut[medium_of(mw[e], sp.m4b, p + e, c1)].y : sp.cb_uniform;
+      const float cb2 = sp.m4 ? sp.lut[medium_of(mw[e], sp.m4b, p + e, c2)].y : sp.cb_uniform;
+      // PEC walls of the other transverse axes: E_c1 is tangential to the c2-wall, E_c2 to the c1-wall
+      auto on_wall = [&](int cw) {
+        const int ic = cw == 0 ? i + e : (cw == 1 ? j : k);
+        const int bc = cw == 0 ? g.bcx0 : (cw == 1 ? g.bcy0 : (g.pec_z0 ? BC_PEC : BC_NEIGHBOR));
+        return ic == 0 && bc == BC_PEC;
+      };
+      if (!on_wall(c2)) x1[e] -= cb1 * (kv * d2 + p1);
+      if (!on_wall(c1)) x2[e] += cb2 * (kv * d1 + p2);
+    } else {
+      x1[e] += g.ch * (kv * d2 + p1);
+      x2[e] -= g.ch * (kv * d1 + p2);
+    }
   }
   stv<V>(psi1 + q, q1);
   stv<V>(psi2 + q, q2);
-  stv<V>(e1 + p, x1);
-  stv<V>(e2 + p, x2);
-}
-
-__global__ __launch_bounds__(256) void pml_h4_kernel(GridP g, SlabP sl_lo, SlabP sl_hi, float* h1, float* h2, const float* e1,
-                                                      const float* e2, float* psi1, float* psi2,
-                                                      const float4* cf4,
-                                                      const float* ipl) {
-  const SlabP sl = blockIdx.y ? sl_hi : sl_lo;   // both faces of an axis in one launch (disjoint cells)
-  constexpr int V = 4;
-  const int bx = g.nx / V;
-  const int by = (sl.a == 1) ? sl.s_n : g.ny;
-  const int bz = sl.kend - sl.kbeg;
-  const long long total = (long long)bx * by * bz;
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int i0 = (int)(t % bx) * V;
-  const int ly = (int)((t / bx) % by);
-  const int lz = (int)(t / ((long long)bx * by));
-  const int j = (sl.a == 1) ? sl.s_lo + ly : ly;
-  const int k = sl.kbeg + lz;
-  const int ia = (sl.a == 1) ? j : k;
-  const long long stride = (sl.a == 1) ? (long long)g.nx : g.sxy;
-  const long long p = (long long)k * g.sxy + (long long)j * g.nx + i0;
-  float n1[V], n2[V], c1v[V], c2v[V];
-  if (ia == g.ny - 1 && sl.a == 1) {
-    if (g.bcy1 == BC_PERIODIC) {
-      ldv<V>(n1, e1 + p - (long long)(g.ny - 1) * stride);
-      ldv<V>(n2, e2 + p - (long long)(g.ny - 1) * stride);
-    } else { zero<V>(n1); zero<V>(n2); }
-  } else {
-    ldv<V>(n1, e1 + p + stride);
-    ldv<V>(n2, e2 + p + stride);
-  }
-  ldv<V>(c1v, e1 + p);
-  ldv<V>(c2v, e2 + p);
-  const int si = sl.psi_base + (ia - sl.s_lo);
-  const long long q = psi_index(g, sl, i0, j, k, si);
-  const float4 cf = cf4[ia];
-  const float kv = cf.x, b = cf.y, c = cf.z, w = ipl[ia];
-  float q1[V], q2[V], x1[V], x2[V];
-  ldv<V>(q1, psi1 + q);
-  ldv<V>(q2, psi2 + q);
-  ldv<V>(x1, h1 + p);
-  ldv<V>(x2, h2 + p);
-#pragma unroll
-  for (int e = 0; e < V; ++e) {
-    const float d1 = (n1[e] - c1v[e]) * w;
-    const float d2 = (n2[e] - c2v[e]) * w;
-    const float p1 = b * q1[e] + c * d2;
-    const float p2 = b * q2[e] + c * d1;
-    q1[e] = p1;
-    q2[e] = p2;
-    x1[e] += g.ch * (kv * d2 + p1);
-    x2[e] -= g.ch * (kv * d1 + p2);
-  }
-  stv<V>(psi1 + q, q1);
-  stv<V>(psi2 + q, q2);
-  stv<V>(h1 + p, x1);
-  stv<V>(h2 + p, x2);
+  stv<V>(f1 + p, x1);
+  stv<V>(f2 + p, x2);
 }
 
 // =============================================================================================
@@ -1715,67 +1588,48 @@ struct DampP {
   int lo[3], hi[3];        // layers of axis b: index < lo[b] or index >= hi[b]
 };
 
+// V = 4: y / z layers on float4-aligned rows, four x cells per thread (one 16-byte load and store per component); never for a == 0
+template <int V>
 __global__ __launch_bounds__(256) void damp_kernel(GridP g, DampP d, float* f0, float* f1, float* f2, int is_h,
                                                    int a, int s_lo, int s_n, int kbeg, int kend) {
-  const long long bx = (a == 0) ? s_n : g.nx, by = (a == 1) ? s_n : g.ny;
+  static_assert(V == 1 || V == 4, "one cell per thread, or four cells of a row");
+  bool ax = false;
+  if constexpr (V == 1) ax = a == 0;
+  const long long bx = ax ? s_n : g.nx / V, by = (a == 1) ? s_n : g.ny;
   const long long bz = (a == 2) ? s_n : (kend - kbeg);
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= bx * by * bz) return;
-  const int i = (int)(t % bx) + (a == 0 ? s_lo : 0);
+  const int i = V * (int)(t % bx) + (ax ? s_lo : 0);
   const int j = (int)((t / bx) % by) + (a == 1 ? s_lo : 0);
   const int k = (int)(t / (bx * by)) + (a == 2 ? s_lo : kbeg);
-  if (a >= 1 && (i < d.lo[0] || i >= d.hi[0])) return;
+  // lower axes own the corners: cells of this row inside an x layer belong to the x launch, y-layer rows of a z slab to the y launch
+  auto in_x_layer = [&](int ii) { return !ax && (ii < d.lo[0] || ii >= d.hi[0]); };
+  if constexpr (V == 1) { if (in_x_layer(i)) return; }
   if (a == 2 && (j < d.lo[1] || j >= d.hi[1])) return;
-  const float bxv = d.fb[0][i], cxv = d.fc[0][i];
+  float bxs[V], cxs[V];
+  ldv<V>(bxs, d.fb[0] + i);
+  ldv<V>(cxs, d.fc[0] + i);
   const float byv = d.fb[1][j], cyv = d.fc[1][j];
   const float bzv = d.fb[2][k], czv = d.fc[2][k];
-  float w0, w1, w2;
-  if (is_h) {           // H_c: boundary along c, centres along the other two axes
-    w0 = bxv * cyv * czv; w1 = cxv * byv * czv; w2 = cxv * cyv * bzv;
-  } else {              // E_c: centre along c, boundaries along the other two
-    w0 = cxv * byv * bzv; w1 = bxv * cyv * bzv; w2 = bxv * byv * czv;
-  }
   const long long idx = (long long)k * g.sxy + (long long)j * g.nx + i;
-  f0[idx] *= w0;
-  f1[idx] *= w1;
-  f2[idx] *= w2;
-}
-
-// y / z layers on float4-aligned rows: four x cells per thread (one 16-byte load and store per component)
-__global__ __launch_bounds__(256) void damp4_kernel(GridP g, DampP d, float* f0, float* f1, float* f2, int is_h,
-                                                    int a, int s_lo, int s_n, int kbeg, int kend) {
-  const long long bx = g.nx / 4, by = (a == 1) ? s_n : g.ny;
-  const long long bz = (a == 2) ? s_n : (kend - kbeg);
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= bx * by * bz) return;
-  const int i = 4 * (int)(t % bx);
-  const int j = (int)((t / bx) % by) + (a == 1 ? s_lo : 0);
-  const int k = (int)(t / (bx * by)) + (a == 2 ? s_lo : kbeg);
-  if (a == 2 && (j < d.lo[1] || j >= d.hi[1])) return;
-  const float4 bx4 = *reinterpret_cast<const float4*>(d.fb[0] + i);
-  const float4 cx4 = *reinterpret_cast<const float4*>(d.fc[0] + i);
-  const float byv = d.fb[1][j], cyv = d.fc[1][j];
-  const float bzv = d.fb[2][k], czv = d.fc[2][k];
-  const float bxs[4] = {bx4.x, bx4.y, bx4.z, bx4.w}, cxs[4] = {cx4.x, cx4.y, cx4.z, cx4.w};
-  const long long idx = (long long)k * g.sxy + (long long)j * g.nx + i;
-  float4 v0 = *reinterpret_cast<float4*>(f0 + idx);
-  float4 v1 = *reinterpret_cast<float4*>(f1 + idx);
-  float4 v2 = *reinterpret_cast<float4*>(f2 + idx);
-  float* p0 = reinterpret_cast<float*>(&v0);
-  float* p1 = reinterpret_cast<float*>(&v1);
-  float* p2 = reinterpret_cast<float*>(&v2);
+  float v0[V], v1[V], v2[V];
+  ldv<V>(v0, f0 + idx);
+  ldv<V>(v1, f1 + idx);
+  ldv<V>(v2, f2 + idx);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    // cells of this row that lie in an x layer belong to the x launch (scalar kernel)
-    if (i + q < d.lo[0] || i + q >= d.hi[0]) continue;
-    float w0, w1, w2;            // same products, in the same order, as damp_kernel
-    if (is_h) { w0 = bxs[q] * cyv * czv; w1 = cxs[q] * byv * czv; w2 = cxs[q] * cyv * bzv; }
-    else      { w0 = cxs[q] * byv * bzv; w1 = bxs[q] * cyv * bzv; w2 = bxs[q] * byv * czv; }
-    p0[q] *= w0; p1[q] *= w1; p2[q] *= w2;
+  for (int q = 0; q < V; ++q) {
+    if (in_x_layer(i + q)) continue;
+    float w0, w1, w2;
+    if (is_h) {           // H_c: boundary along c, centres along the other two axes
+      w0 = bxs[q] * cyv * czv; w1 = cxs[q] * byv * czv; w2 = cxs[q] * cyv * bzv;
+    } else {              // E_c: centre along c, boundaries along the other two
+      w0 = cxs[q] * byv * bzv; w1 = bxs[q] * cyv * bzv; w2 = bxs[q] * byv * czv;
+    }
+    v0[q] *= w0; v1[q] *= w1; v2[q] *= w2;
   }
-  *reinterpret_cast<float4*>(f0 + idx) = v0;
-  *reinterpret_cast<float4*>(f1 + idx) = v1;
-  *reinterpret_cast<float4*>(f2 + idx) = v2;
+  stv<V>(f0 + idx, v0);
+  stv<V>(f1 + idx, v1);
+  stv<V>(f2 + idx, v2);
 }
 
 // ---- Bloch boundaries (complex fields as a (Re, Im) pair of real field sets) ------------------

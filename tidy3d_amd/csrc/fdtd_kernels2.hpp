@@ -146,7 +146,7 @@ __device__ __forceinline__ long long rep_at(const GridP& g, int seam, int arr, i
 }
 
 // OPT: the word of fdtd_fused2.hpp (kF2NT ... kF2Rep) — materials as fused_step_kernel<MAT>, absorber layers as the damping of
-// damp_kernel / damp4_kernel applied in registers.  (8-wave workgroups run two per CU: LB = 512 asks for 4 waves per SIMD, i.e. <= 128 VGPRs)
+// damp_kernel<V> applied in registers.  (8-wave workgroups run two per CU: LB = 512 asks for 4 waves per SIMD, i.e. <= 128 VGPRs)
 // x neighbours across the wave: lane i takes the value of lane i+1 / i-1 (the last / first lane keeps its own, as __shfl_down /
 // __shfl_up do).  One DPP move (wave_shl:1 / wave_shr:1, GFX9) instead of a ds_bpermute through the LDS crossbar with its
 // address arithmetic and its lgkmcnt wait on the critical path of every stage.

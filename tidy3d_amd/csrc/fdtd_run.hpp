@@ -82,6 +82,15 @@ int run_stats(Handles hs) {
 }
 
 struct GraphRec { const float* set; int parity; hipGraphExec_t exec; };
+// Axes whose CPML recursions a one-GPU sweep carries: by default all that have layers, FDTD_OPT_PML_FUSED = 0 keeps the slab kernels,
+// any other mask selects axes; none when the workgroup with its halo wave would pass 512 threads (`fits` = false: the request alone,
+// whatever the tile geometry — what Run::setup_schedules asks before the geometry is final)
+int sweep_pml_axes(const FdtdSolver* h, bool fits = true) {
+  if (!any_pml(h) || (fits && 64 * (h->rows_f + 1) > 512)) return 0;
+  return (h->pml_fused < 0 ? 7 : h->pml_fused) & pml_in_sweep_mask(h);
+}
+// a CPML step as three launches by tile class (Run::fused_one): by default from 2^24 cells up
+bool pml_three_launches(const FdtdSolver* h) { return h->pml_split < 0 ? n_cells(h) >= (1LL << 24) : h->pml_split != 0; }
 // The form steps n and n + 1 take when they go out as one pair (Run::choose_pair decides, Run::loop dispatches):
 //   Plain: one two-step sweep over the whole grid; Shell: the bulk as a two-step sweep, the CPML shell as two single steps (round-4 form);
 //   Shell2: the shell as shell2_step_kernel boxes; Shell2Holes: the same with the planes of the source lists as z holes that take single
@@ -331,8 +340,7 @@ struct Run {
     // from device memory (step_dev + offset; the graph's last node advances it by two).  Same launches, same order, same
     // arguments otherwise: bit-identical to direct launches (tests/test_gpu_production_path.py).  One stream only: not
     // with the three-launch CPML split of large grids, not on z-slabs, not with per-launch timing events.
-    split_now = (h->pml_split < 0 ? n_cells(h) >= (1LL << 24) : h->pml_split != 0) && any_pml(h) &&
-                           (((h->pml_fused < 0 ? 7 : h->pml_fused) & pml_in_sweep_mask(h)) & 6) != 0;
+    split_now = pml_three_launches(h) && (sweep_pml_axes(h, false) & 6) != 0;
     graph_ok = fused && !tb_ok && !split_now && !(h->cfg.flags & FDTD_FLAG_TIME_KERNELS) && !has_lists(h) &&    // (first_list_kind says why)
                     h->use_graph > 0;      // on request only: measured on ROCm 7.2 (profiles/r3i) a replayed pair is ~3 us per step
                                            // SLOWER than launching its kernels (64^3 17.6 -> 20.8, 128^3 28.8 -> 31.4, 200^3 81.5 -> 84.0)
@@ -386,12 +394,9 @@ struct Run {
   int fused_one(long long n, bool rec_post) {
     // H-side corrections are additive: pre-apply them to H^{n-1/2}; E-side ones follow the sweep.
     // With pml_in the CPML recursions run inside the sweep (same arithmetic, no slab kernels).
-    // pml_in = axes whose recursions run inside the sweep (default: all that have layers; FDTD_OPT_PML_FUSED
-    // = 0 keeps the slab kernels, any other mask selects axes).  Inside the sweep the field values a slab
+    // pml_in = axes whose recursions run inside the sweep (sweep_pml_axes).  Inside the sweep the field values a slab
     // kernel would re-read and re-write stay in registers: only psi moves (32 B per cell and axis membership).
-    int pml_in = 0;
-    if (any_pml(h) && 64 * (h->rows_f + 1) <= 512)
-      pml_in = (h->pml_fused < 0 ? 7 : h->pml_fused) & pml_in_sweep_mask(h);
+    const int pml_in = sweep_pml_axes(h);
     // (periodic z: the wrapped copies in the ghost planes were taken at the end of the last step, in front of this refresh —
     //  their images beyond an x / y wall are refreshed with the planes they copy; a z-slab rank receives its ghost planes
     //  refreshed by their owner)
@@ -403,8 +408,7 @@ struct Run {
     advance_tfsf_aux(h, false, n, st);
     if (h->cfg.bc[4] == FDTD_BC_PERIODIC) fill_ghost_h(h, st);   // ghost(-1) must carry the pre-corrections too
     // small grids are bound by dependent launches, not by occupancy: one launch of the all-axes instantiation
-    const bool split = h->pml_split < 0 ? n_cells(h) >= (1LL << 24) : h->pml_split != 0;
-    if ((pml_in & 6) == 0 || !split) {
+    if ((pml_in & 6) == 0 || !pml_three_launches(h)) {
       if (launch_fused(h, st, pml_in)) return -1;
     } else {
       // The instantiation that carries the y / z recursions holds their psi values in registers from the
@@ -442,10 +446,7 @@ struct Run {
     if (!exec) {
       // everything a captured launch may allocate or upload must exist before the capture starts
       if (ensure_second_set(h)) return -1;
-      if (any_pml(h) && 64 * (h->rows_f + 1) <= 512) {
-        const int pml_in = (h->pml_fused < 0 ? 7 : h->pml_fused) & pml_in_sweep_mask(h);
-        if (pml_in && ensure_pml_blocks(h, pml_in)) return -1;
-      }
+      if (const int pml_in = sweep_pml_axes(h); pml_in && ensure_pml_blocks(h, pml_in)) return -1;
       if (!h->step_dev && dev_alloc(h, &h->step_dev, 1)) return -1;
       const float* set0 = h->f.ex;
       const int par0 = h->pml_parity | (h->pml_e_parity << 1);
