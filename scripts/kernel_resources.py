@@ -1,13 +1,19 @@
 #!/usr/bin/env python
 """Register / scratch / LDS use of every kernel of one translation unit (hipcc -Rpass-analysis=kernel-resource-usage),
-one line per kernel:  python scripts/kernel_resources.py tidy3d_amd/csrc/fdtd_fused2c.hip [substring]"""
+one line per kernel:  python scripts/kernel_resources.py tidy3d_amd/csrc/fdtd_fused2c.hip [substring]
+(the single-step sweep:  python scripts/kernel_resources.py tidy3d_amd/csrc/fdtd_capi.hip fused_step_kernel).
+The unit's own flags are the build's (tidy3d_amd/build.py SOURCE_FLAGS)."""
+import os
 import re
 import subprocess
 import sys
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from tidy3d_amd.build import SOURCE_FLAGS  # noqa: E402
+
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
-flags = ["-fno-slp-vectorize"] if "fused2" in src else []
+flags = SOURCE_FLAGS.get(os.path.basename(src), [])
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mllvm", "-disable-lsr",
        "-I/opt/rocm/include", *flags, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr

@@ -19,6 +19,16 @@ DEPS = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CS
     os.path.abspath(__file__)]
 
 
+def hip_sources() -> list:
+    """The library's translation units: the list the device build keeps (tidy3d_amd/build.py SOURCES), read from the file so that
+    this script needs neither the package on sys.path nor its imports."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_fdtd_device_build", os.path.join(ROOT, "tidy3d_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return list(mod.SOURCES)
+
+
 def build(force: bool = False) -> str:
     if not force and os.path.exists(LIB) and all(
             os.path.getmtime(d) <= os.path.getmtime(LIB) for d in DEPS):
@@ -31,9 +41,7 @@ def build(force: bool = False) -> str:
     import tempfile
     flags = [cxx, "-O2", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mfma", "-I" + HERE,
              "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-pass-failed"]
-    srcs = [os.path.join(CSRC, "fdtd_capi.hip"), os.path.join(CSRC, "fdtd_fused2.hip"), os.path.join(CSRC, "fdtd_fused2c.hip"),
-            os.path.join(CSRC, "fdtd_fused2d.hip"), os.path.join(CSRC, "fdtd_fused2w.hip"), os.path.join(CSRC, "fdtd_fused2s.hip"), os.path.join(CSRC, "fdtd_shell2.hip"),
-            os.path.join(HERE, "hip_emu.cpp")]
+    srcs = [*hip_sources(), os.path.join(HERE, "hip_emu.cpp")]
     tmp = tempfile.mkdtemp(prefix="fdtd_emu_")
     try:
         procs, objs = [], []

@@ -18,6 +18,7 @@
 
 #include "../../include/fdtd_hip.h"
 #include "fdtd_kernels.hpp"
+#include "fdtd_fused.hpp"
 #include "fdtd_fused2.hpp"
 #include "fdtd_strip.hpp"
 #include "fdtd_shell2_host.hpp"
@@ -921,6 +922,9 @@ void swap_psi_e(FdtdSolver* h) {
 struct ShellSets { FieldP src, dst; int parity; int ex_j0, ex_j1; const PmlP* pm = nullptr; };     // pm: a parameter block of the caller's (z holes of a shell2 pair)
 // One launch of the sweep: planes [k0, k1) and [k2_0, k2_1), `pml` = pml_inside; call sites name the fields they set.
 struct FusedRange { int k0, k1; int pml = 0; int k2_0 = 0, k2_1 = 0; int ty_n = -1, ty_a = 0, ty_gap = 0; bool edge = false; const ShellSets* sh = nullptr; };
+// launches <fused_word(L)>, exactly, or returns false with nothing launched: the list of fdtd_fused.hpp as case labels — this line
+// instantiates the 42 kernels of the single-step sweep
+FDTD_F1_LAUNCHER(launch_fused_step, FDTD_F1_LIST)
 int launch_fused_range(FdtdSolver* h, hipStream_t st, const FusedRange& r) {
   int kbeg = r.k0, kend = r.k1, k2beg = r.k2_0, k2end = r.k2_1, ty_n = r.ty_n, ty_a = r.ty_a, ty_gap = r.ty_gap;
   const int pml_inside = r.pml;
@@ -932,9 +936,17 @@ int launch_fused_range(FdtdSolver* h, hipStream_t st, const FusedRange& r) {
   }
   if (ty_n == 0) return 0;
   const GridP& g = h->g;
+  const int R = h->rows_f;
+  // the word of the launch (fdtd_fused.hpp): material form, launch bound (the register budget follows the workgroup size), CPML form, hint
+  const int matf = h->mat4 ? (h->mat4b ? 2 : 1) : 0;
+  const FusedWord w = fused_word(matf, 64 * (R + 1), h->fused_lb, pml_inside, h->mem_hints);
+  const auto no_sweep = [&] {
+    return fail(h, "launch_fused_range: no instantiation of the sweep for the word (material form %d, launch bound %d, CPML form %d, hint %d), %d threads",
+                w.matf, w.lb, w.pml, w.hint, 64 * (R + 1));
+  };
+  if (!fused_instantiated(w)) return no_sweep();       // (in front of everything that changes the handle's state)
   if (ensure_second_set(h)) return -1;
   if (pml_inside && ensure_pml_blocks(h, pml_inside)) return -1;
-  const int R = h->rows_f;
   // z-chunk: 16 planes per workgroup when CPML runs inside the sweep, 8 when not — measured inside engines: 8 is
   // 0 ... 1.5 % faster on the 512^3 plain / materials sweeps and 2 % slower on the CPML-carrying step (profiles/
   // r03f), 2.5 ... 4.5 % faster on the 64- and 128-plane slabs a rank of an 8- / 4-GPU run holds (r03n).  A shape set
@@ -954,7 +966,6 @@ int launch_fused_range(FdtdSolver* h, hipStream_t st, const FusedRange& r) {
     const int want = h->edge_zchunk > 0 ? h->edge_zchunk : (int)std::max(2LL, std::min((long long)zc, wg_planes / 1024));
     zc = std::min(zc, want);
   }
-  dim3 block(64, R + 1, 1);
   const int nby_all = (g.ny + R - 1) / R;
   if (ty_n < 0) { ty_n = nby_all; ty_a = nby_all; ty_gap = 0; }
   const int nbx = (g.nx + 255) / 256, nby = ty_n, nbz1 = (kend - kbeg + zc - 1) / zc;
@@ -968,65 +979,15 @@ int launch_fused_range(FdtdSolver* h, hipStream_t st, const FusedRange& r) {
   // 8.6 GB per 512^3 sweep in the plain order) but has the eight XCDs stream eight distant regions of every array.
   // Runs of 6 ... 32 tiles are within 0.5 % of each other.
   const int remap = h->xcd_remap < 0 ? kTileRun : h->xcd_remap;
-  dim3 grid(remap ? ((total + 7) / 8) * 8 : total, 1, 1);
-  const size_t shmem = ((size_t)2 * 2 * (R + 1) * 64 + (pml_inside ? 6 * 64 : 0)) * sizeof(float4) + (size_t)h->lds_pad;   // both CPML instantiations stage the x coefficients
   const int pmc = h->cfg.bc[4] == FDTD_BC_PMC;
-  MatP m = mat_params(h);
-  StepP s = step_params(h);
-  // register budget follows the workgroup size: __launch_bounds__ of 256 / 512 / 1024 threads
-  const int threads = 64 * (R + 1);
-  int lb = h->fused_lb ? h->fused_lb : (threads <= 256 ? 256 : (threads <= 512 ? 512 : 1024));
-  if (lb < threads) lb = threads <= 512 ? 512 : 1024;
   time_begin(h, sh ? 3 : 2, st);
   const PmlP* pm = pml_inside ? ((sh && sh->pm) ? sh->pm : h->pml_blk[pml_inside][sh ? sh->parity : h->pml_parity][h->pml_e_parity]) : nullptr;
-  const FieldP fa = sh ? sh->src : h->f, fb = sh ? sh->dst : h->f2;
-  const int ex_j0 = sh ? sh->ex_j0 : 0, ex_j1 = sh ? sh->ex_j1 : 0;
-  // MATV: 0 = uniform medium, 1 = packed words + LDS table, 2 = the wide table (WIDE: the same (LB, PML, HINT) forms)
-#define FDTD_LAUNCH_FUSED_ARGS grid, block, shmem, st, g, fa, fb, s, m, kbeg, \
-                     kend, zc, pmc, nbx, nby, nbz, remap, pm, nbz1, k2beg, k2end, ty_a, ty_gap, ex_j0, ex_j1
-#define FDTD_LAUNCH_FUSED_H(MATV, LBV, PMLV, HV)                                                       \
-  do {                                                                                                \
-    if (MATV == 2) hipLaunchKernelGGL((fused_step_kernel<true, LBV, PMLV, HV, true>), FDTD_LAUNCH_FUSED_ARGS); \
-    else hipLaunchKernelGGL((fused_step_kernel<(MATV != 0), LBV, PMLV, HV>), FDTD_LAUNCH_FUSED_ARGS);   \
-  } while (0)
-  // Non-temporal field stores (FDTD_OPT_MEM_HINTS) in the instantiations WITHOUT CPML only: measured inside one engine
-  // (profiles/r02z_probe_same_engine_cache_hints.jsonl) they take 2.1 % off the plain sweep and 3.1 % off the one with
-  // materials, and ADD 13 % to the CPML-carrying ones (2-3 waves per SIMD: the slower store completion is not hidden).
-  // With them goes the order of the stores: H ahead of the row exchange instead of behind the E update (-0.5 % there,
-  // +12 % in the CPML-carrying instantiations; raising the wave priority while a plane's loads go out: +0.6 %;
-  // profiles/r03k_probe_early_h_stores_setprio.jsonl).
-  // The CPML-carrying instantiations store their H-side psi behind the E update instead of in the H phase in front of
-  // the row exchange: -2.7 ... -3.3 % of the whole CPML step (profiles/r04j_probe_late_psi_h_stores_all.jsonl).
-  // Non-temporal field stores on top of that: +13 % again (r04k).
-  // Without CPML (256-thread instantiations) the E values of a plane are stored one H phase later, behind the loads of
-  // the next plane (12 more live registers): -0.3 ... -0.9 % (r04l); the same in the CPML instantiations: +10 % (r04m).
-#define FDTD_LAUNCH_FUSED(MATV, LBV, PMLV)                                                            \
-  do {                                                                                                \
-    if (PMLV == 0 && LBV == 256 && h->mem_hints) FDTD_LAUNCH_FUSED_H(MATV, 256, 0, 265);              \
-    else if (PMLV == 0 && h->mem_hints) FDTD_LAUNCH_FUSED_H(MATV, LBV, 0, 9);                         \
-    else if (PMLV != 0 && h->mem_hints) FDTD_LAUNCH_FUSED_H(MATV, LBV, PMLV, 128);                    \
-    else FDTD_LAUNCH_FUSED_H(MATV, LBV, PMLV, 0);                                                     \
-  } while (0)
-  const bool wide = h->mat4 && h->mat4b;
-  if (pml_inside == 1) {        // x recursions only: every tile of a grid with x layers
-    if (wide) { if (lb == 256) FDTD_LAUNCH_FUSED(2, 256, 1); else FDTD_LAUNCH_FUSED(2, 512, 1); }
-    else if (h->mat4) { if (lb == 256) FDTD_LAUNCH_FUSED(1, 256, 1); else FDTD_LAUNCH_FUSED(1, 512, 1); }
-    else { if (lb == 256) FDTD_LAUNCH_FUSED(0, 256, 1); else FDTD_LAUNCH_FUSED(0, 512, 1); }
-  } else if (pml_inside) {      // all axes (axes outside `pml_inside` have no members in the block)
-    if (wide) { if (lb == 256) FDTD_LAUNCH_FUSED(2, 256, 7); else FDTD_LAUNCH_FUSED(2, 512, 7); }
-    else if (h->mat4) { if (lb == 256) FDTD_LAUNCH_FUSED(1, 256, 7); else FDTD_LAUNCH_FUSED(1, 512, 7); }
-    else { if (lb == 256) FDTD_LAUNCH_FUSED(0, 256, 7); else FDTD_LAUNCH_FUSED(0, 512, 7); }
-  } else if (wide) {
-    if (lb == 256) FDTD_LAUNCH_FUSED(2, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(2, 512, 0); else FDTD_LAUNCH_FUSED(2, 1024, 0);
-  } else if (h->mat4) {
-    if (lb == 256) FDTD_LAUNCH_FUSED(1, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(1, 512, 0); else FDTD_LAUNCH_FUSED(1, 1024, 0);
-  } else {
-    if (lb == 256) FDTD_LAUNCH_FUSED(0, 256, 0); else if (lb == 512) FDTD_LAUNCH_FUSED(0, 512, 0); else FDTD_LAUNCH_FUSED(0, 1024, 0);
-  }
-#undef FDTD_LAUNCH_FUSED
-#undef FDTD_LAUNCH_FUSED_H
-#undef FDTD_LAUNCH_FUSED_ARGS
+  const bool launched = launch_fused_step(FusedLaunch{
+      st, remap ? ((total + 7) / 8) * 8 : total, R + 1, matf, h->fused_lb, pml_inside, h->mem_hints, (size_t)h->lds_pad,
+      g, sh ? sh->src : h->f, sh ? sh->dst : h->f2, step_params(h), mat_params(h), kbeg, kend, zc, pmc, nbx, nby, nbz, remap, pm,
+      nbz1, k2beg, k2end, ty_a, ty_gap, sh ? sh->ex_j0 : 0, sh ? sh->ex_j1 : 0});
   time_end(h, st);
+  if (!launched) return no_sweep();       // (the launcher's case labels and fused_instantiated expand the same list)
   return 0;
 }
 
