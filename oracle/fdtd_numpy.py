@@ -416,7 +416,10 @@ class OracleFdtd:
 
     # ------------------------------------------------------------------ TFSF (1-D auxiliary grid)
     def _tfsf_init(self, t):
-        return dict(e=np.zeros(t.n_aux + 1, np.float64), h=np.zeros(t.n_aux, np.float64))
+        """the incident line is state like the fields: an fp32 oracle stores it in fp32, one store — one rounding — per update of h1 and
+        of e1 (the coefficient tables stay float64 and promote the arithmetic between two stores).  The source cell of e1 is stored a
+        second time when the soft source is added, as tfsf_aux_e_kernel stores it twice."""
+        return dict(e=np.zeros(t.n_aux + 1, self.rdtype), h=np.zeros(t.n_aux, self.rdtype))
 
     def _tfsf_h(self, n: int):
         """Advance the incident 1-D H (uses e_inc^n), then correct the 3-D H nodes whose
@@ -434,8 +437,7 @@ class OracleFdtd:
                         ijk = t.h_corr_ijk[m]
                         np.add.at(self.H[c], (ijk[:, 2], ijk[:, 1], ijk[:, 0]),
                                   vals[m].astype(self.dtype))
-            h1 *= t.ah
-            h1 -= t.bh * (e1[1:] - e1[:-1])
+            h1[:] = h1 * t.ah - t.bh * (e1[1:] - e1[:-1])          # (one store, one rounding)
 
     def _tfsf_e(self, n: int):
         for t, st in zip(self.spec.tfsf, self.tfsf_state):

@@ -152,16 +152,16 @@ def _plane_waves(shape, rng, cplx):
     return out
 
 
-def raw_state(spec, seed):
-    """six fp32 (complex64 under Bloch phases) arrays [nz, ny, nx], none of them zero anywhere"""
+def raw_state(spec, seed, amp=AMP):
+    """six fp32 (complex64 under Bloch phases) arrays [nz, ny, nx], none of them zero anywhere; E of amplitude ``amp``, H of amp / eta0"""
     nx, ny, nz = spec.shape
     cplx = spec.bloch is not None
     rng = np.random.default_rng([int(seed), nx, ny, nz])
     out = []
     for c in range(6):
-        f = (AMP if c < 3 else AMP / ETA0) * _plane_waves((nz, ny, nx), rng, cplx)
+        f = (amp if c < 3 else amp / ETA0) * _plane_waves((nz, ny, nx), rng, cplx)
         f = f.astype(np.complex64 if cplx else np.float32)
-        tiny = np.float32(1e-3 * (AMP if c < 3 else AMP / ETA0))
+        tiny = np.float32(1e-3 * (amp if c < 3 else amp / ETA0))
         f[f == 0] = tiny                                    # (a band-limited sum + noise hits 0.0f at no node in practice; make sure)
         out.append(f)
     return out
@@ -182,11 +182,11 @@ def _load(o, state):
         o.H[c][...] = state[3 + c]
 
 
-def admissible_state(spec, seed=1):
+def admissible_state(spec, seed=1, amp=AMP):
     """-> (state, excluded): the dense state with the pinned nodes and everything beyond a PMC-plus wall at zero, and per component
     the boolean mask of the nodes left out of the measure (those same nodes)."""
     from oracle.fdtd_numpy import OracleFdtd
-    state = raw_state(spec, seed)
+    state = raw_state(spec, seed, amp)
     o = OracleFdtd(spec)
     _load(o, state)
     o.step()
@@ -214,36 +214,51 @@ class Run:
     pairs: int = 0
     shell2_pairs: int = 0
     why: int = 0
+    src_paged_pairs: int = 0
 
 
-def run_oracle(spec, state, K, dtype=np.float64, plant=None):
-    """K steps of the oracle from ``state``; ``plant(oracle)`` perturbs the instance's coefficients before the first step"""
+def run_oracle(spec, state, K, dtype=np.float64, plant=None, warmup=0):
+    """K steps of the oracle from ``state``; ``plant(oracle)`` perturbs the instance before the first step.  ``warmup``: that many
+    steps from zero fields first, then the six fields are overwritten with ``state`` (the incident lines, psi and the pole states
+    stay as the warm-up left them).  K may be a tuple of ascending counts: -> {K: Run}, every one what a run of its own gives."""
     from oracle.fdtd_numpy import OracleFdtd
     o = OracleFdtd(spec, dtype=dtype)
     if plant is not None:
         plant(o)
-    _load(o, state)
-    for _ in range(K):
+    for _ in range(warmup):
         o.step()
-    return Run([np.array(f) for f in o.E + o.H], {k: np.array(v) for k, v in o.results().items()})
+    _load(o, state)
+    out, done = {}, 0
+    for k in ((K,) if np.isscalar(K) else K):
+        for _ in range(k - done):
+            o.step()
+        done = k
+        out[k] = Run([np.array(f) for f in o.E + o.H], {n: np.array(v) for n, v in o.results().items()})
+    return out[K] if np.isscalar(K) else out
 
 
-def run_engine(spec, lib, state, K, path, axis_shift=0, twostep=5 + 64 * 3, shell2=1):
+def run_engine(spec, lib, state, K, path, axis_shift=0, twostep=5 + 64 * 3, shell2=1, warmup=0, options=(), **engine_kw):
     """K steps of the library from ``state``: the fused single steps ("fused"), the two-pass kernels ("twopass"), or step pairs
     wherever the run takes them ("pairs": the two-step sweep, shell pairs and the shell2 form forced on as
-    tests/test_emu_shell2.py forces them)."""
+    tests/test_emu_shell2.py forces them).  ``warmup``: a run of that many steps from zero fields in front of ``set_field`` (the
+    counters returned are those of the K steps); ``options``: (key, value) pairs set last; ``engine_kw``: to HipEngine."""
     kw = dict(variant=L.VARIANT_ZMARCH) if path == "twopass" else {}
-    with HipEngine(spec, lib=lib, axis_shift=axis_shift, **kw) as e:
+    with HipEngine(spec, lib=lib, axis_shift=axis_shift, **kw, **engine_kw) as e:
         if path == "pairs":
             e.set_option(L.OPT_TWOSTEP, twostep)
             e.set_option(L.OPT_SHELL_PAIRS, 1)
             e.set_option(L.OPT_SHELL2, shell2)
         else:
             e.set_option(L.OPT_TWOSTEP, 0)
+        for key, value in options:
+            e.set_option(key, value)
+        if warmup:
+            e.run(warmup)
         for c in range(6):
             e.set_field(c, state[c])
         st = e.run(K)
-        return Run([e.get_field(c) for c in range(6)], e.results(), int(st.fused2_pairs), int(st.shell2_pairs), int(st.fused2_off_reason))
+        return Run([e.get_field(c) for c in range(6)], e.results(), int(st.fused2_pairs), int(st.shell2_pairs), int(st.fused2_off_reason),
+                   int(st.src_paged_pairs))
 
 
 # ---------------------------------------------------------------------------------------------------------------- measure
@@ -299,7 +314,27 @@ def where(spec, c, kji):
         m = int(spec.mat_idx[c % 3][idx[2], idx[1], idx[0]])
         nb = spec.mat_idx[c % 3][max(idx[2] - 1, 0):idx[2] + 2, max(idx[1] - 1, 0):idx[1] + 2, max(idx[0] - 1, 0):idx[0] + 2]
         parts.append(f"medium {m} ({getattr(spec.media[m], 'name', '')})" + (", on a body surface" if (nb != m).any() else ""))
+    parts += listed(spec, c, idx)
     return "; ".join(parts)
+
+
+def listed(spec, c, ijk):
+    """the source lists that hold node ``ijk`` = (i, j, k) of component c, one clause per list and side: TFSF box or point list, E or
+    H side, the entries of that node (index in the list as the spec holds it) of how many, and for a box the aux indices they read"""
+    out = []
+    side = "EH"[c // 3]
+    for n, t in enumerate(spec.tfsf):
+        comp, nodes, aux = (t.e_corr_comp, t.e_corr_ijk, t.e_corr_aux) if c < 3 else (t.h_corr_comp, t.h_corr_ijk, t.h_corr_aux)
+        hit = np.nonzero((comp == c) & (nodes == np.asarray(ijk)).all(axis=1))[0] if len(comp) else ()
+        if len(hit):
+            out.append(f"listed: TFSF box {n}, {side} side, entr{'y' if len(hit) == 1 else 'ies'} {', '.join(str(int(q)) for q in hit)} of {len(comp)} "
+                       f"({len(hit)} on this node), reading aux {', '.join(str(int(aux[q])) for q in hit)} of the {'h' if c < 3 else 'e'} line")
+    for n, s in enumerate(spec.sources):
+        hit = np.nonzero((s.comp == c) & (s.ijk == np.asarray(ijk)).all(axis=1))[0] if len(s.comp) else ()
+        if len(hit):
+            out.append(f"listed: point list {n}{' (' + s.name + ')' if s.name else ''}, {side} side, entr{'y' if len(hit) == 1 else 'ies'} "
+                       f"{', '.join(str(int(q)) for q in hit)} of {len(s.comp)} ({len(hit)} on this node)")
+    return out
 
 
 @dataclasses.dataclass
@@ -376,6 +411,7 @@ def rel_l2(ref, got):
 
 class Case:
     """A spec with its state, its fp64 references and its fp32 floors per K, computed once and shared by the tests that need them."""
+    tag, note, warmup = "dense", "", 0          # (tests/source_state.py: a warm-up in front of the state)
 
     def __init__(self, label, spec, seed=1):
         self.label, self.spec = label, spec
@@ -385,13 +421,13 @@ class Case:
 
     def ref(self, K):
         if K not in self._ref:
-            self._ref[K] = run_oracle(self.spec, self.state, K)
+            self._ref[K] = run_oracle(self.spec, self.state, K, warmup=self.warmup)
         return self._ref[K]
 
     def floor(self, K):
         """(fields, records): the fp32 oracle against the fp64 oracle"""
         if K not in self._floor:
-            f, r = measure(self.spec, self.state, self.excluded, self.ref(K), run_oracle(self.spec, self.state, K, dtype=np.float32))
+            f, r = measure(self.spec, self.state, self.excluded, self.ref(K), run_oracle(self.spec, self.state, K, dtype=np.float32, warmup=self.warmup))
             self._floor[K] = (f, r)
         return self._floor[K]
 
@@ -400,16 +436,21 @@ class Case:
         f, r = self.floor(K)
         return MARGIN * max(f.value, r.value)
 
+    def bars(self, K):
+        """(the bar of the nodes, the bar of the record elements): here one number for both"""
+        return self.bar(K), self.bar(K)
+
     def check(self, got, K, what):
         """assert every node and every record element of ``got`` under the bar; -> (fields, records) figures"""
         f, r = measure(self.spec, self.state, self.excluded, self.ref(K), got)
-        bar = self.bar(K)
+        nbar, rbar = self.bars(K)
         ff, fr = self.floor(K)
-        print(f"[dense] {self.label} K={K} {what}: nodes {f.value:.3e} records {r.value:.3e} | floor {ff.value:.3e} / {fr.value:.3e} "
-              f"bar {bar:.3e} | ratio to floor {max(f.value, r.value) / max(ff.value, fr.value, 1e-300):.2f} | excluded {100 * self.share:.2f} %"
-              f" | pairs {got.pairs} (shell2 {got.shell2_pairs}, off-reason {got.why})")
-        assert f.value <= bar, f"{self.label} K={K} {what}: node over the bar {bar:.3e} (floor {ff.value:.3e}): {f}"
-        assert r.value <= bar, f"{self.label} K={K} {what}: record over the bar {bar:.3e} (floor {fr.value:.3e}): {r}"
+        ratio = max(f.value / max(nbar / MARGIN, 1e-300), r.value / max(rbar / MARGIN, 1e-300))
+        print(f"[{self.tag}] {self.label} K={K} {what}: nodes {f.value:.3e} records {r.value:.3e} | floor {ff.value:.3e} / {fr.value:.3e} "
+              f"bar {nbar:.3e}{'' if rbar == nbar else f' / {rbar:.3e}'} | ratio to floor {ratio:.2f} | excluded {100 * self.share:.2f} %"
+              f" | pairs {got.pairs} (shell2 {got.shell2_pairs}, off-reason {got.why}){self.note}")
+        assert f.value <= nbar, f"{self.label} K={K} {what}: node over the bar {nbar:.3e} (floor {ff.value:.3e}): {f}"
+        assert r.value <= rbar, f"{self.label} K={K} {what}: record over the bar {rbar:.3e} (floor {fr.value:.3e}): {r}"
         return f, r
 
 

@@ -1124,7 +1124,8 @@ bool fused2_eligible(const FdtdSolver* h) { return !any_pml(h) && fused2_why_not
 // point-source lists or none: they must be all alive (then at most kMaxInj nodes — a dipole, a few; not a mode plane or a current
 // sheet —, no H_y / H_z node left of a tile seam, no magnetic node together with absorber layers, and the table of all steps
 // for magnetic nodes) or all spent (then nothing is injected and their number does not matter: a mode source or a TFSF box
-// keeps single steps for the length of its pulse, the rest of the run goes out in pairs).  `*alive`: the lists inject at step n.
+// keeps single steps for the length of its pulse, the rest of the run goes out in pairs).  That is judged at step n; of step n + 1 one
+// thing is asked as well: no list may end at n while another list's H side goes on (below).  `*alive`: the lists inject at step n.
 int fused2_sources_why_not(const FdtdSolver* h, long long n, bool* alive = nullptr) {
   bool any_alive = false, any_spent = false;
   for (const PointSrc& s : h->psrc)
@@ -1133,6 +1134,12 @@ int fused2_sources_why_not(const FdtdSolver* h, long long n, bool* alive = nullp
   for (const Tfsf& t : h->tfsf) if (n < t.n_steps) return FDTD_F2_OFF_TFSF;
   if (any_alive && any_spent) return FDTD_F2_OFF_SOURCES;
   if (!any_alive) return 0;
+  // the pair (n, n + 1): the sweep takes the H-side terms of step n + 1 from the table row of ALL lists (InjP::val2) or from none.  A
+  // list whose last step is n while an H side goes on at n + 1 would leave that H side without its term: single steps there
+  bool ends = false, h_goes_on = false;
+  for (const PointSrc& s : h->psrc)
+    if (s.has_nodes()) { ends = ends || (s.alive(n) && !s.alive(n + 1)); h_goes_on = h_goes_on || (s.h.n > 0 && s.alive(n + 1)); }
+  if (ends && h_goes_on) return FDTD_F2_OFF_SOURCES;
   if (h->src_nodes > kMaxInj) return FDTD_F2_OFF_SOURCES;
   if (h->src_h_nodes > 0 && !h->src_tab) return FDTD_F2_OFF_SOURCES;      // H-side nodes take their terms of step n+1 from the table only
   if (h->has_damp && h->src_h_nodes > 0) return FDTD_F2_OFF_H_SOURCE_ABSORBER;  // absorber layers are applied inside the sweep, H-side sources of step n in front of it
