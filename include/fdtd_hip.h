@@ -411,8 +411,8 @@ int fdtd_get_monitor(FdtdSolver* h, int monitor_id, void* host, size_t bytes);
  * out[3] = tables (phase tables; taps, weights, per-tile partial sums) */
 int fdtd_get_monitor_bytes(FdtdSolver* h, int monitor_id, int64_t out[4]);
 
-/* whole-volume field access [nz][ny][nx] (tests, benchmarks, checkpointing); the reference exposes
- * fields only through monitors (ref monitor.py:363), so this has no cloud counterpart */
+/* whole-volume field access [nz][ny][nx] (tests, benchmarks; a checkpoint is fdtd_get_state / fdtd_set_state below: the fields are
+ * not the whole state); the reference exposes fields only through monitors (ref monitor.py:363), so this has no cloud counterpart */
 int fdtd_set_field(FdtdSolver* h, int comp, const float* host, size_t bytes);
 int fdtd_get_field(FdtdSolver* h, int comp, float* host, size_t bytes);
 
@@ -533,6 +533,49 @@ enum { FDTD_OPT_FLAGS = 0 /* Not switched between runs by any test. */, FDTD_OPT
 int fdtd_set_option(FdtdSolver* h, int key, int value);
 int fdtd_get_seam_stats(FdtdSolver* h, FdtdSeamStats* out);
 int fdtd_reset(FdtdSolver* h);      /* zero fields, auxiliaries, monitors and the step counter */
+
+/* Checkpoint and resume: everything of a handle that evolves from step to step, as one host blob, and back into a fresh handle that
+ * was set up the same way (docs/history/CHECKPOINT.md).  The library keeps ONE table of state sections (a device pointer and a byte
+ * count each; fdtd_capi.hip state_sections) that fdtd_reset zeroes, fdtd_get_state copies out and fdtd_set_state copies in:
+ *   saved    the six live field arrays (ghost planes included), the live CPML psi sets of every axis (E side, H side), e_old and q of
+ *            every ADE group, e1 / h1 of every TFSF box, `data` of every monitor and the reduced series / gathered array of a ring
+ *            monitor — in this order;
+ *   scratch  the other two field sets and the other psi sets: the write sides of the ping-pongs, overwritten before they are read.
+ *            Not in the blob; fdtd_set_state zeroes those the handle holds;
+ *   derived  the paged ADE memory terms: cc S(Q), a function of q alone.  Not in the blob: they are written in their UNPAGED form (q),
+ *            and rebuilt from it by the set-up kernel that laid them out — by fdtd_set_state on a handle that has paged, by the first
+ *            fdtd_run on one that has not run yet.
+ * Live buffers: the library swaps the POINTERS of its field and psi sets after every sweep, so the arrays a handle calls current are the
+ * live ones whatever the step's parity; the blob holds them under that name — a canonical buffer, no index stored — and
+ * fdtd_set_state writes them into whatever the receiving handle calls current.
+ * Blob = FdtdStateHeader, uint64 section_bytes[n_sections], uint64 {next, reduced}[n_monitors], then the saved sections back to back.
+ * The fingerprint hashes what fixes the layout and meaning of the sections: the padded grid and field_bytes; per axis the CPML layer
+ * counts and psi entries; comp, n, n_poles of every ADE group; n_aux of every TFSF box; kind, form, data_bytes, result_bytes of every
+ * monitor; the counts of anisotropic / modulation / conformal / nonlinear lists.  It does not change with the steps taken or fdtd_reset.
+ * fdtd_get_state first synchronises the handle's streams, flushes deferred seam columns and drains the monitor rings, as fdtd_run does
+ * on its way out.  fdtd_set_state checks everything before it touches the handle and refuses by name: "bad magic", "format version",
+ * "fingerprint", "section ... bytes", "too small".  Handles with a communicator (z-slab ranks) refuse fingerprint, get and set:
+ * "state save / restore is not available on z-slab handles".  The two handles of an fdtd_run_bloch pair each have their own blob. */
+#define FDTD_STATE_MAGIC "FDTDSTA1"
+#define FDTD_STATE_VERSION 1
+typedef struct FdtdStateHeader {
+  char     magic[8];         /* FDTD_STATE_MAGIC                                             */
+  uint64_t version;          /* FDTD_STATE_VERSION                                           */
+  uint64_t fingerprint;      /* fdtd_state_fingerprint of the handle that wrote it           */
+  int64_t  step;             /* the handle's step counter                                    */
+  uint64_t n_sections;
+  uint64_t n_monitors;
+  double   energy_max;
+  int64_t  steps_done;       /* FdtdStats: the four fields fdtd_reset clears                 */
+  int64_t  diverged;
+  int64_t  stopped_early;
+  double   field_decay;
+  uint64_t total_bytes;      /* of the whole blob = fdtd_state_bytes                         */
+} FdtdStateHeader;
+int     fdtd_state_fingerprint(FdtdSolver* h, uint64_t* out);
+int64_t fdtd_state_bytes(FdtdSolver* h);                               /* < 0: error */
+int     fdtd_get_state(FdtdSolver* h, void* host, size_t bytes);       /* bytes >= fdtd_state_bytes */
+int     fdtd_set_state(FdtdSolver* h, const void* host, size_t bytes);
 
 /* Which instantiations of the two-step sweep ran.  fused2_step_kernel<LB, OPT> exists once per listed (LB, OPT) pair (launch bound in
  * threads: 512 / 768 / 1024; OPT: the feature word of tidy3d_amd/csrc/fdtd_fused2.hpp — 1 non-temporal stores, 2 materials, 4 monitor

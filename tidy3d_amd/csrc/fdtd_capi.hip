@@ -4281,38 +4281,231 @@ int fdtd_comm_init(FdtdSolver* h, const char id[128], int rank, int n_ranks) {
   return 0;
 }
 
+}  // extern "C"
+namespace {
+// ---- the state that evolves from step to step: ONE table (include/fdtd_hip.h, above fdtd_get_state) ---------------------------------
+// fdtd_reset zeroes every section; fdtd_state_bytes, fdtd_get_state and fdtd_set_state walk the Saved ones in this order.
+//   Saved:   what the blob of fdtd_get_state holds.  The field and psi pointers a handle calls current ARE the live ones (swap_sets,
+//            swap_psi_h, swap_psi_e exchange the pointers), so the section is the live array whatever the step's parity.
+//   Scratch: the write sides of the ping-pongs (lazily allocated: a fresh handle may lack them) — every value read from them was
+//            written in the same step or pair.  fdtd_set_state zeroes them.
+//   Derived: disp.cs = cc S(Q) of every dispersive cell, a function of q alone (ade_kernel, ade2_kernel and disp_qoff_kernel form it
+//            with the same operations in the same order).  fdtd_set_state rebuilds it where the handle has paged (state_rebuild_paged).
+enum StateRole { kStateSaved, kStateScratch, kStateDerived };
+struct StateSection { void* p; size_t bytes; StateRole role; };
+std::vector<StateSection> state_sections(FdtdSolver* h) {
+  std::vector<StateSection> v;
+  for (int c = 0; c < 6; ++c) v.push_back({h->fbase[c], h->field_bytes, kStateSaved});
+  for (int c = 0; c < 6; ++c) if (h->fbase2[c]) v.push_back({h->fbase2[c], h->field_bytes, kStateScratch});
+  for (int c = 0; c < 6; ++c) if (h->fbase3[c]) v.push_back({h->fbase3[c], h->field_bytes, kStateScratch});
+  for (int a = 0; a < 3; ++a) {
+    PmlAxisDev& P = h->pml[a];
+    if (P.n == 0) continue;
+    for (int q = 0; q < 2; ++q)
+      for (int s = 0; s < PmlAxisDev::kSets; ++s)
+        if (P.set(s)[q]) v.push_back({P.set(s)[q], P.set_count(s) * 4, s == PmlAxisDev::kE || s == PmlAxisDev::kH ? kStateSaved : kStateScratch});
+  }
+  for (AdeGroup& a : h->ade) {
+    v.push_back({a.e_old, (size_t)a.n * 4, kStateSaved});
+    v.push_back({a.q, (size_t)a.n * a.p.n_poles * 8, kStateSaved});
+  }
+  if (h->disp.state == 1) v.push_back({h->disp.cs, (size_t)h->disp.seg.n_blocks * 3 * 256 * sizeof(float), kStateDerived});
+  for (Tfsf& t : h->tfsf) {
+    v.push_back({t.e1, ((size_t)t.n_aux + 1) * 4, kStateSaved});
+    v.push_back({t.h1, (size_t)t.n_aux * 4, kStateSaved});
+  }
+  for (Monitor& m : h->mons) {
+    v.push_back({m.data, m.data_bytes, kStateSaved});
+    if (has_ring(m)) v.push_back({m.result(), std::max<size_t>(m.result_bytes, sizeof(float)), kStateSaved});
+  }
+  return v;
+}
+std::vector<StateSection> saved_sections(FdtdSolver* h) {
+  std::vector<StateSection> v;
+  for (const StateSection& s : state_sections(h)) if (s.role == kStateSaved) v.push_back(s);
+  return v;
+}
+size_t state_table_bytes(size_t n_sections, size_t n_monitors) { return sizeof(FdtdStateHeader) + 8 * n_sections + 16 * n_monitors; }
+// 64-bit FNV-1a over the words that fix the layout and the meaning of the Saved sections
+uint64_t state_fingerprint(const FdtdSolver* h) {
+  uint64_t x = 1469598103934665603ull;
+  auto mix = [&](uint64_t v) { for (int b = 0; b < 8; ++b) { x ^= (v >> (8 * b)) & 0xff; x *= 1099511628211ull; } };
+  mix((uint64_t)h->g.nx); mix((uint64_t)h->g.ny); mix((uint64_t)h->g.nz); mix(h->field_bytes);
+  for (int a = 0; a < 3; ++a) {
+    const PmlAxisDev& P = h->pml[a];
+    mix((uint64_t)P.n_lo); mix((uint64_t)P.n_hi);
+    mix(P.ns > 0 ? P.set_count(PmlAxisDev::kE) : 0); mix(P.ns > 0 ? P.set_count(PmlAxisDev::kH) : 0);
+  }
+  mix(h->ade.size());
+  for (const AdeGroup& a : h->ade) { mix((uint64_t)a.comp); mix((uint64_t)a.n); mix((uint64_t)a.p.n_poles); }
+  mix(h->tfsf.size());
+  for (const Tfsf& t : h->tfsf) mix((uint64_t)t.n_aux);
+  mix(h->mons.size());
+  for (const Monitor& m : h->mons) { mix((uint64_t)m.kind); mix((uint64_t)m.form); mix(m.data_bytes); mix(m.result_bytes); }
+  for (int kind = 0; kind < kListKinds; ++kind) mix(n_lists(h, kind));
+  return x;
+}
+int refuse_state_on_z_slabs(FdtdSolver* h, const char* who) {
+  return h->comm ? fail(h, "%s: state save / restore is not available on z-slab handles", who) : 0;
+}
+// the paged memory terms of a handle that has paged, from the pole states as they stand: the set-up kernel again (it writes the slots
+// and the bounding box it found the first time).
+// What this RELIES on: disp_qoff_kernel gives cc * S(Q) the bits ade_kernel / ade2_kernel leave in `cs`.  The three write the same
+// expression — S += 2 ((kap.x - 1) q.x - kap.y q.y) over the poles in ascending order from 0.f, then cc * S — but two of them in a loop
+// unrolled over kMaxPoles and one in a run-time loop, so equal bits need each operation rounded on its own in all three: no FMA
+// contraction.  The library is built with -ffp-contract=off (tidy3d_amd/build.py, tests/hipemu/build_emu.py: the flag every bit
+// comparison between its schedules rests on); a build without it would break this, and the lazy paging of a restored handle
+// (disp_setup) with it.  Held by scenario (d) and the live-handle tests of tests/test_emu_checkpoint.py / test_gpu_checkpoint.py
+// (one-, two- and three-pole media).
+int state_rebuild_paged(FdtdSolver* h) {
+  Disp& D = h->disp;
+  if (D.state != 1) return 0;
+  const GridP& g = h->g;
+  const int nbx = (g.nx + 255) / 256;
+  int* box = nullptr;
+  if (box_seed_upload(h, &box)) return -1;
+  for (AdeGroup& a : h->ade)
+    hipLaunchKernelGGL(disp_qoff_kernel, dim3(nblk(a.n)), dim3(256), 0, h->stream, (const uint32_t*)a.cell, a.n, g.nx, g.ny, nbx,
+                       (const int*)D.seg.dev, a.comp, (const float2*)a.q, a.p, a.qoff, D.cs, box);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  release_buf(h, box);
+  return 0;
+}
+int state_sync(FdtdSolver* h) {
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->comm_stream && !h->streams_shared) HIPCHK(h, hipStreamSynchronize(h->comm_stream));
+  if (h->box_stream) HIPCHK(h, hipStreamSynchronize(h->box_stream));
+  return 0;
+}
+}  // namespace
+extern "C" {
+
 int fdtd_reset(FdtdSolver* h) {
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->seam_pending = false;
   h->sweep_words.clear();
-  for (int c = 0; c < 6; ++c) HIPCHK(h, hipMemset(h->fbase[c], 0, h->field_bytes));
-  for (int c = 0; c < 6; ++c) if (h->fbase2[c]) HIPCHK(h, hipMemset(h->fbase2[c], 0, h->field_bytes));
-  for (int c = 0; c < 6; ++c) if (h->fbase3[c]) HIPCHK(h, hipMemset(h->fbase3[c], 0, h->field_bytes));
-  for (int a = 0; a < 3; ++a) {
-    PmlAxisDev& P = h->pml[a];
-    if (P.n == 0) continue;
-    for (int q = 0; q < 2; ++q)
-      for (int s = 0; s < PmlAxisDev::kSets; ++s)
-        if (P.set(s)[q]) HIPCHK(h, hipMemset(P.set(s)[q], 0, P.set_count(s) * 4));
-  }
-  for (AdeGroup& a : h->ade) {
-    HIPCHK(h, hipMemset(a.e_old, 0, (size_t)a.n * 4));
-    HIPCHK(h, hipMemset(a.q, 0, (size_t)a.n * a.p.n_poles * 8));
-  }
-  if (h->disp.state == 1) HIPCHK(h, hipMemset(h->disp.cs, 0, (size_t)h->disp.seg.n_blocks * 3 * 256 * sizeof(float)));
-  for (Tfsf& t : h->tfsf) {
-    HIPCHK(h, hipMemset(t.e1, 0, ((size_t)t.n_aux + 1) * 4));
-    HIPCHK(h, hipMemset(t.h1, 0, (size_t)t.n_aux * 4));
-  }
-  for (Monitor& m : h->mons) {
-    HIPCHK(h, hipMemset(m.data, 0, m.data_bytes));
-    m.next = 0;
-    if (has_ring(m)) { HIPCHK(h, hipMemset(m.result(), 0, std::max<size_t>(m.result_bytes, sizeof(float)))); m.reduced = 0; }
-  }
+  for (const StateSection& s : state_sections(h)) HIPCHK(h, hipMemset(s.p, 0, s.bytes));
+  for (Monitor& m : h->mons) { m.next = 0; m.reduced = 0; }
   h->step = 0; h->energy_max = 0.0;
   h->stats.steps_done = 0; h->stats.diverged = 0; h->stats.stopped_early = 0; h->stats.field_decay = 0.0;      // (what a fresh handle reports until its first decay check)
+  return 0;
+}
+
+int fdtd_state_fingerprint(FdtdSolver* h, uint64_t* out) {
+  if (!h) return -1;
+  if (!out) return fail(h, "fdtd_state_fingerprint: null argument");
+  if (refuse_state_on_z_slabs(h, "fdtd_state_fingerprint")) return -1;
+  *out = state_fingerprint(h);
+  return 0;
+}
+
+int64_t fdtd_state_bytes(FdtdSolver* h) {
+  if (!h) return -1;
+  if (refuse_state_on_z_slabs(h, "fdtd_state_bytes")) return -1;
+  const std::vector<StateSection> sec = saved_sections(h);
+  size_t total = state_table_bytes(sec.size(), h->mons.size());
+  for (const StateSection& s : sec) total += s.bytes;
+  return (int64_t)total;
+}
+
+int fdtd_get_state(FdtdSolver* h, void* host, size_t bytes) {
+  if (!h) return -1;
+  if (refuse_state_on_z_slabs(h, "fdtd_get_state")) return -1;
+  const int64_t need = fdtd_state_bytes(h);
+  if (!host || bytes < (size_t)need) return fail(h, "fdtd_get_state: buffer of %zu bytes is too small (the state holds %lld)", bytes, (long long)need);
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (state_sync(h)) return -1;
+  flush_seams(h, h->stream);          // (what fdtd_run does on its way out: nothing pending, no record waiting in a ring)
+  ring_drain(h, h->stream);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const std::vector<StateSection> sec = saved_sections(h);
+  FdtdStateHeader hd{};
+  std::memcpy(hd.magic, FDTD_STATE_MAGIC, 8);
+  hd.version = FDTD_STATE_VERSION;
+  hd.fingerprint = state_fingerprint(h);
+  hd.step = h->step;
+  hd.n_sections = sec.size();
+  hd.n_monitors = h->mons.size();
+  hd.energy_max = h->energy_max;
+  hd.steps_done = h->stats.steps_done; hd.diverged = h->stats.diverged; hd.stopped_early = h->stats.stopped_early;
+  hd.field_decay = h->stats.field_decay;
+  hd.total_bytes = (uint64_t)need;
+  char* out = static_cast<char*>(host);
+  std::memcpy(out, &hd, sizeof(hd));
+  out += sizeof(hd);
+  for (const StateSection& s : sec) { const uint64_t b = s.bytes; std::memcpy(out, &b, 8); out += 8; }
+  for (const Monitor& m : h->mons) { const uint64_t v[2] = {m.next, m.reduced}; std::memcpy(out, v, 16); out += 16; }
+  for (const StateSection& s : sec) {
+    if (s.bytes) HIPCHK(h, hipMemcpy(out, s.p, s.bytes, hipMemcpyDeviceToHost));
+    out += s.bytes;
+  }
+  return 0;
+}
+
+int fdtd_set_state(FdtdSolver* h, const void* host, size_t bytes) {
+  if (!h) return -1;
+  if (refuse_state_on_z_slabs(h, "fdtd_set_state")) return -1;
+  // every check in front of the first change
+  FdtdStateHeader hd;
+  if (!host || bytes < sizeof(hd)) return fail(h, "fdtd_set_state: buffer of %zu bytes is too small for the header (%zu)", bytes, sizeof(hd));
+  std::memcpy(&hd, host, sizeof(hd));
+  if (std::memcmp(hd.magic, FDTD_STATE_MAGIC, 8) != 0) return fail(h, "fdtd_set_state: bad magic (not a state blob of this library)");
+  if (hd.version != FDTD_STATE_VERSION)
+    return fail(h, "fdtd_set_state: format version %llu, this library reads %d", (unsigned long long)hd.version, FDTD_STATE_VERSION);
+  const uint64_t fp = state_fingerprint(h);
+  if (hd.fingerprint != fp)
+    return fail(h, "fdtd_set_state: fingerprint %016llx is not this handle's (%016llx): the blob was written by a handle set up differently",
+                (unsigned long long)hd.fingerprint, (unsigned long long)fp);
+  const std::vector<StateSection> sec = saved_sections(h);
+  if (hd.n_sections != sec.size() || hd.n_monitors != h->mons.size())
+    return fail(h, "fdtd_set_state: section count %llu / monitor count %llu differ from this handle's %zu / %zu",
+                (unsigned long long)hd.n_sections, (unsigned long long)hd.n_monitors, sec.size(), h->mons.size());
+  const size_t table = state_table_bytes(sec.size(), h->mons.size());
+  if (bytes < table) return fail(h, "fdtd_set_state: buffer of %zu bytes is too small for the section table (%zu)", bytes, table);
+  const char* in = static_cast<const char*>(host) + sizeof(hd);
+  size_t total = table;
+  for (size_t i = 0; i < sec.size(); ++i) {
+    uint64_t b;
+    std::memcpy(&b, in + 8 * i, 8);
+    if (b != sec[i].bytes)
+      return fail(h, "fdtd_set_state: section %zu holds %llu bytes, this handle's %zu", i, (unsigned long long)b, sec[i].bytes);
+    total += sec[i].bytes;
+  }
+  if (bytes < total || hd.total_bytes != total)
+    return fail(h, "fdtd_set_state: buffer of %zu bytes is too small (the state holds %zu; its header says %llu)", bytes, total,
+                (unsigned long long)hd.total_bytes);
+  const char* mon_in = in + 8 * sec.size();
+  for (size_t i = 0; i < h->mons.size(); ++i) {
+    uint64_t v[2];
+    std::memcpy(v, mon_in + 16 * i, 16);
+    if (v[0] > h->mons[i].steps.size() || v[1] > v[0])
+      return fail(h, "fdtd_set_state: monitor %zu at record %llu (reduced %llu) of %zu", i, (unsigned long long)v[0], (unsigned long long)v[1],
+                  h->mons[i].steps.size());
+  }
+  if (hd.step < 0) return fail(h, "fdtd_set_state: step %lld", (long long)hd.step);
+  // from here on the handle changes
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (state_sync(h)) return -1;
+  h->seam_pending = false;            // (the seam columns arrive with the fields)
+  const char* data = static_cast<const char*>(host) + table;
+  for (const StateSection& s : sec) {
+    if (s.bytes) HIPCHK(h, hipMemcpy(s.p, data, s.bytes, hipMemcpyHostToDevice));
+    data += s.bytes;
+  }
+  for (const StateSection& s : state_sections(h))
+    if (s.role == kStateScratch) HIPCHK(h, hipMemset(s.p, 0, s.bytes));
+  HIPCHK(h, hipStreamSynchronize(nullptr));
+  if (state_rebuild_paged(h)) return -1;
+  for (size_t i = 0; i < h->mons.size(); ++i) {
+    uint64_t v[2];
+    std::memcpy(v, mon_in + 16 * i, 16);
+    h->mons[i].next = (size_t)v[0]; h->mons[i].reduced = (size_t)v[1];
+  }
+  h->step = hd.step; h->energy_max = hd.energy_max;
+  h->stats.steps_done = hd.steps_done; h->stats.diverged = (int32_t)hd.diverged; h->stats.stopped_early = (int32_t)hd.stopped_early;
+  h->stats.field_decay = hd.field_decay;
   return 0;
 }
 

@@ -8,6 +8,8 @@ happens inside ``fdtd_run`` on the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import json
+import os
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -17,6 +19,10 @@ from .constants import EPSILON_0
 from .coeffs import damping_tables, h_coeff, inv_steps, material_table, pml_axis
 from .exceptions import SetupError, SolverLibraryError, Tidy3dNotImplementedError
 from .spec import BC_PEC, BC_PERIODIC, LIST_KINDS, SPARSE_KINDS, MonitorSpec, SolverSpec, refuse_together  # noqa: F401 (LIST_KINDS, refuse_together: also for web.py)
+
+
+# state files (HipEngine.save_state): one line of JSON, then the raw blobs of fdtd_get_state
+STATE_FILE_MAGIC, STATE_FILE_VERSION = "tidy3d_amd-state", 1
 
 
 def _f32(a) -> np.ndarray:
@@ -916,6 +922,111 @@ class HipEngine:
         self._chk(self.lib.dll.fdtd_reset(self.handle), "fdtd_reset")
         if self.twin is not None:
             self.twin.reset()
+
+    # ------------------------------------------------------------------ checkpoint / resume (docs/history/CHECKPOINT.md)
+    def state_fingerprint(self) -> int:
+        """64-bit hash of what fixes the layout of this handle's state blob (``fdtd_state_fingerprint``); the same before and after
+        any number of steps."""
+        out = C.c_uint64()
+        self._chk(self.lib.dll.fdtd_state_fingerprint(self.handle, C.byref(out)), "fdtd_state_fingerprint")
+        return int(out.value)
+
+    def get_state(self) -> np.ndarray:
+        """Everything of this handle that evolves from step to step, as one uint8 array (``fdtd_get_state``; a Bloch twin has its own)."""
+        n = int(self.lib.dll.fdtd_state_bytes(self.handle))
+        self._chk(min(n, 0), "fdtd_state_bytes")
+        blob = np.empty(n, dtype=np.uint8)
+        self._chk(self.lib.dll.fdtd_get_state(self.handle, _ptr(blob), blob.nbytes), "fdtd_get_state")
+        return blob
+
+    def set_state(self, blob):
+        """Put a blob of ``get_state`` back — into this handle or a fresh one of the same spec (``fdtd_set_state``); a refusal leaves
+        the handle as it was."""
+        a = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8))
+        self._chk(self.lib.dll.fdtd_set_state(self.handle, _ptr(a), a.nbytes), "fdtd_set_state")
+
+    def save_state(self, path: str, meta: dict, extra: Optional[dict] = None) -> int:
+        """Write the state of this engine (and of its Bloch twin) to ``path``: one line of JSON — magic, format version, ``meta``,
+        ``axis_shift``, the byte counts and fingerprints of the blobs, ``extra`` (the caller's own notes, not compared) — then the raw
+        blobs.  Atomic: ``path + ".tmp"``, flush, fsync, replace.  Returns the step saved."""
+        engines = [self] + ([self.twin] if self.twin is not None else [])
+        blobs = [e.get_state() for e in engines]
+        step = int(L.FdtdStateHeader.from_buffer_copy(blobs[0][:C.sizeof(L.FdtdStateHeader)].tobytes()).step)
+        head = {"magic": STATE_FILE_MAGIC, "version": STATE_FILE_VERSION, "meta": meta, "axis_shift": int(self.axis_shift), "step": step,
+                "blobs": [{"bytes": int(b.nbytes), "fingerprint": "%016x" % e.state_fingerprint()} for e, b in zip(engines, blobs)],
+                "extra": extra or {}}
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(json.dumps(head, sort_keys=True).encode("utf-8") + b"\n")
+            for b in blobs:
+                f.write(memoryview(b))
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+        return step
+
+    @staticmethod
+    def read_state_header(path: str) -> dict:
+        """The JSON header of a state file (``SetupError`` if it is none)."""
+        with open(path, "rb") as f:
+            line = f.readline(1 << 26)
+        try:
+            head = json.loads(line.decode("utf-8"))
+            ok = isinstance(head, dict) and head.get("magic") == STATE_FILE_MAGIC
+        except (ValueError, UnicodeDecodeError):
+            ok = False
+        if not ok:
+            raise SetupError(f"'{path}' is not a state file of this package (bad magic)")
+        if head.get("version") != STATE_FILE_VERSION:
+            raise SetupError(f"state file '{path}': format version {head.get('version')!r}, this package reads {STATE_FILE_VERSION}")
+        head["_offset"] = len(line)
+        return head
+
+    def load_state(self, path: str, meta: dict) -> dict:
+        """Restore this engine (and its Bloch twin) from ``path``.  ``SetupError`` names what differs — a key of ``meta``, ``axis_shift``,
+        a fingerprint — or that the file is truncated; nothing reaches the device before every check of the file has passed.  With a
+        Bloch twin the two blobs go in one after the other: should the library fail on the second (its own checks passed above, so
+        only a device error can do that), both handles are reset to step 0 — the pair is never left half restored.  Returns the header."""
+        head = self.read_state_header(path)
+        saved = head.get("meta", {})
+        for key in sorted(set(saved) | set(meta)):
+            if saved.get(key) != meta.get(key):
+                raise SetupError(f"state file '{path}' was written for another run: meta '{key}' differs "
+                                 f"({saved.get(key)!r} in the file, {meta.get(key)!r} now)")
+        if int(head.get("axis_shift", -1)) != int(self.axis_shift):
+            raise SetupError(f"state file '{path}': axis_shift {head.get('axis_shift')} in the file, {self.axis_shift} now")
+        engines = [self] + ([self.twin] if self.twin is not None else [])
+        entries = head.get("blobs", [])
+        if len(entries) != len(engines):
+            raise SetupError(f"state file '{path}' holds {len(entries)} blobs, this run has {len(engines)} handles")
+        for e, ent in zip(engines, entries):
+            fp = "%016x" % e.state_fingerprint()
+            if ent["fingerprint"] != fp:
+                raise SetupError(f"state file '{path}': fingerprint {ent['fingerprint']} in the file, {fp} now "
+                                 "(grid, CPML, dispersive media, TFSF boxes or monitors differ)")
+        want = head["_offset"] + sum(int(ent["bytes"]) for ent in entries)
+        have = os.path.getsize(path)
+        if have != want:
+            raise SetupError(f"state file '{path}' is truncated or damaged: {have} bytes, its header says {want}")
+        blobs = []
+        with open(path, "rb") as f:
+            f.seek(head["_offset"])
+            for ent in entries:
+                b = np.fromfile(f, dtype=np.uint8, count=int(ent["bytes"]))
+                if b.nbytes != int(ent["bytes"]):
+                    raise SetupError(f"state file '{path}' is truncated: a blob of {ent['bytes']} bytes ends after {b.nbytes}")
+                blobs.append(b)
+        for q, (e, b) in enumerate(zip(engines, blobs)):
+            try:
+                e.set_state(b)
+            except SolverLibraryError as err:
+                if q > 0:           # (a Bloch pair whose first handle took its blob: never leave the two at different steps)
+                    try:
+                        self.reset()
+                    except SolverLibraryError:
+                        pass
+                raise SetupError(f"state file '{path}': {err}" + (" (both handles of the pair were reset to step 0)" if q > 0 else "")) from err
+        return head
 
     def _dev_comp(self, comp: int) -> int:
         """Component id on the device (axes cyclically renamed by ``axis_shift``)."""

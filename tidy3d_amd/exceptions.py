@@ -37,6 +37,15 @@ except Exception:  # tidy3d (or one of its dependencies) is not importable here
         """A functionality is not (yet) supported (ref exceptions.py:51)."""
 
 
+class RunSuspended(Tidy3dError):
+    """``web.run(..., checkpoint=path)`` used up its ``step_budget`` / ``time_budget`` before the last time step: the whole device
+    state is in the file ``path`` (at time step ``step`` of ``n_steps``), and the same call again continues from there."""
+
+    def __init__(self, path: str, step: int, n_steps: int):
+        super().__init__(f"run suspended at time step {step} of {n_steps}; state saved to '{path}' — the same call resumes it")
+        self.path, self.step, self.n_steps = path, int(step), int(n_steps)
+
+
 class SolverLibraryError(RuntimeError):
     """The HIP solver library is missing, failed to load, or returned an error.
 

@@ -44,6 +44,7 @@ SYMBOLS = (
     "fdtd_add_pec_conformal", "fdtd_add_nonlinear",
     "fdtd_near_field", "fdtd_near_field_chunks",
     "fdtd_set_lattice_flux_weights", "fdtd_lattice_flux", "fdtd_rasterize",
+    "fdtd_state_fingerprint", "fdtd_state_bytes", "fdtd_get_state", "fdtd_set_state",
 )
 
 BC_PEC, BC_PMC, BC_PERIODIC, BC_NEIGHBOR = 0, 1, 2, 3
@@ -90,6 +91,21 @@ class FdtdSeamStats(C.Structure):
     _fields_ = [("seam_deferred_pairs", C.c_int64), ("seam_flushes", C.c_int64), ("seam_pending", C.c_int32),
                 ("reserved", C.c_int32), ("seam_flush_ms", C.c_double)]
 
+
+class FdtdStateHeader(C.Structure):
+    """The fixed head of a state blob (``fdtd_get_state``); ``section_bytes[n_sections]`` and ``{next, reduced}[n_monitors]`` follow."""
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint64), ("fingerprint", C.c_uint64), ("step", C.c_int64),
+                ("n_sections", C.c_uint64), ("n_monitors", C.c_uint64), ("energy_max", C.c_double),
+                ("steps_done", C.c_int64), ("diverged", C.c_int64), ("stopped_early", C.c_int64),
+                ("field_decay", C.c_double), ("total_bytes", C.c_uint64)]
+
+
+STATE_MAGIC, STATE_VERSION = b"FDTDSTA1", 1
+# What a state file is tied to on the library's side.  An explicit constant, bumped ON PURPOSE by whoever changes something that makes
+# an older file resume to other bits or another meaning: the arithmetic or the order of operations of a kernel, what a section of the
+# blob means, how the host lays out lists or monitors.  Adding a symbol, an option or a FdtdStats field does not bump it (the blob's own
+# format has STATE_VERSION, which fdtd_set_state checks).  History: 1 = the first state files.
+ABI_VERSION = 1
 
 RASTER_BOX, RASTER_SPHERE, RASTER_CYLINDER = 0, 1, 2
 
@@ -176,6 +192,11 @@ class FdtdLib:
         d.fdtd_near_field.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, f64, f64, f64, C.c_int, vp, vp, vp, vp]
         d.fdtd_near_field_chunks.argtypes = [C.c_int, C.c_int, C.c_int]
         d.fdtd_rasterize.argtypes = [C.POINTER(FdtdRasterJob), vp]
+        d.fdtd_state_fingerprint.argtypes = [vp, C.POINTER(C.c_uint64)]
+        d.fdtd_state_bytes.argtypes = [vp]
+        d.fdtd_state_bytes.restype = C.c_int64
+        d.fdtd_get_state.argtypes = [vp, vp, C.c_size_t]
+        d.fdtd_set_state.argtypes = [vp, vp, C.c_size_t]
 
     def rasterize(self, shape, coords, records, device: int = 0):
         """``fdtd_rasterize``: the records (``FdtdRasterRecord``, in the order of the structures) painted over a background of 1 on the

@@ -87,6 +87,159 @@ def _log_line(step: int, n_steps: int, t: float, decay: float) -> str:
     return f"- Time step {step:6d} / time {t:.2e}s ({perc:3d} % done), field decay: {mant}"
 
 
+CHECKPOINT_TIME_CHUNK = 1000       # time_budget without checkpoint_steps: the clock is read every that many time steps
+
+
+def _hash_value(h, v, where="simulation") -> None:
+    """Feed ``v`` — anything the mirror simulation's ``dict()`` can hold — into the hash ``h`` in a canonical form: mappings by sorted
+    key, sequences in order, numbers by their exact value, arrays and datasets (anything with ``values`` and ``coords``: custom media,
+    custom sources, modulation amplitudes) by dtype, shape and BYTES of the values and of every coordinate.  Nothing is ever hashed
+    by its ``repr``: an object this walk does not know is refused (``Tidy3dNotImplementedError``), since a state file must not be
+    accepted for a simulation that differs in something the hash did not see."""
+    import dataclasses
+
+    def tag(t, payload=b""):
+        h.update(t.encode("ascii") + b":" + str(len(payload)).encode("ascii") + b":")
+        h.update(payload)
+
+    if v is None or isinstance(v, (bool, np.bool_)):
+        tag("c", repr(None if v is None else bool(v)).encode("ascii"))
+    elif isinstance(v, (int, np.integer)):
+        tag("i", str(int(v)).encode("ascii"))
+    elif isinstance(v, (float, np.floating)):
+        tag("f", float(v).hex().encode("ascii"))
+    elif isinstance(v, (complex, np.complexfloating)):
+        tag("z", (float(v.real).hex() + "," + float(v.imag).hex()).encode("ascii"))
+    elif isinstance(v, str):
+        tag("s", v.encode("utf-8"))
+    elif isinstance(v, bytes):
+        tag("b", v)
+    elif isinstance(v, dict):
+        tag("d", str(len(v)).encode("ascii"))
+        for k in sorted(v, key=str):
+            tag("k", str(k).encode("utf-8"))
+            _hash_value(h, v[k], f"{where}.{k}")
+    elif isinstance(v, (list, tuple)):
+        tag("l", str(len(v)).encode("ascii"))
+        for q, x in enumerate(v):
+            _hash_value(h, x, f"{where}[{q}]")
+    elif isinstance(v, np.ndarray):
+        if v.dtype.kind not in "biufc":
+            raise Tidy3dNotImplementedError(f"checkpoint=: cannot tie a state file to {where}, an array of dtype {v.dtype}")
+        a = np.ascontiguousarray(v)
+        tag("a", (a.dtype.str + str(a.shape)).encode("ascii"))
+        tag("v", a.tobytes())
+    elif hasattr(v, "values") and hasattr(v, "coords") and not callable(getattr(v, "values")):       # a dataset array, ours or xarray's
+        tag("D", str(getattr(v, "tag", type(v).__name__)).encode("utf-8"))
+        _hash_value(h, [str(d) for d in getattr(v, "dims", ())], where + ".dims")
+        coords = v.coords
+        for d in sorted(coords, key=str):
+            tag("k", str(d).encode("utf-8"))
+            _hash_value(h, np.asarray(getattr(coords[d], "values", coords[d])), f"{where}.coords[{d}]")
+        _hash_value(h, np.asarray(v.values), where + ".values")
+    elif hasattr(v, "dict") and callable(v.dict):
+        tag("m", type(v).__name__.encode("utf-8"))
+        _hash_value(h, v.dict(), where)
+    elif hasattr(v, "raw") and type(v).__name__ == "Unsupported":
+        tag("u")
+        _hash_value(h, v.raw, where)
+    elif dataclasses.is_dataclass(v) and not isinstance(v, type):
+        tag("o", type(v).__name__.encode("utf-8"))
+        _hash_value(h, {f.name: getattr(v, f.name) for f in dataclasses.fields(v)}, where)
+    else:
+        raise Tidy3dNotImplementedError(f"checkpoint=: cannot tie a state file to {where}, an object of type "
+                                        f"{type(v).__name__} (its contents would not be part of the file's simulation hash)")
+
+
+def _checkpoint_meta(sim, spec, mode_grid_dispersion, lib) -> dict:
+    """What a state file is tied to besides the handle's own fingerprint: the simulation (a hash of its ``dict()`` in the canonical
+    form of ``_hash_value``: dataset values and coordinates byte for byte), the run length, the device-path choices as RESOLVED —
+    the kind every monitor of ``spec`` came out as under the ``*_device`` keywords and thresholds (two calls whose keywords differ
+    but resolve alike share a file) — the mode-source choice and the state-file ABI."""
+    import hashlib
+    from . import lib as L
+    from .discretize import MODE_SOURCE_GRID_DISPERSION
+    h = hashlib.sha256()
+    _hash_value(h, sim.dict())
+    return {"simulation": h.hexdigest(), "n_steps": int(spec.n_steps),
+            "device_paths": [[m.name, m.kind] for m in spec.monitors],
+            "mode_grid_dispersion": bool(MODE_SOURCE_GRID_DISPERSION if mode_grid_dispersion is None else mode_grid_dispersion),
+            "abi": L.ABI_VERSION, "library": os.path.basename(lib.path)}
+
+
+_PAIR_COUNTERS = ("fused2_pairs", "shell_pairs", "shell2_pairs", "disp_pairs", "src_paged_pairs")
+
+
+def _run_in_chunks(eng, spec, progress, lines, verbose, path, meta, checkpoint_steps, step_budget, time_budget):
+    """The solve of ``run(..., checkpoint=path)``: a sequence of ``eng.run(chunk)`` calls from the step a matching state file holds
+    (or 0) to the last step, the state written at every multiple of ``checkpoint_steps`` and when a budget ends the call
+    (``RunSuspended``).  The library checks the field decay on the handle's GLOBAL step count (``step % decay_every``,
+    csrc/fdtd_run.hpp ``Run::decay_at``), so a chunk boundary may fall on any step: a chunked run meets the same checks at the same
+    steps as a whole one, and ``checkpoint_steps`` is used as given.  -> (stats of the whole run, solve seconds of all calls)."""
+    from .exceptions import RunSuspended
+    n_steps = int(spec.n_steps)
+    every = None if checkpoint_steps is None else int(checkpoint_steps)
+    step, solve_before, sums = 0, 0.0, dict.fromkeys(_PAIR_COUNTERS, 0)
+    in_file = None                                        # the step the file at `path` holds, where this call knows it
+
+    def say(ln):
+        lines.append(ln)
+        if verbose:
+            print(ln, flush=True)
+
+    if os.path.exists(path):
+        head = eng.load_state(path, meta)               # (SetupError names what differs; the file stays)
+        extra = head.get("extra", {})
+        step, solve_before = int(head["step"]), float(extra.get("solve_s", 0.0))
+        in_file = step
+        sums.update({k: int(v) for k, v in extra.get("pairs", {}).items() if k in sums})
+        lines.extend(extra.get("log", []))
+        say(f"Resumed from step {step} of {n_steps} (checkpoint '{path}')")
+    if every is not None:
+        say(f"Checkpoint every {every} time steps to '{path}' (field-decay checks count the run's own steps: no rounding needed)")
+    n_head = len(lines)
+
+    def save():
+        keep = [ln for ln in lines[n_head:] if ln.startswith("- Time step")]
+        t = time.perf_counter()
+        eng.save_state(path, meta, extra={"solve_s": solve_before + (t - t0), "pairs": sums, "log": head_log + keep})
+        return time.perf_counter() - t
+
+    head_log = [ln for ln in lines[:n_head] if ln.startswith("- Time step")]
+    t0 = time.perf_counter()
+    taken, stats, save_s, n_saves = 0, eng.stats(), 0.0, 0
+    while step < n_steps:
+        chunk = n_steps - step
+        if every is not None:
+            chunk = min(chunk, every - step % every)
+        elif time_budget is not None:
+            chunk = min(chunk, CHECKPOINT_TIME_CHUNK)
+        if step_budget is not None:
+            chunk = min(chunk, int(step_budget) - taken)
+        if chunk <= 0 or (time_budget is not None and time.perf_counter() - t0 >= float(time_budget)):
+            if in_file != step:                           # (a budget that ends on a periodic write, or on the step resumed from: the file holds it)
+                save()
+            raise RunSuspended(path, step, n_steps)
+        stats = eng.run(chunk, progress=progress)
+        for k in _PAIR_COUNTERS:
+            sums[k] += int(getattr(stats, k))
+        taken += chunk
+        step = int(stats.steps_done)
+        if stats.stopped_early or stats.diverged:
+            break
+        if every is not None and step < n_steps and step % every == 0:
+            save_s += save()
+            n_saves += 1
+            in_file = step
+    for k in _PAIR_COUNTERS:                              # the schedule line speaks of the whole run
+        setattr(stats, k, sums[k])
+    if n_saves:
+        say(f"Checkpoints written: {n_saves} ({save_s:.4f} s)")
+    if os.path.exists(path):
+        os.remove(path)
+    return stats, solve_before + (time.perf_counter() - t0)
+
+
 def run(simulation, task_name: Optional[str] = None, folder_name: str = "default",
         path: Optional[str] = None, callback_url: Optional[str] = None, verbose: bool = True,
         progress_callback_upload=None, progress_callback_download=None,
@@ -97,7 +250,8 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         mode_grid_dispersion: Optional[bool] = None, flux_time_device: Optional[bool] = None,
         field_time_device: Optional[bool] = None, field_dft_device: Optional[bool] = None,
         projection_device: Optional[bool] = None, exact_projection_device: Optional[bool] = None,
-        rasterize_device: Optional[bool] = None) -> SimulationData:
+        rasterize_device: Optional[bool] = None, checkpoint: Optional[str] = None, checkpoint_steps: Optional[int] = None,
+        step_budget: Optional[int] = None, time_budget: Optional[float] = None) -> SimulationData:
     """Solve ``simulation`` on the local MI355X and return its ``SimulationData``.
 
     Cloud-only arguments (``folder_name``, ``callback_url``, ``progress_callback_*``,
@@ -128,9 +282,25 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
     the material volumes on the device during set-up (True; a scene with any other geometry, a Custom* medium, a Medium2D sheet or a
     medium of the whole-grid node lists takes the host path as a whole), on the host (False), or by
     ``discretize.RASTER_DEVICE_CELLS`` (None: the host); the volumes are the same bit for bit and ``SimulationData.log`` names the
-    path.  One-GPU runs: with more than one GPU in ``devices`` every rank rasterises on the host, and True is refused."""
+    path.  One-GPU runs: with more than one GPU in ``devices`` every rank rasterises on the host, and True is refused.
+    ``checkpoint``: the path of a state file; setting it turns checkpoint and resume on (docs/history/CHECKPOINT.md).  A file there
+    that matches this call — the simulation, the number of steps, the device paths, the library — means the run continues from its
+    time step (the log says ``Resumed from step S of N``); one that does not match raises ``SetupError`` and is left alone.
+    ``checkpoint_steps``: write the file whenever the step count reaches a multiple of it.  ``step_budget`` / ``time_budget``: take
+    at most that many time steps / start no new chunk of steps once that many seconds of solve time have passed in this call; a
+    call that ends before the last step writes the file and raises ``exceptions.RunSuspended`` (``.path``, ``.step``) — the same
+    call again resumes.  A call that reaches the last step, or stops on shutoff, removes the file and returns data that equal,
+    bit for bit, those of the call without these keywords.  One-GPU runs; a budget or ``checkpoint_steps`` needs ``checkpoint``."""
     from .engine import HipEngine
 
+    if checkpoint is None and any(v is not None for v in (checkpoint_steps, step_budget, time_budget)):
+        raise Tidy3dNotImplementedError("checkpoint_steps / step_budget / time_budget without checkpoint= (the path of the state "
+                                        "file) are not supported")
+    if checkpoint_steps is not None and int(checkpoint_steps) < 1:
+        raise Tidy3dNotImplementedError(f"checkpoint_steps={checkpoint_steps}: an interval below 1 time step is not supported")
+    if checkpoint is not None and devices is not None and len(devices) > 1:
+        raise Tidy3dNotImplementedError("checkpoint= together with devices= with more than one GPU is not supported (a z-slab run "
+                                        "needs one state per rank)")
     sim, was_tidy3d = _as_mirror(simulation)
     sim = td.with_nonlinear(sim)      # (Medium placeholders with a NonlinearSpec of NonlinearSusceptibility models become media)
     sim.validate_pre_upload(source_required=True)
@@ -193,8 +363,13 @@ def run(simulation, task_name: Optional[str] = None, folder_name: str = "default
         used_lib = eng.lib                                  # the library that ran the solve also integrates the projections
         setup_s = time.perf_counter() - t_setup
         t0 = time.perf_counter()
-        stats = eng.run(progress=progress if spec.decay_every else None)
-        solve_s = time.perf_counter() - t0
+        if checkpoint is None:
+            stats = eng.run(progress=progress if spec.decay_every else None)
+            solve_s = time.perf_counter() - t0
+        else:
+            meta = _checkpoint_meta(sim, spec, mode_grid_dispersion, eng.lib)
+            stats, solve_s = _run_in_chunks(eng, spec, progress if spec.decay_every else None, lines, verbose, str(checkpoint), meta,
+                                            checkpoint_steps, step_budget, time_budget)
         raw = eng.results()
         from .projection import FLUX_SUFFIX
         raw.update({name + FLUX_SUFFIX: fl for name, fl in eng.lattice_flux().items()})    # DirectivityMonitor surfaces on the device path
