@@ -370,9 +370,16 @@ class OracleFdtd:
             # (the kernels write the wall-tangential E as zero inside the sweep: the curl recovered at a wall node is zero — the
             #  walls are applied here as well, before the coupling reads those nodes)
             self._pec_walls()
+            # (a slot across a Bloch face holds the real node j on the far side and the periods crossed, s = nbr_wrap: that node stands
+            #  for exp(+i sum_a s_a phi_a) E(j), the convention of ``_fwd`` — F[N] = exp(+i phi) F[0].  Factor and product are formed in
+            #  double whatever the field's type and rounded on the way into ``d``; a slot that crosses nothing is not touched)
+            phases = np.asarray(self.bloch, np.float64) if self.bloch is not None else None
             deltas = []
             for st in aniso:
                 d = np.zeros(len(st.ijk), dtype=E[0].dtype)
+                wrap = getattr(st, "nbr_wrap", None) if phases is not None else None
+                if phases is not None and wrap is None:          # (the engine refuses such lists too)
+                    raise ValueError("fully anisotropic lists without wrap signs (nbr_wrap) cannot run with Bloch boundaries")
                 for slot in range(8):
                     b = st.nbr_comp[slot]
                     j = st.nbr_ijk[:, slot]
@@ -382,7 +389,13 @@ class OracleFdtd:
                     cb_b = self.cb[b][kk, jj, ii] if np.ndim(self.cb[b]) else self.cb[b]
                     cb_safe = np.where(cb_b == 0, 1.0, cb_b)
                     curl = np.where(cb_b == 0, 0.0, (E[b][kk, jj, ii] - ca_b * e_prev[b][kk, jj, ii]) / cb_safe)
-                    d[ok] += (spec.dt / _EPS0) * st.g[ok, slot] * curl
+                    term = (spec.dt / _EPS0) * st.g[ok, slot] * curl
+                    if wrap is not None:
+                        s = np.asarray(wrap, np.int64)[ok, slot]
+                        across = s.any(axis=1)
+                        if across.any():
+                            term[across] = term[across] * np.exp(1j * (s[across] @ phases))
+                    d[ok] += term
                 deltas.append(d)
             for st, d in zip(aniso, deltas):
                 E[st.comp][st.ijk[:, 2], st.ijk[:, 1], st.ijk[:, 0]] += d

@@ -106,6 +106,10 @@ class Scenario:
             return np.asarray(s.nbr_ijk), True
         return kerr_slots(self.spec, s.comp, s.ijk)[1], False
 
+    def wraps_of(self, s, e):
+        """what a kind whose lists record the periods crossed adds to the sentence about entry e (tests/aniso_case.py: the signs)"""
+        return ""
+
     def check_inputs(self):
         """what keeps the measure honest: at most SHARE_CAP of the nodes left out, no listed node among them"""
         assert self.share <= SHARE_CAP, f"{self.label}: {100 * self.share:.2f} % of the nodes are excluded"
@@ -124,7 +128,7 @@ class Scenario:
                 empty = int((nbr[e, :, 0] < 0).sum())
                 wrapped = int(((nbr[e, :, 0] >= 0) & (np.abs(nbr[e] - ijk[None, :]) > 1).any(axis=1)).sum())
                 return out + (f"; listed: {self.TAG} list {n} ({ds.COMP[s.comp]}), entry {e} of {len(s.ijk)} (block {e // BLOCK}, lane {e % BLOCK}); "
-                              f"{empty} of its {nbr.shape[1]} slots empty, {wrapped} wrapped" + ("" if read else " (this kind reads no slots)"))
+                              f"{empty} of its {nbr.shape[1]} slots empty, {wrapped} wrapped" + self.wraps_of(s, e) + ("" if read else " (this kind reads no slots)"))
         every = np.concatenate([s.ijk for s in self.lists])
         return out + f"; not listed: {int(np.abs(every - ijk[None, :]).max(axis=1).min())} cells (Chebyshev) from the nearest listed node"
 
@@ -151,7 +155,7 @@ class Scenario:
         print(f"[dense] {self.TAG} {self.label} K={K}{''.join(f' {h}' for h in how)} {what}: nodes {w.value:.3e} | floor {fl.value:.3e} bar {bar:.3e} | "
               f"ratio to floor {w.value / max(fl.value, 1e-300):.2f} | excluded {100 * self.share:.2f} % | lists "
               + " ".join(f"{ds.COMP[s.comp]} {len(s.ijk)}" for s in self.lists))
-        assert w.value <= bar, f"{self.TAG} {self.label} K={K} {how} {what}: node over the bar {bar:.3e} (floor {fl.value:.3e}): {w}"
+        assert w.value <= bar, f"{self.TAG} {self.label} K={K}{''.join(f' {h}' for h in how)} {what}: node over the bar {bar:.3e} (floor {fl.value:.3e}): {w}"
         return w
 
 
@@ -318,6 +322,40 @@ def check_plant(sc, name, spec, named, *how):
     print(f"[plant] {sc.TAG} {sc.label} {name} K={K}: per node {w.value:.3e} = {w.value / bar:.1f} x bar {bar:.3e} | whole-array rel-L2 {l2:.3e} "
           f"(bar 2e-5) | names the planted node: {hit} | {w.at}")
     return K, w, bar, l2, hit
+
+
+L2_BAR = 2e-5                 # the whole-array bar the plants are printed beside
+FACTOR = 4.0                  # a plant stands at least this many bars high
+RELS = (ds.REL, 1e-2, 1e-1)   # a coefficient plant steps up until it does; beyond 1e-1 the measure does not resolve the coefficient
+
+
+def stands(sc, name, spec, named, *how, under_l2=False):
+    K, w, bar, l2, hit = check_plant(sc, name, spec, named, *how)
+    assert w.value >= FACTOR * bar, f"{sc.label} {name} K={K}: {w.value:.3e} is under {FACTOR:g} x the bar {bar:.3e}: {w}"
+    assert hit, f"{sc.label} {name} K={K}: the worst node is not the planted one {named}: {w}"
+    if under_l2:              # ... and the whole-array measure would have let it through
+        assert l2 < L2_BAR, (sc.label, name, K, l2)
+    return K, w, bar, l2
+
+
+def resolved(sc, name, make, named, *how):
+    """the smallest rel of RELS at which the coefficient plant stands; the value is the measure's resolution for that coefficient"""
+    for rel in RELS:
+        K, w, bar, l2, hit = check_plant(sc, f"{name} x (1 + {rel:g})", make(rel), named, *how)
+        if w.value >= FACTOR * bar and hit:
+            print(f"[plant] {sc.TAG} {sc.label} {name}: resolved at rel {rel:g}")
+            return rel, l2
+    raise AssertionError(f"{sc.label} {name}: not resolvable by the per-node measure up to rel {RELS[-1]:g}")
+
+
+def best(size):
+    """(entry, slot) of the candidate at the median of the non-zero sizes: a node like most, chosen by the state alone — the largest
+    candidate is also the one the whole-array figure sees best"""
+    flat = np.flatnonzero(size.reshape(-1) > 0)
+    assert flat.size
+    pick = flat[np.argsort(size.reshape(-1)[flat], kind="stable")[flat.size // 2]]
+    e, slot = np.unravel_index(int(pick), size.shape)
+    return int(e), int(slot)
 
 
 def scenario(cls, label):

@@ -122,6 +122,32 @@ def compare_with_oracle(lib, variant, z, n_steps=80, tol=2e-5):
     assert max(float(np.linalg.norm(f[3 + c] - o.H[c]) / hn) for c in range(3)) < tol
 
 
+def compare_wrapped_with_oracle(lib, variant, n_steps=100, tol=2e-5):
+    """``compare_with_oracle`` for the corner cell, a time and a DFT monitor added: rows that cross the x wrap, the y wrap and both.  The
+    oracle rotates the curl it recovers through such a slot by the Bloch factor (tests/test_aniso_nodes.py pins that factor)."""
+    import dataclasses
+    from cases import rel_err
+    from tidy3d_amd.engine import HipEngine
+    monitors = [td.FieldTimeMonitor(center=(0.3, 0.25, 0.0), size=(0.25, 0.15, 0.1), name="t", colocate=False, interval=7),
+                td.FieldMonitor(center=(0, 0, 0), size=(0.8, 0.6, 0), freqs=[2.5e14, 3e14], name="f")]
+    spec = discretize(dataclasses.replace(wrapped_cell(), monitors=monitors), n_steps=n_steps).spec
+    w = np.concatenate([np.abs(st.nbr_wrap[st.g != 0]).reshape(-1, 3) for st in spec.aniso])
+    assert w[:, 0].any() and w[:, 1].any() and (w[:, 0] & w[:, 1]).any()
+    o = OracleFdtd(spec)
+    ref = o.run()
+    with HipEngine(spec, lib=lib, variant=variant) as e:
+        e.run()
+        got = e.results()
+        f = [e.get_field(c) for c in range(6)]
+    assert set(ref) == {"t", "f"}
+    for k in ref:
+        assert rel_err(got[k], ref[k]) < tol, k
+    en = np.sqrt(sum(np.linalg.norm(x) ** 2 for x in o.E))
+    hn = np.sqrt(sum(np.linalg.norm(x) ** 2 for x in o.H))
+    assert max(float(np.linalg.norm(f[c] - o.E[c]) / en) for c in range(3)) < tol
+    assert max(float(np.linalg.norm(f[3 + c] - o.H[c]) / hn) for c in range(3)) < tol
+
+
 def test_wrap_signs_of_the_coupling_lists():
     """_aniso_sets records the period each slot crossed: +1 beyond the upper face, -1 beyond the lower one, on periodic axes
     only; wrapping the unwrapped neighbour index back into the grid gives nbr_ijk."""
@@ -153,6 +179,11 @@ def test_body_clear_of_the_wraps_matches_the_oracle(variant, z, emu_lib):
 def test_body_across_the_wraps_is_a_translation(variant, emu_lib):
     fa, mapped = translated_fields(emu_lib, L.VARIANT_FUSED if variant == "fused" else L.VARIANT_ZMARCH)
     assert_translation(fa, mapped)
+
+
+@pytest.mark.parametrize("variant", ["fused", "two_pass"])
+def test_body_across_the_wraps_matches_the_oracle(variant, emu_lib):
+    compare_wrapped_with_oracle(emu_lib, L.VARIANT_FUSED if variant == "fused" else L.VARIANT_ZMARCH)
 
 
 def test_bad_wrap_codes_are_refused(emu_lib):

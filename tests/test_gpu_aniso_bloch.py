@@ -1,7 +1,8 @@
 """FullyAnisotropicMedium together with Bloch boundaries on the device (the emulator's pins are in tests/test_aniso_bloch.py):
 
   (a) a body clear of the wraps against the oracle, fused sweep and two-pass kernels;
-  (b) a body cut by the x and y wraps against the same cell translated by whole cells (the phase of the coupling across a wrap);
+  (b) a body cut by the x and y wraps against the same cell translated by whole cells (the phase of the coupling across a wrap),
+      and against the oracle, which carries that phase itself;
   (c) physics: an oblique plane wave through a rotated uniaxial slab that fills the period, against the 4 x 4 transfer matrix —
       co- and cross-polarised transmission and the reflected / transmitted power; the bar is set by the same set-up with an
       isotropic slab (the discretisation's own error: staircased faces, numerical dispersion);
@@ -17,7 +18,8 @@ from tidy3d_amd.data import assemble
 from tidy3d_amd.discretize import discretize
 from tidy3d_amd.engine import HipEngine
 
-from test_aniso_bloch import assert_translation, berreman_slab, compare_with_oracle, rot, translated_fields, vacuum_modes, wrapped_cell
+from test_aniso_bloch import (assert_translation, berreman_slab, compare_with_oracle, compare_wrapped_with_oracle, rot, translated_fields, vacuum_modes,
+                              wrapped_cell)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +36,11 @@ def test_body_clear_of_the_wraps_matches_the_oracle(variant, z, hip_lib):
 def test_body_across_the_wraps_is_a_translation(variant, hip_lib):
     fa, mapped = translated_fields(hip_lib, VARIANTS[variant], n_steps=200)
     assert_translation(fa, mapped)
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_body_across_the_wraps_matches_the_oracle(variant, hip_lib):
+    compare_wrapped_with_oracle(hip_lib, VARIANTS[variant], n_steps=120)
 
 
 # ------------------------------------------------------------------------------------------------------------- (c) physics
